@@ -1,8 +1,12 @@
 #!/usr/bin/env python
 """bench.py -- proposals/sec through the LSM ROI head on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W            (N > 1 without a launcher: starts N ranks itself)
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]   (N > 1 without a launcher: starts N ranks itself)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps of scope S2 (below), writes the last step's outputs when --dump-outputs is given
+and prints the line: `value` (proposals/s), `ms_per_step`, and the roofline of the dominant kernel read from the same timed steps.
+Every other figure below takes runs of its own and comes only with --full.
 
 A step = one pass of the hot path over one batch of synthetic input resident in HBM, THROUGH THE PLUGIN SURFACE the
 reference defines the metric on: `--images` res4 feature maps [B,1024,50,84] (1333x800 images, stride 16)
@@ -15,11 +19,11 @@ and `--proposals` boxes per image as Detectron2-style `Instances` / `Boxes` ->
 
 Images shard over ranks with no data-path collective (inference needs none): weak scaling.
 `value` is scope S2 = the full head as the reference executes it (Res5 included).  Scope S1 = the north-star kernel list only
-(ROIAlign + mean/FCs/similarity on a stand-in for the Res5 output) and the 1024-d bank variants are reported in "scopes".
+(ROIAlign + mean/FCs/similarity on a stand-in for the Res5 output) and the 1024-d bank variants are reported in "scopes" (--full).
 
-`scopes.eval_1img` is the reference's EVALUATION call (TEST.IMS_PER_BATCH 1: one image x 1000 proposals per call through
+`scopes.eval_1img` (--full) is the reference's EVALUATION call (TEST.IMS_PER_BATCH 1: one image x 1000 proposals per call through
 roi_heads(images, features, proposals, None) incl. softmax / box decoding / score threshold / class-wise NMS / top-100), per image.
-The default run's `train` object times one LSM and one STT training step of the path (fixed batch, then `ms_per_step_multiscale`:
+The --full run's `train` object times one LSM and one STT training step of the path (fixed batch, then `ms_per_step_multiscale`:
 a different batch of the reference's real training shapes every step) and, under N ranks or through a one-rank probe, places
 DistributedDataParallel's buckets on the Res5 backward's timeline (`train.gradient_exchange.schedule`).
 
@@ -56,10 +60,17 @@ def parse(argv=None):
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=20)
     p.add_argument("--warmup", type=int, default=5)
+    p.add_argument("--full", action="store_true",
+                   help="also every figure beside the headline: the f32-MFMA reference, scope S1 and its ROIAlign roofline, the 1024-d "
+                        "bank variants, scopes.eval_1img, the compact `train` object and the CPU baseline (the --skip-* / --no-cpu-baseline "
+                        "options select among them).  Without it a run times the S2 headline steps and nothing else")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed S2 step returned (the box predictor's scores and "
+                        "proposal_deltas, rank 0's images) as DIR/<name>.npy in float32 (a fixed row sample above 64 MB in all)")
     p.add_argument("--mode", choices=["infer", "train"], default="infer",
                    help="train: the detailed training report (one --train-config, hip next to the MIOpen-autograd form of the same "
-                        "module).  The default run already carries a compact `train` object: configs 4 and 5 on the hip backend")
-    p.add_argument("--skip-train", action="store_true", help="no `train` object in the default run (profile runs)")
+                        "module).  The --full run already carries a compact `train` object: configs 4 and 5 on the hip backend")
+    p.add_argument("--skip-train", action="store_true", help="no `train` object in the --full run (profile runs)")
     p.add_argument("--images", type=int, default=8, help="images per GPU per step (SURVEY.md 8d: N = 8 / GPU)")
     p.add_argument("--proposals", type=int, default=1000)
     p.add_argument("--classes", type=int, default=1203)
@@ -108,6 +119,11 @@ def parse(argv=None):
     p.add_argument("--skip-exchange-probe", action="store_true",
                    help="no train.gradient_exchange.schedule (the traced DDP steps that place the buckets on the Res5 backward's timeline)")
     args = p.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:
+        # a plain run is the headline alone: as if every option that skips a figure beside it had been given
+        args.skip_f32_reference = args.skip_s1 = args.skip_variants = args.skip_eval = args.skip_train = args.no_cpu_baseline = True
     if args.share_gpu and args.dist_backend == "nccl":
         # RCCL cannot place two ranks on one device (the attempt hangs for minutes before it fails): single-GPU test boxes use gloo
         print("bench.py: --share-gpu implies --dist-backend gloo", file=sys.stderr)
@@ -294,11 +310,21 @@ class Workload:
             self.proposals.append(inst)
         self.boxes = [p.proposal_boxes for p in self.proposals]
         self.heads, _ = build_heads(args, device)
-        self.r5_standin = torch.randn(B * R, 2048, 7, 7, generator=gen).clamp_(min=0).to(device)
+        self._gen = gen         # (r5_standin's: drawn on first use, the generator's last draw, so the same values either way)
         rois = torch.cat([torch.cat([torch.full((R, 1), float(i)), p.proposal_boxes.tensor.cpu()], 1)
                           for i, p in enumerate(self.proposals)]).to(device)
         self.rois = rois
         self.ev = []        # (start, end) events around the dominant hand-written kernel in miopen mode (ROIAlign)
+
+    @property
+    def r5_standin(self):
+        """Scope S1's stand-in for the Res5 output, [B*R, 2048, 7, 7] (3.2 GB at the default size): only S1 reads it."""
+        import torch
+        hit = self.__dict__.get("_r5_standin")
+        if hit is None:
+            B, R = self.args.images, self.args.proposals
+            hit = self._r5_standin = torch.randn(B * R, 2048, 7, 7, generator=self._gen).clamp_(min=0).to(self.device)
+        return hit
 
     def step_s2(self, heads=None, timed=False):
         """_shared_roi_transform -> mean -> box_predictor.forward, through the plugin."""
@@ -620,6 +646,29 @@ def cpu_baseline(args, seconds: float):
                         "sample": f"BASELINE config 1: 2 images x 100 proposals, 80-class bank, median of {runs} runs, {t1:.2f} s each"}}
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, arrays, budget: int = DUMP_BUDGET_BYTES):
+    """--dump-outputs: every array as out_dir/<name>.npy, float64 kept as float64 and every other dtype as float32.  Above `budget`
+    bytes in all, each array keeps the same share of its rows (leading dimension), drawn by a fixed seed: arrays with as many rows
+    keep the same rows, and two runs of the same shapes keep the same ones."""
+    os.makedirs(out_dir, exist_ok=True)
+    host = {}
+    for name, a in arrays.items():
+        if hasattr(a, "detach"):                                   # torch tensor (bf16 has no numpy form: widened on the device)
+            a = a.detach()
+            a = (a if str(a.dtype) == "torch.float64" else a.float()).cpu().numpy()
+        a = np.asarray(a)
+        host[name] = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+    total = sum(a.nbytes for a in host.values())
+    for name, a in host.items():
+        if total > budget and a.ndim and a.shape[0] > 1:
+            keep = max(1, a.shape[0] * budget // total)
+            a = a[np.sort(np.random.default_rng(1992).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -753,9 +802,17 @@ def main():
         return
 
     props_per_step = args.images * args.proposals * world
+    last = {}
+
+    def step_s2(**kw):
+        last["out"] = wl.step_s2(**kw)          # (what the caller receives: kept for --dump-outputs)
     # dominant kernel: the library brackets each of its GEMM-kernel launches with HIP events on the
     # launch stream while this is enabled (include/locov_hip.h, locov_gemm_timing_*)
-    dt2 = timed(wl.step_s2, args.steps, args.warmup, on_start=lambda: lib.locov_gemm_timing_enable(1), key="s2", timed=True)
+    dt2 = timed(step_s2, args.steps, args.warmup, on_start=lambda: lib.locov_gemm_timing_enable(1), key="s2", timed=True)
+    if args.dump_outputs and rank == 0:
+        scores, proposal_deltas = last.pop("out")
+        dump_outputs(args.dump_outputs, {"scores": scores, "proposal_deltas": proposal_deltas})
+    last.clear()
 
     def gemm_class(cls):
         import ctypes
@@ -903,7 +960,7 @@ def main():
 
     train = None
     if args.mode == "infer" and not args.skip_train and args.res5 == "hip" and args.res5_dtype in ("f16x2", "fp32"):
-        # BASELINE configs 4 and 5 in the default line (compact: the hand-written path only; `--mode train` adds the
+        # BASELINE configs 4 and 5 in the --full line (compact: the hand-written path only; `--mode train` adds the
         # MIOpen-autograd form of the same module): one training step of the path per iteration, forward + backward + SGD,
         # wrapped in DistributedDataParallel (RCCL all-reduce of the path's gradients) when there is more than one rank
         train = {"lsm": dict(time_train("lsm", "hip"), config="configs/coco_lsm.yaml",
@@ -1045,7 +1102,7 @@ def main():
             "metric": "proposals/sec through LSM ROI-head (1333x800, 1000 prop, 1203-class text bank)",
             "value": props_per_step * args.steps / dt2,
             "unit": "proposals/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "full": args.full,
             "ms_per_step": dt2 / args.steps * 1e3,
             "per_rank_ms_per_step": per_rank["s2"], "single_steps_ms": step_stats["s2"],
             "timing": {"how": "hipEventElapsedTime between two events on the launch stream around the K timed steps, inside the "

@@ -145,7 +145,7 @@ def _check_bucket_schedule(ex):
 
 def test_bench_starts_its_own_ranks():
     """`python bench.py --gpus 2` with no launcher (it used to run ONE rank and report n_gpus 1)."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu", "--dist-backend", "gloo", "--steps", "2",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu", "--dist-backend", "gloo", "--steps", "2", "--full",
            "--warmup", "1", "--images", "1", "--proposals", "200", "--classes", "80", "--no-cpu-baseline", "--skip-s1",
            "--skip-f32-reference", "--skip-variants", "--skip-eval", "--multiscale-batches", "2"]
     env = _env()
@@ -162,7 +162,7 @@ def test_bench_rehearses_eight_ranks():
     """The driver's SCALE run is the first time eight ranks exist (train_ovnet.py:100-107 launches one process per GPU): rehearse
     the flow on ONE GPU -- `bench.py --gpus 8` starts eight ranks itself, every rank times the inference step and one LSM / STT
     training step under DistributedDataParallel on its own images, and the line names all eight."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--share-gpu", "--dist-backend", "gloo", "--steps", "2",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--share-gpu", "--dist-backend", "gloo", "--steps", "2", "--full",
            "--warmup", "1", "--images", "1", "--proposals", "200", "--classes", "80", "--train-images", "1", "--train-samples", "32",
            "--unfrozen-steps", "0", "--no-cpu-baseline", "--skip-s1", "--skip-f32-reference", "--skip-variants", "--skip-eval", "--multiscale-batches", "2"]
     env = _env()
@@ -188,7 +188,7 @@ def test_rccl_one_rank_rehearsal():
     """RCCL itself on this code (the two-rank tests above share one GPU and therefore run gloo): `bench.py --force-dist` creates the
     RCCL communicator with ONE rank, wraps both training steps in DistributedDataParallel -- its bucketed all-reduce hooks fire
     inside the joint Res5 backward with its side stream, on the RCCL stream -- and takes the timing collectives on device tensors."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-dist", "--dist-backend", "nccl", "--steps", "2",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-dist", "--dist-backend", "nccl", "--steps", "2", "--full",
            "--warmup", "1", "--images", "1", "--proposals", "200", "--classes", "80", "--train-images", "1", "--train-samples", "32",
            "--unfrozen-steps", "0", "--no-cpu-baseline", "--skip-s1", "--skip-f32-reference", "--skip-variants", "--skip-eval", "--multiscale-batches", "2"]
     env = _env()

@@ -400,6 +400,48 @@ def test_bench_refuses_a_pmc_traffic_record_taken_on_other_sources(monkeypatch):
     assert "another workload (differs in proposals)" in bench.traffic_source(args)
 
 
+SKIPS = ("skip_f32_reference", "skip_s1", "skip_variants", "skip_eval", "skip_train", "no_cpu_baseline")
+
+
+def test_bench_plain_run_is_the_headline_alone_and_full_keeps_every_figure():
+    """A plain `bench.py` run times only the headline steps (every figure beside it skipped); --full runs them all, and under
+    --full the --skip-* options still select among them."""
+    import importlib, sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    bench = importlib.import_module("bench")
+    plain = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert not plain.full and plain.steps == 7 and plain.warmup == 3 and plain.dump_outputs is None
+    assert all(getattr(plain, k) for k in SKIPS)
+    full = bench.parse(["--full"])
+    assert full.full and not any(getattr(full, k) for k in SKIPS)
+    some = bench.parse(["--full", "--skip-s1", "--no-cpu-baseline"])
+    assert some.skip_s1 and some.no_cpu_baseline and not (some.skip_eval or some.skip_train or some.skip_variants)
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit):
+            bench.parse(bad)
+
+
+def test_bench_dump_outputs_writes_float_arrays_and_a_fixed_row_sample_above_the_budget(tmp_path):
+    import importlib, sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    bench = importlib.import_module("bench")
+    g = torch.Generator().manual_seed(3)
+    scores, deltas = torch.randn(500, 81, generator=g), torch.randn(500, 4, generator=g).double()
+    bench.dump_outputs(str(tmp_path / "all"), {"scores": scores.bfloat16(), "proposal_deltas": deltas})
+    got_s, got_d = np.load(tmp_path / "all" / "scores.npy"), np.load(tmp_path / "all" / "proposal_deltas.npy")
+    assert got_s.dtype == np.float32 and got_d.dtype == np.float64
+    assert np.array_equal(got_s, scores.bfloat16().float().numpy()) and np.array_equal(got_d, deltas.numpy())
+    # above the budget: the same seeded rows of both arrays, the same on every call, within the budget
+    budget = 40_000
+    for name in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / name), {"scores": scores, "proposal_deltas": deltas}, budget=budget)
+    a_s, a_d = np.load(tmp_path / "a" / "scores.npy"), np.load(tmp_path / "a" / "proposal_deltas.npy")
+    assert a_s.nbytes + a_d.nbytes <= budget and 0 < len(a_s) == len(a_d) < 500
+    assert np.array_equal(a_s, np.load(tmp_path / "b" / "scores.npy"))
+    rows = [int(np.flatnonzero((scores.numpy() == r).all(1))[0]) for r in a_s]
+    assert rows == sorted(rows) and np.array_equal(a_d, deltas.numpy()[rows])
+
+
 def test_stock_library_fallback_is_announced_once_with_the_failed_condition(lsm_cfg):
     """with RES5_BACKEND "hip" a call that cannot take the hand-written Res5 path (odd pooler size,
     non-FrozenBN, grouped 3x3, channels not a multiple of 32, host tensors, a dtype without a backward) runs torch.conv2d --
