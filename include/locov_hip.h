@@ -32,6 +32,7 @@
 extern "C" {
 #endif
 
+/* 8: locov_detect_postprocess; later, additively: locov_grounding_ce_dist_fwd / _bwd, locov_distill_loss_fwd / _bwd */
 #define LOCOV_ABI_VERSION 8
 
 #define LOCOV_OK 0
@@ -536,6 +537,51 @@ int locov_grounding_ce_fwd(const float *cost_w2r, const float *cost_r2w, const f
 int locov_grounding_ce_bwd(const float *cost_w2r, const float *cost_r2w, const float *caption_mask, const float *region_mask, int B,
                            int T, int NR, const float *g_w2r_caption, const float *g_w2r_image, const float *g_r2w_caption,
                            const float *g_r2w_image, float *dcost_w2r, float *dcost_r2w, locov_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
+ * a-12  the same cross-entropy tail when GroundingHead also returns its distributions (MMSS_HEAD.DISTILLATION_LOSS, grounding_head.py:
+ * 380-382 hands {"w2r", "r2w"} to the distillation losses, distill_prop_mmss_gcnn.py:424-442).  Added under ABI version 8.
+ *   _fwd: what locov_grounding_ce_fwd does, and also writes the filled costs pw_w2r / pw_r2w [B, B] (:239-251: the cost where the
+ *     caption has words or the image has regions, else max(cost) + 100 in fp32 -- bit-identical to torch.where(ok, cost,
+ *     cost.max() + 100)).  pw_* is required where cost_* is given.
+ *   _bwd: as locov_grounding_ce_bwd, plus the upstream gradients g_pw_w2r / g_pw_r2w [B, B] of the returned distributions (NULL = 0),
+ *     added to dcost on the ok pairs only: the fill is a detached constant.
+ * ------------------------------------------------------------------------------------- */
+int locov_grounding_ce_dist_fwd(const float *cost_w2r, const float *cost_r2w, const float *caption_mask, const float *region_mask, int B,
+                                int T, int NR, float *out8, float *pw_w2r, float *pw_r2w, locov_stream_t stream);
+int locov_grounding_ce_dist_bwd(const float *cost_w2r, const float *cost_r2w, const float *caption_mask, const float *region_mask, int B,
+                                int T, int NR, const float *g_w2r_caption, const float *g_w2r_image, const float *g_r2w_caption,
+                                const float *g_r2w_image, const float *g_pw_w2r, const float *g_pw_r2w, float *dcost_w2r, float *dcost_r2w,
+                                locov_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
+ * The distillation losses of the LSM meta-architecture over the [B, B] caption x image costs, ONE launch each way (SURVEY 8f-3;
+ * ovr/modeling/meta_arch/distill_mmss_gcnn.py:211-433, called three times per step at distill_prop_mmss_gcnn.py:424-442).
+ * Added under ABI version 8.
+ *   trans [B, B] = the transformer's costs, w2r / r2w [B, B] = GroundingHead's distributions (rows = captions, columns = images).
+ *   A cost matrix is read per image over the captions ("cap": softmax of -cost / temperature over dim 0) and per caption over the
+ *   images ("img": over dim 1).  kind:
+ *     LOCOV_DISTILL_KD   MultiDistillLoss (:211-290): temperature^2 * KL(teacher || student), "batchmean" (sum / B), over
+ *                        {cap, img} x {w2r, r2w}; transformer_teacher != 0: trans teaches w2r and r2w, else w2r and r2w teach trans.
+ *     LOCOV_DISTILL_JS   MultiDistillLossJS (:293-376): 1/2 KL(P || M) + 1/2 KL(Q || M), M = the mixture of the "cap" views; as in
+ *                        the reference (:357-366) the "img" terms are measured against the "cap" mixture too.
+ *     LOCOV_DISTILL_MSE  MultiDistillLossL2 (:379-433): mse(trans, S) + mse(trans^T, S^T) for S = w2r, r2w (temperature unused).
+ *   The result is multiplied by loss_weight.  _fwd writes the scalar *loss.  _bwd takes the device scalar grad_loss = d L / d loss and
+ *   writes grad_trans / grad_w2r / grad_r2w [B, B]; any of them may be NULL (a detached teacher, an input without grad).
+ *   0 * log 0 := 0 as torch.nn.functional.kl_div defines it.  The one intended difference from torch: where a teacher probability
+ *   underflows to exactly 0, torch's teacher gradient there is NaN (d/dp of p log p at 0); the kernel returns the finite limit (0 for
+ *   that element's softmax term).
+ *   1 <= B <= LOCOV_DISTILL_MAX_B, temperature > 0.
+ * ------------------------------------------------------------------------------------- */
+#define LOCOV_DISTILL_KD 0   /* MultiDistillLoss,   distill_mmss_gcnn.py:211-290 */
+#define LOCOV_DISTILL_JS 1   /* MultiDistillLossJS, distill_mmss_gcnn.py:293-376 */
+#define LOCOV_DISTILL_MSE 2  /* MultiDistillLossL2, distill_mmss_gcnn.py:379-433 */
+#define LOCOV_DISTILL_MAX_B 64 /* B = IMS_PER_BATCH per GPU (configs/coco_lsm.yaml: 32 over 8 GPUs = 4) */
+int locov_distill_loss_fwd(const float *trans, const float *w2r, const float *r2w, int B, int kind, int transformer_teacher,
+                           float temperature, float loss_weight, float *loss, locov_stream_t stream);
+int locov_distill_loss_bwd(const float *trans, const float *w2r, const float *r2w, int B, int kind, int transformer_teacher,
+                           float temperature, float loss_weight, const float *grad_loss, float *grad_trans, float *grad_w2r,
+                           float *grad_r2w, locov_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * Backward of the predictor's dense layers under autograd (locov_pool_fc_bwd, locov_sim_gemm_bwd; the

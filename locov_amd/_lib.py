@@ -28,6 +28,7 @@ ZERO_LIST_MAX = 24
 LABEL_MAX_IMAGES, LABEL_MAX_THRESHOLDS, SAMPLE_MAX_PROPOSALS = 64, 6, 4096
 ABI_VERSION = 8
 DETECT_MAX_CANDIDATES, DETECT_FLAG_NONFINITE, DETECT_FLAG_OVERFLOW = 8192, 1, 2
+DISTILL_KD, DISTILL_JS, DISTILL_MSE, DISTILL_MAX_B = 0, 1, 2, 64
 
 _p = c_void_p  # device pointer
 
@@ -90,6 +91,10 @@ SIGNATURES = {
     "locov_box_reg_loss": (c_int, [_p, _p, _p, c_int64, _p, c_int64, c_int64, c_float, c_float, c_float, c_float, c_float, _p, _p, _p]),
     "locov_grounding_ce_fwd": (c_int, [_p, _p, _p, _p, c_int, c_int, c_int, _p, _p]),
     "locov_grounding_ce_bwd": (c_int, [_p, _p, _p, _p, c_int, c_int, c_int, _p, _p, _p, _p, _p, _p, _p]),
+    "locov_grounding_ce_dist_fwd": (c_int, [_p, _p, _p, _p, c_int, c_int, c_int, _p, _p, _p, _p]),
+    "locov_grounding_ce_dist_bwd": (c_int, [_p, _p, _p, _p, c_int, c_int, c_int, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "locov_distill_loss_fwd": (c_int, [_p, _p, _p, c_int, c_int, c_int, c_float, c_float, _p, _p]),
+    "locov_distill_loss_bwd": (c_int, [_p, _p, _p, c_int, c_int, c_int, c_float, c_float, _p, _p, _p, _p, _p]),
     "locov_nms_workspace_bytes": (c_int64, [c_int64]),
     "locov_nms_sorted": (c_int, [_p, c_int64, c_float, _p, _p, _p, _p]),
     "locov_detect_postprocess_workspace_bytes": (c_int64, [c_int64, c_int]),

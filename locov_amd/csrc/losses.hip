@@ -1,4 +1,4 @@
-// The two scalar-sized loss tails of a training step, each as ONE launch instead of a chain of ~40 small torch launches (and as many
+// The scalar-sized loss tails of a training step, each as ONE launch instead of a chain of ~40 small torch launches (and as many
 // again in autograd's backward): what a step of the LSM / STT configurations spends on them is launch gaps, not work.
 //
 //   * locov_box_reg_loss -- [D2-upstream] FastRCNNOutputLayers.box_reg_loss as the reference's heads call it
@@ -7,7 +7,10 @@
 //     number of ALL rows; the gradient with respect to the predictions comes out of the same launch.
 //   * locov_grounding_ce_fwd / _bwd -- the cross-entropy tail of GroundingHead.forward (ovr/modeling/mmss_heads/grounding_head.py:
 //     239-251 the "(max + 100)" replacement of pairs with neither words nor regions, :273-290 log_softmax over captions and over
-//     images + the diagonal means, :357-377 the batch accuracies) on the [B, B] caption x image cost matrices of locov_grounding_fwd.
+//     images + the diagonal means, :357-377 the batch accuracies) on the [B, B] caption x image cost matrices of locov_grounding_fwd;
+//     locov_grounding_ce_dist_fwd / _bwd the same launch when the head also returns the filled costs (DISTILLATION_LOSS).
+//   * locov_distill_loss_fwd / _bwd -- MultiDistillLoss / MultiDistillLossJS / MultiDistillLossL2 (ovr/modeling/meta_arch/
+//     distill_mmss_gcnn.py:211-433) on the transformer's and the grounding head's [B, B] costs, one workgroup, all three staged in LDS.
 //
 // Built with -ffp-contract=off: each step is the torch op it replaces, rounded on its own; the sums run in a fixed order (one
 // workgroup, a fixed tree), so a step's losses are reproducible run to run.
@@ -108,12 +111,15 @@ __global__ __launch_bounds__(kLossThreads) void box_reg_loss_kernel(const float4
 
 // out[tag * 4 + k], tag 0 = cost0 ("Words": w2r), 1 = cost1 ("Regions": r2w); k: 0 = CE choose caption (softmax over dim 0),
 // 1 = CE choose image (dim 1), 2 / 3 = the batch accuracies of the same two directions.  GRAD: d(sum_k up[tag*2+k] * CE_k) / d cost.
-template <bool GRAD>
-__global__ __launch_bounds__(kLossThreads) void grounding_ce_kernel(const float *__restrict__ cost0, const float *__restrict__ cost1,
-                                                                    const float *__restrict__ cmask, const float *__restrict__ rmask, int B,
-                                                                    int T, int NR, float *__restrict__ out, const float *up0,
-                                                                    const float *up1, const float *up2, const float *up3,
-                                                                    float *__restrict__ d0, float *__restrict__ d1)
+// DIST (the head also returns its distributions): the forward writes the filled costs pw0 / pw1, the backward adds their upstream
+// gradients gpw0 / gpw1 (either may be null) on the ok pairs.
+template <bool GRAD, bool DIST>
+__device__ __forceinline__ void grounding_ce_body(const float *__restrict__ cost0, const float *__restrict__ cost1,
+                                                  const float *__restrict__ cmask, const float *__restrict__ rmask, int B, int T, int NR,
+                                                  float *__restrict__ out, const float *up0, const float *up1, const float *up2,
+                                                  const float *up3, float *__restrict__ d0, float *__restrict__ d1,
+                                                  float *__restrict__ pw0, float *__restrict__ pw1, const float *__restrict__ gpw0,
+                                                  const float *__restrict__ gpw1)
 {
     __shared__ float red[kLossThreads];
     __shared__ float z[LOCOV_GROUNDING_CE_MAX_B * LOCOV_GROUNDING_CE_MAX_B];       // -cost' of the current tag
@@ -131,14 +137,19 @@ __global__ __launch_bounds__(kLossThreads) void grounding_ce_kernel(const float 
     __syncthreads();
     for (int tag = 0; tag < 2; tag++) {
         const float *cost = tag ? cost1 : cost0;
-        if (!cost) continue;                                  // (workgroup-uniform)
+        if (!cost) {                                          // (workgroup-uniform)
+            if (DIST && !GRAD && t < 4) out[tag * 4 + t] = 0.f;   // (the plain entry's caller zero-fills out8 itself)
+            continue;
+        }
         float m = -INFINITY;
         for (int e = t; e < BB; e += kLossThreads) m = fmaxf(m, cost[e]);
         const float fill = block_max(m, red) + 100.0f;       // pairs with neither words nor regions: max + 100 (:239-251)
         for (int e = t; e < BB; e += kLossThreads) {
             const int i = e / B, j = e - i * B;
             const bool ok = nw[i] > 0.f || nr[j] > 0.f;
-            z[e] = -(ok ? cost[e] : fill);
+            const float c = ok ? cost[e] : fill;
+            z[e] = -c;
+            if (DIST && !GRAD) (tag ? pw1 : pw0)[e] = c;
         }
         __syncthreads();
         // log_softmax's pieces: x - max - log(sum exp(x - max)), per column (dim 0) and per row (dim 1)
@@ -185,10 +196,219 @@ __global__ __launch_bounds__(kLossThreads) void grounding_ce_kernel(const float 
                 const bool ok = nw[i] > 0.f || nr[j] > 0.f;
                 const float pcol = expf((z[e] - cmx[j]) - cls_[j]), prow = expf((z[e] - rmx[i]) - rls_[i]);
                 const float dz = gc * (pcol - (i == j ? 1.f : 0.f)) + gi * (prow - (i == j ? 1.f : 0.f));
-                d[e] = ok ? -dz : 0.f;                        // z = -cost'; the replaced pairs are constants
+                float dc = -dz;                               // z = -cost'; the replaced pairs are constants
+                if (DIST) {
+                    const float *gp = tag ? gpw1 : gpw0;
+                    if (gp) dc = dc + gp[e];
+                }
+                d[e] = ok ? dc : 0.f;
             }
         }
         __syncthreads();
+    }
+}
+
+template <bool GRAD>
+__global__ __launch_bounds__(kLossThreads) void grounding_ce_kernel(const float *__restrict__ cost0, const float *__restrict__ cost1,
+                                                                    const float *__restrict__ cmask, const float *__restrict__ rmask, int B,
+                                                                    int T, int NR, float *__restrict__ out, const float *up0,
+                                                                    const float *up1, const float *up2, const float *up3,
+                                                                    float *__restrict__ d0, float *__restrict__ d1)
+{
+    grounding_ce_body<GRAD, false>(cost0, cost1, cmask, rmask, B, T, NR, out, up0, up1, up2, up3, d0, d1, nullptr, nullptr, nullptr,
+                                   nullptr);
+}
+
+template <bool GRAD>
+__global__ __launch_bounds__(kLossThreads) void grounding_ce_dist_kernel(const float *__restrict__ cost0, const float *__restrict__ cost1,
+                                                                         const float *__restrict__ cmask, const float *__restrict__ rmask,
+                                                                         int B, int T, int NR, float *__restrict__ out, const float *up0,
+                                                                         const float *up1, const float *up2, const float *up3,
+                                                                         float *__restrict__ d0, float *__restrict__ d1,
+                                                                         float *__restrict__ pw0, float *__restrict__ pw1,
+                                                                         const float *__restrict__ gpw0, const float *__restrict__ gpw1)
+{
+    grounding_ce_body<GRAD, true>(cost0, cost1, cmask, rmask, B, T, NR, out, up0, up1, up2, up3, d0, d1, pw0, pw1, gpw0, gpw1);
+}
+
+
+// ---- the distillation losses (locov_distill_loss_fwd / _bwd; include/locov_hip.h states the arithmetic) ----
+constexpr int kDistMaxB = LOCOV_DISTILL_MAX_B;
+
+// Matrix X = 0 trans, 1 w2r, 2 r2w, staged as z = -cost / temperature; per column (softmax over dim 0, the "cap" view) and per row
+// (dim 1, "img"): max, sum of exp(z - max) and its log -- softmax = exp(z - max) / sum and log_softmax = (z - max) - log(sum), as
+// torch's softmax / log_softmax epilogues round them.
+struct DistillSmem {
+    float z[3][kDistMaxB * kDistMaxB];
+    float cmx[3][kDistMaxB], csum[3][kDistMaxB], clse[3][kDistMaxB];
+    float rmx[3][kDistMaxB], rsum[3][kDistMaxB], rlse[3][kDistMaxB];
+    float aux[6][kDistMaxB];                                  // per-slice sums of the backward
+    float red[kLossThreads];
+};
+
+struct DistillView {
+    const DistillSmem &s;
+    int B;
+    __device__ __forceinline__ float zz(int X, int i, int j) const { return s.z[X][i * B + j]; }
+    __device__ __forceinline__ float pcol(int X, int i, int j) const { return expf(zz(X, i, j) - s.cmx[X][j]) / s.csum[X][j]; }
+    __device__ __forceinline__ float lcol(int X, int i, int j) const { return (zz(X, i, j) - s.cmx[X][j]) - s.clse[X][j]; }
+    __device__ __forceinline__ float prow(int X, int i, int j) const { return expf(zz(X, i, j) - s.rmx[X][i]) / s.rsum[X][i]; }
+    __device__ __forceinline__ float lrow(int X, int i, int j) const { return (zz(X, i, j) - s.rmx[X][i]) - s.rlse[X][i]; }
+    // JS: the "cap" mixture of trans and cost X, and d L / d M at (i, j) up to the scale k (0 where M == 0: every path from M
+    // to the logits there is multiplied by a zero probability -- the finite limit of torch's 0 * (-inf))
+    __device__ __forceinline__ float mix(int X, int i, int j) const { return 0.5f * (pcol(0, i, j) + pcol(X, i, j)); }
+    __device__ __forceinline__ float js_gm(int X, int i, int j, float k) const
+    {
+        const float m = mix(X, i, j);
+        if (m == 0.f) return 0.f;
+        const float lsum = ((lcol(0, i, j) + lcol(X, i, j)) + lrow(0, j, i)) + lrow(X, j, i);
+        return k * (4.f * logf(m) - lsum);
+    }
+};
+
+// xlogy(x, x) as kl_div's target term forms it: 0 where x == 0
+__device__ __forceinline__ float xlogx(float x) { return x == 0.f ? 0.f : x * logf(x); }
+
+template <bool GRAD>
+__global__ __launch_bounds__(kLossThreads) void distill_loss_kernel(const float *__restrict__ trans, const float *__restrict__ w2r,
+                                                                    const float *__restrict__ r2w, int B, int kind, int tt,
+                                                                    float temperature, float loss_weight, float *__restrict__ loss,
+                                                                    const float *__restrict__ gloss, float *__restrict__ dtrans,
+                                                                    float *__restrict__ dw2r, float *__restrict__ dr2w)
+{
+    __shared__ DistillSmem s;
+    const int t = threadIdx.x, BB = B * B;
+    const float nb = (float)B;
+    const float g = GRAD ? gloss[0] * loss_weight : 0.f;       // d L / d (the sum before loss_weight)
+    if (kind == LOCOV_DISTILL_MSE) {
+        // mse(trans, S) + mse(trans^T, S^T): the same mean counted twice, for S = w2r then r2w
+        const float n = (float)BB;
+        float s1 = 0.f, s2 = 0.f;
+        for (int e = t; e < BB; e += kLossThreads) {
+            const float a = trans[e] - w2r[e], b = trans[e] - r2w[e];
+            if (GRAD) {
+                const float ga = (2.f / n) * a * g, gb = (2.f / n) * b * g;    // mse_loss_backward: 2 / N * (x - y) * grad
+                if (dtrans) dtrans[e] = (ga + ga) + (gb + gb);
+                if (dw2r) dw2r[e] = -(ga + ga);
+                if (dr2w) dr2w[e] = -(gb + gb);
+            } else {
+                s1 = s1 + a * a;
+                s2 = s2 + b * b;
+            }
+        }
+        if (!GRAD) {
+            const float m1 = block_sum(s1, s.red) / n, m2 = block_sum(s2, s.red) / n;
+            if (t == 0) loss[0] = (((m1 + m1) + m2) + m2) * loss_weight;
+        }
+        return;
+    }
+    // stage z = -cost / temperature (torch on the device: a negation, then a multiplication by the fp32 reciprocal)
+    const float inv_t = 1.0f / temperature;
+    for (int e = t; e < 3 * BB; e += kLossThreads) {
+        const int X = e / BB, k = e - X * BB;
+        const float *src = X == 0 ? trans : (X == 1 ? w2r : r2w);
+        s.z[X][k] = -src[k] * inv_t;
+    }
+    __syncthreads();
+    for (int u = t; u < 6 * B; u += kLossThreads) {
+        const int X = u / (2 * B), r = u - X * 2 * B;
+        const bool col = r < B;
+        const int k = col ? r : r - B;
+        const float *zx = s.z[X];
+        float mx = -INFINITY;
+        for (int v = 0; v < B; v++) mx = fmaxf(mx, col ? zx[v * B + k] : zx[k * B + v]);
+        float sm = 0.f;
+        for (int v = 0; v < B; v++) sm = sm + expf((col ? zx[v * B + k] : zx[k * B + v]) - mx);
+        (col ? s.cmx : s.rmx)[X][k] = mx;
+        (col ? s.csum : s.rsum)[X][k] = sm;
+        (col ? s.clse : s.rlse)[X][k] = logf(sm);
+    }
+    __syncthreads();
+    const DistillView v{s, B};
+    const bool js = kind == LOCOV_DISTILL_JS;
+    const float t2 = temperature * temperature;
+    if (!GRAD) {
+        // KD: sum over the two (teacher, student) pairs and both views of p_t log p_t - p_t log q_s; JS: over both costs of the four
+        // kl_div(log ., M) terms (cap and img view of trans and of the cost, all against the cap mixture M)
+        float part = 0.f;
+        for (int e = t; e < BB; e += kLossThreads) {
+            const int i = e / B, j = e - i * B;
+#pragma unroll
+            for (int X = 1; X <= 2; X++) {
+                if (js) {
+                    const float m = v.mix(X, i, j), xm = xlogx(m);
+                    part = part + ((((xm - m * v.lcol(0, i, j)) + (xm - m * v.lcol(X, i, j))) + (xm - m * v.lrow(0, j, i))) +
+                                   (xm - m * v.lrow(X, j, i)));
+                } else {
+                    const int te = tt ? 0 : X, st = tt ? X : 0;
+                    const float pc = v.pcol(te, i, j), pr = v.prow(te, i, j);
+                    part = part + ((xlogx(pc) - pc * v.lcol(st, i, j)) + (xlogx(pr) - pr * v.lrow(st, i, j)));
+                }
+            }
+        }
+        const float total = block_sum(part, s.red) / nb;
+        if (t == 0) loss[0] = (js ? 0.5f * (total * t2) : total * t2) * loss_weight;
+        return;
+    }
+    const float k = (js ? 0.5f : 1.f) * g * t2 / nb;          // d L / d (each element's term)
+    // per-slice sums.  KD: aux[2 p + 0][j] = sum_i p_t (l_t - l_s) over column j, aux[2 p + 1][i] the same over row i, for the pair
+    // p = (teacher, student) of cost X = p + 1.  JS, cost X = c + 1: aux[3 c][j] = column sums of M, aux[3 c + 1][j] / aux[3 c + 2][j]
+    // = column sums of p_cap(trans) * dP / p_cap(cost) * dP, dP = d L / d p_cap = 1/2 d L / d M.
+    const int ntask = (js ? 6 : 4) * B;
+    for (int u = t; u < ntask; u += kLossThreads) {
+        const int a = u / B, q = u - a * B;
+        float acc = 0.f;
+        if (js) {
+            const int X = a / 3 + 1, w = a % 3;
+            for (int i = 0; i < B; i++) {
+                if (w == 0) acc = acc + v.mix(X, i, q);
+                else acc = acc + v.pcol(w == 1 ? 0 : X, i, q) * (0.5f * v.js_gm(X, i, q, k));
+            }
+        } else {
+            const int X = a / 2 + 1, te = tt ? 0 : X, st = tt ? X : 0;
+            for (int r = 0; r < B; r++) {
+                if ((a & 1) == 0) acc = acc + v.pcol(te, r, q) * (v.lcol(te, r, q) - v.lcol(st, r, q));
+                else acc = acc + v.prow(te, q, r) * (v.lrow(te, q, r) - v.lrow(st, q, r));
+            }
+        }
+        s.aux[a][q] = acc;
+    }
+    __syncthreads();
+    for (int e = t; e < BB; e += kLossThreads) {
+        const int i = e / B, j = e - i * B;
+        float d0 = 0.f, d1 = 0.f, d2 = 0.f;                    // d L / d z of trans, w2r, r2w
+#pragma unroll
+        for (int X = 1; X <= 2; X++) {
+            float &dx = X == 1 ? d1 : d2;
+            if (js) {
+                const int c = X - 1;
+                const float dp = 0.5f * v.js_gm(X, i, j, k);
+                const float mij = v.mix(X, i, j), mji = v.mix(X, j, i);
+                const float *cm = s.aux[3 * c];
+                // through p_cap (softmax over dim 0), log_softmax over dim 0 (cap view), log_softmax over dim 1 read transposed (img)
+                const float pa = v.pcol(0, i, j), px = v.pcol(X, i, j);
+                d0 = d0 + ((pa * (dp - s.aux[3 * c + 1][j]) + (-k * mij + pa * (k * cm[j]))) + (-k * mji + v.prow(0, i, j) * (k * cm[i])));
+                dx = dx + ((px * (dp - s.aux[3 * c + 2][j]) + (-k * mij + px * (k * cm[j]))) + (-k * mji + v.prow(X, i, j) * (k * cm[i])));
+            } else {
+                const int te = tt ? 0 : X, st = tt ? X : 0;
+                const float pct = v.pcol(te, i, j), prt = v.prow(te, i, j);
+                // teacher: p_t (l_t - l_s - sum_slice p_t (l_t - l_s)), 0 where p_t == 0; student: p_s - p_t
+                const float gt = k * (pct * ((v.lcol(te, i, j) - v.lcol(st, i, j)) - s.aux[2 * (X - 1)][j]) +
+                                      prt * ((v.lrow(te, i, j) - v.lrow(st, i, j)) - s.aux[2 * (X - 1) + 1][i]));
+                const float gs = k * ((v.pcol(st, i, j) - pct) + (v.prow(st, i, j) - prt));
+                if (tt) {
+                    d0 = d0 + gt;
+                    dx = dx + gs;
+                } else {
+                    d0 = d0 + gs;
+                    dx = dx + gt;
+                }
+            }
+        }
+        // z = -cost / temperature
+        if (dtrans) dtrans[e] = -(d0 * inv_t);
+        if (dw2r) dw2r[e] = -(d1 * inv_t);
+        if (dr2w) dr2w[e] = -(d2 * inv_t);
     }
 }
 
@@ -238,4 +458,73 @@ extern "C" int locov_grounding_ce_bwd(const float *cost_w2r, const float *cost_r
     hipLaunchKernelGGL(grounding_ce_kernel<true>, dim3(1), dim3(kLossThreads), 0, as_stream(stream), cost_w2r, cost_r2w, caption_mask,
                        region_mask, B, T, NR, nullptr, g_w2r_caption, g_w2r_image, g_r2w_caption, g_r2w_image, dcost_w2r, dcost_r2w);
     return check_launch("locov_grounding_ce_bwd");
+}
+
+static int grounding_ce_dist_args(const float *c0, const float *c1, const float *cm, const float *rm, int B, int T, int NR)
+{
+    using namespace locov;
+    LOCOV_REQUIRE(B >= 1 && B <= LOCOV_GROUNDING_CE_MAX_B && T >= 0 && NR >= 0, "locov_grounding_ce_dist: 1 <= B <= %d",
+                  LOCOV_GROUNDING_CE_MAX_B);
+    LOCOV_REQUIRE((c0 || c1) && cm && rm, "locov_grounding_ce_dist: null pointer");
+    return LOCOV_OK;
+}
+
+extern "C" int locov_grounding_ce_dist_fwd(const float *cost_w2r, const float *cost_r2w, const float *caption_mask, const float *region_mask,
+                                           int B, int T, int NR, float *out8, float *pw_w2r, float *pw_r2w, locov_stream_t stream)
+{
+    using namespace locov;
+    if (int rc = grounding_ce_dist_args(cost_w2r, cost_r2w, caption_mask, region_mask, B, T, NR)) return rc;
+    LOCOV_REQUIRE(out8 && (!cost_w2r || pw_w2r) && (!cost_r2w || pw_r2w), "locov_grounding_ce_dist_fwd: null output");
+    hipLaunchKernelGGL(grounding_ce_dist_kernel<false>, dim3(1), dim3(kLossThreads), 0, as_stream(stream), cost_w2r, cost_r2w, caption_mask,
+                       region_mask, B, T, NR, out8, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, pw_w2r, pw_r2w, nullptr, nullptr);
+    return check_launch("locov_grounding_ce_dist_fwd");
+}
+
+extern "C" int locov_grounding_ce_dist_bwd(const float *cost_w2r, const float *cost_r2w, const float *caption_mask, const float *region_mask,
+                                           int B, int T, int NR, const float *g_w2r_caption, const float *g_w2r_image,
+                                           const float *g_r2w_caption, const float *g_r2w_image, const float *g_pw_w2r,
+                                           const float *g_pw_r2w, float *dcost_w2r, float *dcost_r2w, locov_stream_t stream)
+{
+    using namespace locov;
+    if (int rc = grounding_ce_dist_args(cost_w2r, cost_r2w, caption_mask, region_mask, B, T, NR)) return rc;
+    LOCOV_REQUIRE((!cost_w2r || dcost_w2r) && (!cost_r2w || dcost_r2w), "locov_grounding_ce_dist_bwd: null gradient output");
+    hipLaunchKernelGGL(grounding_ce_dist_kernel<true>, dim3(1), dim3(kLossThreads), 0, as_stream(stream), cost_w2r, cost_r2w, caption_mask,
+                       region_mask, B, T, NR, nullptr, g_w2r_caption, g_w2r_image, g_r2w_caption, g_r2w_image, dcost_w2r, dcost_r2w,
+                       nullptr, nullptr, cost_w2r ? g_pw_w2r : nullptr, cost_r2w ? g_pw_r2w : nullptr);
+    return check_launch("locov_grounding_ce_dist_bwd");
+}
+
+static int distill_args(const float *trans, const float *w2r, const float *r2w, int B, int kind, float temperature)
+{
+    using namespace locov;
+    LOCOV_REQUIRE(B >= 1 && B <= LOCOV_DISTILL_MAX_B, "locov_distill_loss: 1 <= B <= %d", LOCOV_DISTILL_MAX_B);
+    LOCOV_REQUIRE(kind == LOCOV_DISTILL_KD || kind == LOCOV_DISTILL_JS || kind == LOCOV_DISTILL_MSE, "locov_distill_loss: unknown kind %d",
+                  kind);
+    LOCOV_REQUIRE(temperature > 0.f, "locov_distill_loss: temperature must be > 0");
+    LOCOV_REQUIRE(trans && w2r && r2w, "locov_distill_loss: null pointer");
+    return LOCOV_OK;
+}
+
+extern "C" int locov_distill_loss_fwd(const float *trans, const float *w2r, const float *r2w, int B, int kind, int transformer_teacher,
+                                      float temperature, float loss_weight, float *loss, locov_stream_t stream)
+{
+    using namespace locov;
+    if (int rc = distill_args(trans, w2r, r2w, B, kind, temperature)) return rc;
+    LOCOV_REQUIRE(loss, "locov_distill_loss_fwd: null output");
+    hipLaunchKernelGGL(distill_loss_kernel<false>, dim3(1), dim3(kLossThreads), 0, as_stream(stream), trans, w2r, r2w, B, kind,
+                       transformer_teacher ? 1 : 0, temperature, loss_weight, loss, nullptr, nullptr, nullptr, nullptr);
+    return check_launch("locov_distill_loss_fwd");
+}
+
+extern "C" int locov_distill_loss_bwd(const float *trans, const float *w2r, const float *r2w, int B, int kind, int transformer_teacher,
+                                      float temperature, float loss_weight, const float *grad_loss, float *grad_trans, float *grad_w2r,
+                                      float *grad_r2w, locov_stream_t stream)
+{
+    using namespace locov;
+    if (int rc = distill_args(trans, w2r, r2w, B, kind, temperature)) return rc;
+    LOCOV_REQUIRE(grad_loss, "locov_distill_loss_bwd: null grad_loss");
+    if (!grad_trans && !grad_w2r && !grad_r2w) return LOCOV_OK;      // nothing asks for a gradient
+    hipLaunchKernelGGL(distill_loss_kernel<true>, dim3(1), dim3(kLossThreads), 0, as_stream(stream), trans, w2r, r2w, B, kind,
+                       transformer_teacher ? 1 : 0, temperature, loss_weight, nullptr, grad_loss, grad_trans, grad_w2r, grad_r2w);
+    return check_launch("locov_distill_loss_bwd");
 }

@@ -3,7 +3,10 @@
 Same class names, constructor arguments and `forward(trans_pw_cost, pw_cost_w2r, pw_cost_r2w)` as
 ovr/modeling/meta_arch/distill_mmss_gcnn.py:211-433 (selected in distill_prop_mmss_gcnn.py:127-149);
 the two student matrices are the "w2r" / "r2w" outputs of GroundingHead.forward (grounding_head.py).
-B is the per-GPU batch (4 at 8 GPUs), so this is scalar-sized torch arithmetic -- no kernel.
+B is the per-GPU batch (4 at 8 GPUs): a few dozen scalar-sized torch launches per call, each way.  With the three costs fp32 on
+the device, B <= ops.DISTILL_MAX_B and LOCOV_FUSED_LOSSES not "0", a call is ONE kernel forward and one backward instead
+(ops.distill_loss = locov_distill_loss_fwd / _bwd); anything else -- CPU, fp64 or half tensors, larger B -- runs the torch code
+below unchanged.
 
 A cost matrix is read two ways: per image over the captions (softmax over dim 0, "cap") and per caption
 over the images (softmax over dim 1, transposed, "img").  Every loss is the sum over
@@ -11,8 +14,12 @@ over the images (softmax over dim 1, transposed, "img").  Every loss is the sum 
 """
 from __future__ import annotations
 
+import os
+
 import torch
 from torch import nn
+
+from . import ops
 
 __all__ = ["MultiDistillLoss", "MultiDistillLossJS", "MultiDistillLossL2"]
 
@@ -37,6 +44,14 @@ class _DistillBase(nn.Module):
         self.detach_teacher = detach_teacher
         self.transformer_teacher = transformer_teacher
 
+    def _fused(self, trans, w2r, r2w) -> bool:
+        """The one-launch path applies: three fp32 device [B, B] costs, B <= ops.DISTILL_MAX_B, the fused-loss switch on."""
+        B = trans.shape[0] if trans.dim() == 2 else 0
+        return (1 <= B <= ops.DISTILL_MAX_B
+                and all(c.is_cuda and c.dtype == torch.float32 and tuple(c.shape) == (B, B) for c in (trans, w2r, r2w))
+                and isinstance(self.temp, (int, float)) and self.temp > 0 and isinstance(self.loss_weight, (int, float))
+                and os.environ.get("LOCOV_FUSED_LOSSES", "1") != "0")
+
     def _detach(self, trans, w2r, r2w):
         if self.detach_teacher:
             if self.transformer_teacher:
@@ -52,6 +67,8 @@ class MultiDistillLoss(_DistillBase):
 
     def forward(self, trans_pw_cost, pw_cost_w2r, pw_cost_r2w):
         trans, w2r, r2w = self._detach(trans_pw_cost, pw_cost_w2r, pw_cost_r2w)
+        if self._fused(trans, w2r, r2w):
+            return ops.distill_loss("kd", trans, w2r, r2w, self.temp, self.loss_weight, self.transformer_teacher)
         t2 = self.temp * self.temp
         total = 0.0
         if self.transformer_teacher:
@@ -74,6 +91,8 @@ class MultiDistillLossJS(_DistillBase):
 
     def forward(self, trans_pw_cost, pw_cost_w2r, pw_cost_r2w):
         trans, w2r, r2w = self._detach(trans_pw_cost, pw_cost_w2r, pw_cost_r2w)
+        if self._fused(trans, w2r, r2w):
+            return ops.distill_loss("js", trans, w2r, r2w, self.temp, self.loss_weight, self.transformer_teacher)
         t2 = self.temp * self.temp
         p_cap, _ = _views(trans, self.temp, log=False)
         logp = _views(trans, self.temp, log=True)
@@ -92,6 +111,8 @@ class MultiDistillLossL2(_DistillBase):
 
     def forward(self, trans_pw_cost, pw_cost_w2r, pw_cost_r2w):
         trans, w2r, r2w = self._detach(trans_pw_cost, pw_cost_w2r, pw_cost_r2w)
+        if self._fused(trans, w2r, r2w):
+            return ops.distill_loss("mse", trans, w2r, r2w, self.temp, self.loss_weight, self.transformer_teacher)
         mse = torch.nn.functional.mse_loss
         total = 0.0
         for cost in (w2r, r2w):

@@ -8,8 +8,8 @@ ALIGNMENT "softmax", LOSS "cross_entropy" -- is the hot path: instead of materia
 the captions, regions and masks (:119-144) and running ~30 elementwise launches on [B^2, T, NR]
 tensors with a host sync per logged tensor (`LoggedModule.log`), the region embeddings and the
 caption tokens meet in ONE [B*T, B*NR] GEMM and one fused kernel reduces each T x NR block to its
-two cost entries (csrc/grounding.hip).  The B x B cross-entropy tail stays on torch ops (a few dozen
-scalars).
+two cost entries (csrc/grounding.hip).  The B x B cross-entropy tail is one more launch each way
+(csrc/losses.hip), with or without the distributions DISTILLATION_LOSS asks for.
 
 The other variants the reference defines -- ALIGNMENT hardmax / random_categorical / random_top3
 (:169-208), GLOBAL_METRIC reconstruction_mse (:215-224), LOSS triplet with hardest / easiest / random
@@ -84,11 +84,15 @@ class GroundingHead(nn.Module):
         # :150-228 temperature, masked softmax both ways, aligned-local distances -> [caption, image] costs
         cost_w2r, cost_r2w = ops.grounding_costs(S, caption_mask, region_mask, self.temperature)
         losses, other_info = {}, {}
-        if not self.return_dist and S.is_cuda and B <= ops.GROUNDING_CE_MAX_B and os.environ.get("LOCOV_FUSED_LOSSES", "1") != "0":
+        if S.is_cuda and B <= ops.GROUNDING_CE_MAX_B and os.environ.get("LOCOV_FUSED_LOSSES", "1") != "0":
             # :239-290, :357-377 in one launch (ops.grounding_ce = locov_grounding_ce_fwd / _bwd): the (max + 100) replacement, both
-            # log-softmaxes, the diagonal means and the batch accuracies of both alignments
-            vals = ops.grounding_ce(cost_w2r if self.align_words else None, cost_r2w if self.align_regions else None, caption_mask,
-                                    region_mask)
+            # log-softmaxes, the diagonal means and the batch accuracies of both alignments; with the distributions requested the
+            # same launch also writes the filled costs (ops.grounding_ce_dist = locov_grounding_ce_dist_fwd / _bwd)
+            c0, c1 = cost_w2r if self.align_words else None, cost_r2w if self.align_regions else None
+            if self.return_dist:
+                vals, pw0, pw1 = ops.grounding_ce_dist(c0, c1, caption_mask, region_mask)
+            else:
+                vals = ops.grounding_ce(c0, c1, caption_mask, region_mask)
             for k, (on, tag) in enumerate(((self.align_words, "Words"), (self.align_regions, "Regions"))):
                 if not on:
                     continue
@@ -97,6 +101,8 @@ class GroundingHead(nn.Module):
                 other_info[f"Batch Accuracy (Align {tag}, Choose Caption)"] = vals[4 * k + 2]
                 other_info[f"Batch Accuracy (Align {tag}, Choose Image)"] = vals[4 * k + 3]
             self.log_info = {**losses, **other_info}
+            if self.return_dist:
+                return other_info, losses, {"w2r": pw0, "r2w": pw1}
             return other_info, losses
         # :232-243 pairs with neither words nor regions get (max + 100)
         num_words, num_regions = caption_mask.sum(dim=1), region_mask.sum(dim=1)

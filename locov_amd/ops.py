@@ -14,6 +14,7 @@ import threading
 from typing import NamedTuple, Optional, Sequence, Tuple
 
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _lib
 from ._lib import BF16, F32, NORM_L2, NORM_NONE, NORM_STANDARDIZE, LocovError, check
@@ -1481,6 +1482,111 @@ def grounding_ce(cost_w2r: Optional[torch.Tensor], cost_r2w: Optional[torch.Tens
         raise ValueError(f"grounding_ce: costs must be [B, B] with B <= {GROUNDING_CE_MAX_B}")
     return _GroundingCEFn.apply(cost_w2r, cost_r2w, caption_mask.to(torch.float32), region_mask.to(torch.float32))
 
+
+
+class _GroundingCEDistFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, cost_w2r, cost_r2w, cmask, rmask):
+        ctx.set_materialize_grads(False)                  # unused outputs send NULL, not zero-filled upstream gradients
+        ref = cost_w2r if cost_w2r is not None else cost_r2w
+        c0 = _dev(cost_w2r, "cost_w2r") if cost_w2r is not None else None
+        c1 = _dev(cost_r2w, "cost_r2w") if cost_r2w is not None else None
+        cmask, rmask = _dev(cmask, "caption_mask"), _dev(rmask, "region_mask")
+        B, T, NR = ref.shape[0], cmask.shape[1], rmask.shape[1]
+        out = torch.empty(8, dtype=torch.float32, device=ref.device)          # (the kernel zeroes an absent alignment's four)
+        pw0 = torch.empty_like(c0) if c0 is not None else None
+        pw1 = torch.empty_like(c1) if c1 is not None else None
+        with torch.cuda.device(ref.device):
+            check(_lib.load().locov_grounding_ce_dist_fwd(_ptr(c0), _ptr(c1), _ptr(cmask), _ptr(rmask), B, T, NR, _ptr(out), _ptr(pw0),
+                                                          _ptr(pw1), _stream(ref)), "locov_grounding_ce_dist_fwd")
+        ctx.save_for_backward(*(t for t in (c0, c1) if t is not None), cmask, rmask)
+        ctx.have = (c0 is not None, c1 is not None)
+        vals = out.unbind(0)
+        ctx.mark_non_differentiable(vals[2], vals[3], vals[6], vals[7])
+        return vals + tuple(p for p in (pw0, pw1) if p is not None)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *g):
+        saved = list(ctx.saved_tensors)
+        c0 = saved.pop(0) if ctx.have[0] else None
+        c1 = saved.pop(0) if ctx.have[1] else None
+        cmask, rmask = saved
+        ref = c0 if c0 is not None else c1
+        B, T, NR = ref.shape[0], cmask.shape[1], rmask.shape[1]
+        ups = [(_dev(g[i].reshape(1), "grad") if g[i] is not None else None) for i in (0, 1, 4, 5)]
+        gpw = list(g[8:])
+        g0 = gpw.pop(0) if ctx.have[0] else None
+        g1 = gpw.pop(0) if ctx.have[1] else None
+        g0 = _dev(g0, "grad_pw_w2r") if g0 is not None else None
+        g1 = _dev(g1, "grad_pw_r2w") if g1 is not None else None
+        d0 = torch.empty_like(c0) if c0 is not None else None
+        d1 = torch.empty_like(c1) if c1 is not None else None
+        with torch.cuda.device(ref.device):
+            check(_lib.load().locov_grounding_ce_dist_bwd(_ptr(c0), _ptr(c1), _ptr(cmask), _ptr(rmask), B, T, NR, *(_ptr(u) for u in ups),
+                                                          _ptr(g0), _ptr(g1), _ptr(d0), _ptr(d1), _stream(ref)),
+                  "locov_grounding_ce_dist_bwd")
+        return d0, d1, None, None
+
+
+def grounding_ce_dist(cost_w2r: Optional[torch.Tensor], cost_r2w: Optional[torch.Tensor], caption_mask: torch.Tensor,
+                      region_mask: torch.Tensor) -> Tuple[Tuple[torch.Tensor, ...], Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """grounding_ce for a GroundingHead that also returns its distributions (MMSS_HEAD.DISTILLATION_LOSS): one launch each way
+    (locov_grounding_ce_dist_fwd / _bwd).  Returns (the 8 scalars of grounding_ce, pw_w2r, pw_r2w): the filled [B, B] costs
+    (grounding_head.py:239-251, None for an absent alignment), differentiable in the costs on the pairs that are not filled."""
+    ref = cost_w2r if cost_w2r is not None else cost_r2w
+    if ref is None or ref.dim() != 2 or ref.shape[0] != ref.shape[1] or ref.shape[0] > GROUNDING_CE_MAX_B:
+        raise ValueError(f"grounding_ce_dist: costs must be [B, B] with B <= {GROUNDING_CE_MAX_B}")
+    res = _GroundingCEDistFn.apply(cost_w2r, cost_r2w, caption_mask.to(torch.float32), region_mask.to(torch.float32))
+    pw = list(res[8:])
+    pw0 = pw.pop(0) if cost_w2r is not None else None
+    pw1 = pw.pop(0) if cost_r2w is not None else None
+    return tuple(res[:8]), pw0, pw1
+
+
+DISTILL_MAX_B = _lib.DISTILL_MAX_B   # LOCOV_DISTILL_MAX_B
+DISTILL_KINDS = {"kd": _lib.DISTILL_KD, "js": _lib.DISTILL_JS, "mse": _lib.DISTILL_MSE}
+
+
+class _DistillLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, trans, w2r, r2w, kind, transformer_teacher, temperature, loss_weight):
+        trans, w2r, r2w = _dev(trans, "trans_pw_cost"), _dev(w2r, "pw_cost_w2r"), _dev(r2w, "pw_cost_r2w")
+        loss = torch.empty((), dtype=torch.float32, device=trans.device)
+        with torch.cuda.device(trans.device):
+            check(_lib.load().locov_distill_loss_fwd(_ptr(trans), _ptr(w2r), _ptr(r2w), trans.shape[0], kind, int(transformer_teacher),
+                                                     temperature, loss_weight, _ptr(loss), _stream(trans)), "locov_distill_loss_fwd")
+        ctx.save_for_backward(trans, w2r, r2w)
+        ctx.args = (kind, int(transformer_teacher), temperature, loss_weight)
+        return loss
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_loss):
+        trans, w2r, r2w = ctx.saved_tensors
+        d = [torch.empty_like(x) if ctx.needs_input_grad[i] else None for i, x in enumerate((trans, w2r, r2w))]
+        if any(x is not None for x in d):
+            gl = _dev(grad_loss.reshape(1), "grad_loss")
+            with torch.cuda.device(trans.device):
+                check(_lib.load().locov_distill_loss_bwd(_ptr(trans), _ptr(w2r), _ptr(r2w), trans.shape[0], *ctx.args, _ptr(gl),
+                                                         *(_ptr(x) for x in d), _stream(trans)), "locov_distill_loss_bwd")
+        return d[0], d[1], d[2], None, None, None, None
+
+
+def distill_loss(kind: str, trans_pw_cost: torch.Tensor, pw_cost_w2r: torch.Tensor, pw_cost_r2w: torch.Tensor, temperature: float,
+                 loss_weight: float = 1.0, transformer_teacher: bool = True) -> torch.Tensor:
+    """MultiDistillLoss ("kd") / MultiDistillLossJS ("js") / MultiDistillLossL2 ("mse") of distill_mmss_gcnn.py:211-433 on three
+    [B, B] fp32 device cost matrices (B <= DISTILL_MAX_B): one launch forward (locov_distill_loss_fwd) and one backward
+    (locov_distill_loss_bwd).  A detached input -- the caller's DETACH_TEACHER -- gets no gradient.  Returns the 0-dim loss."""
+    if kind not in DISTILL_KINDS:
+        raise ValueError(f"distill_loss: unknown kind {kind!r} (one of {sorted(DISTILL_KINDS)})")
+    B = trans_pw_cost.shape[0] if trans_pw_cost.dim() == 2 else -1
+    if not 1 <= B <= DISTILL_MAX_B or any(tuple(x.shape) != (B, B) for x in (trans_pw_cost, pw_cost_w2r, pw_cost_r2w)):
+        raise ValueError(f"distill_loss: the three costs must be [B, B] with 1 <= B <= {DISTILL_MAX_B}")
+    if not temperature > 0:
+        raise ValueError("distill_loss: temperature must be > 0")
+    return _DistillLossFn.apply(trans_pw_cost, pw_cost_w2r, pw_cost_r2w, DISTILL_KINDS[kind], bool(transformer_teacher),
+                                float(temperature), float(loss_weight))
 
 class _BoxRegLossFn(torch.autograd.Function):
     @staticmethod
