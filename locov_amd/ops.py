@@ -1744,7 +1744,11 @@ def sim_gemm_autograd(emb: torch.Tensor, bank: torch.Tensor, bias: Optional[torc
 
 
 def to_bf16(x: torch.Tensor) -> torch.Tensor:
+    """fp32 -> bf16, round to nearest even (torch's conversion).  The kernel reads 16 bytes per lane: a contiguous view
+    that does not start on a 16-byte boundary (x[1:]) is converted from an aligned copy."""
     x = _dev(x, "x")
+    if x.data_ptr() % 16:
+        x = x.clone()
     y = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device)
     with torch.cuda.device(x.device):
         check(_lib.load().locov_f32_to_bf16(_ptr(x), x.numel(), _ptr(y), _stream(x)), "locov_f32_to_bf16")
