@@ -1122,6 +1122,18 @@ def winograd_conv3x3_split_ex(x: torch.Tensor, U: SplitWeight, *, scale=None, sh
     return y
 
 
+def winograd_scale_slot(x: torch.Tensor, R: int, Cin: int, N: int, wgrad: bool = False) -> torch.Tensor:
+    """The 16-byte operand-scale slot {s, 1/s, bits of max |.|, -} that the last winograd_conv3x3_split_ex(v_scale=None) (V's scale) or,
+    with wgrad, winograd_wgrad(split=True) (dM's scale) on x's device and current stream filled: winograd.hip keeps it in the last 16
+    bytes of the workspace it is given, here the cached one of that call.  Test / debug aid (a view, valid until the next such call)."""
+    lib = _lib.load()
+    if wgrad:
+        ws = _workspace("wino_wgrad", x, int(lib.locov_winograd_wgrad_workspace_bytes(R, Cin, N)))
+    else:
+        ws = _workspace("wino", x, int(lib.locov_winograd_workspace_bytes(R, Cin, N)))
+    return ws[ws.numel() - 16:].view(torch.float32)
+
+
 PREP_KINDS = {"plain": _lib.PREP_PLAIN, "t": _lib.PREP_TRANSPOSE, "col": _lib.PREP_IM2COL, "flip9": _lib.PREP_IM2COL_FLIP,
               "wino": _lib.PREP_WINO, "uflip": _lib.PREP_WINO_FLIP}
 
