@@ -32,7 +32,8 @@
 extern "C" {
 #endif
 
-/* 8: locov_detect_postprocess; later, additively: locov_grounding_ce_dist_fwd / _bwd, locov_distill_loss_fwd / _bwd */
+/* 8: locov_detect_postprocess; later, additively: locov_grounding_ce_dist_fwd / _bwd, locov_distill_loss_fwd / _bwd,
+ *    locov_detect_postprocess_wide (+ _workspace_bytes) */
 #define LOCOV_ABI_VERSION 8
 
 #define LOCOV_OK 0
@@ -500,6 +501,29 @@ int locov_detect_postprocess(const float *probs, int64_t ld_probs, int num_class
                              float scale_clamp, float score_thresh, float nms_thresh, int topk, void *workspace, int64_t workspace_bytes,
                              float *out_boxes, float *out_scores, int64_t *out_classes, int64_t *out_rows, int *counts_and_flags,
                              locov_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
+ * a-10b the same post-processing for any candidate count (LVIS-style thresholds: SCORE_THRESH_TEST 1e-4, 1 203 classes -> up to
+ * 1.2e6 candidates per image), bit-identical to the torch chain for every count.  Arguments as locov_detect_postprocess, plus
+ * per_class_above: an image with n >= per_class_above candidates runs one NMS per class on the unshifted boxes, one below it
+ * a single NMS on the class-shifted boxes (batched_nms's two branches; the decision is per image, on the device).
+ *   counts_and_flags: as locov_detect_postprocess; only LOCOV_DETECT_FLAG_NONFINITE is ever set (the caller then runs the chain).
+ *   Limits: at most LOCOV_LABEL_MAX_IMAGES images, 16 383 proposals per image, 32 767 classes, 1 <= topk <= 8 192, and
+ *   R x K < 2^31 (R = all rows of the call, K = num_classes).
+ *   workspace: locov_detect_postprocess_wide_workspace_bytes(row_offsets, n_images, num_classes, per_class_above) bytes, from host
+ *   data only.  With R_i the rows of image i, W_i = ceil(R_i / 64), cap_i = clamp(per_class_above - 1, 0, R_i x K), n = n_images:
+ *       16 R + 16 n K + 180 352 n + 8 (sum_i R_i W_i + sum_i cap_i W_i + R K)
+ *   (decoded boxes; per (image, class) counts, survivors, offsets, cursors; per image 128 B of state, 6 x 2 048 histogram bins
+ *   and 16 384 select slots; the row overlap matrices; the shifted branch's overlap words; the candidate keys).  0 for empty
+ *   input (n_images == 0 or R == 0); < 0 on an argument error.
+ * ------------------------------------------------------------------------------------- */
+int64_t locov_detect_postprocess_wide_workspace_bytes(const int *row_offsets, int n_images, int num_classes, int per_class_above);
+
+int locov_detect_postprocess_wide(const float *probs, int64_t ld_probs, int num_classes, const float *deltas, const float *proposal_boxes,
+                                  const int *row_offsets, const float *image_hw, int n_images, float wx, float wy, float ww, float wh,
+                                  float scale_clamp, float score_thresh, float nms_thresh, int topk, int per_class_above, void *workspace,
+                                  int64_t workspace_bytes, float *out_boxes, float *out_scores, int64_t *out_classes, int64_t *out_rows,
+                                  int *counts_and_flags, locov_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * a-12  LSM grounding: word<->region alignment -> [caption, image] cost matrices.

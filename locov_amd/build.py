@@ -33,6 +33,7 @@ FILE_FLAGS = {
     "label.hip": ["-ffp-contract=off"],          # (IoU values must be the torch ops', rounded step by step)
     "losses.hip": ["-ffp-contract=off"],         # (box deltas / log-softmax pieces as the torch ops form them)
     "detect.hip": ["-ffp-contract=off"],         # (box decoding / shifted IoU as the torch ops round them)
+    "detect_wide.hip": ["-ffp-contract=off"],    # (the same, at any candidate count)
 }
 
 

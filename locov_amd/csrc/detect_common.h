@@ -1,0 +1,89 @@
+// Device pieces shared by the two detection post-processing pipelines: detect.hip (candidates sorted in LDS, COCO-style
+// thresholds) and detect_wide.hip (any candidate count, LVIS-style thresholds).  Both files are compiled with -ffp-contract=off:
+// the box decoding and the IoU must round as the torch ops do.
+#pragma once
+#include "common.h"
+
+namespace locov {
+namespace {     // (each pipeline's translation unit keeps its own copy of the kernel)
+
+struct DetGeom {
+    int n_img;
+    int roff[LOCOV_LABEL_MAX_IMAGES + 1];                       // proposals of image i: rows [roff[i], roff[i + 1])
+    float h[LOCOV_LABEL_MAX_IMAGES], w[LOCOV_LABEL_MAX_IMAGES];
+};
+
+__device__ __forceinline__ int det_image_of(const DetGeom &g, int r)
+{
+    int lo = 0, hi = g.n_img - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (g.roff[mid] <= r) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+__device__ __forceinline__ bool det_finite(float v) { return fabsf(v) <= 3.402823466e38f; }        // false for NaN / inf
+
+// Box2BoxTransform.apply_deltas (class-agnostic: one box per proposal) + Boxes.clip, rounded as the torch ops round
+__global__ __launch_bounds__(256) void det_decode_clip_kernel(const float4 *__restrict__ deltas, const float4 *__restrict__ props, int R,
+                                                              DetGeom g, float inv_wx, float inv_wy, float inv_ww, float inv_wh,
+                                                              float scale_clamp, float4 *__restrict__ boxes, int *__restrict__ flags)
+{
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= R) return;
+    const float4 d = deltas[r], b = props[r];
+    const float widths = __fsub_rn(b.z, b.x), heights = __fsub_rn(b.w, b.y);
+    const float ctr_x = __fadd_rn(b.x, __fmul_rn(0.5f, widths)), ctr_y = __fadd_rn(b.y, __fmul_rn(0.5f, heights));
+    const float dx = __fmul_rn(d.x, inv_wx), dy = __fmul_rn(d.y, inv_wy);
+    float dw = __fmul_rn(d.z, inv_ww), dh = __fmul_rn(d.w, inv_wh);
+    dw = dw > scale_clamp ? scale_clamp : dw;                     // torch.clamp(max=): NaN stays NaN
+    dh = dh > scale_clamp ? scale_clamp : dh;
+    const float pcx = __fadd_rn(__fmul_rn(dx, widths), ctr_x), pcy = __fadd_rn(__fmul_rn(dy, heights), ctr_y);
+    const float pw = __fmul_rn(expf(dw), widths), ph = __fmul_rn(expf(dh), heights);
+    float4 o;
+    o.x = __fsub_rn(pcx, __fmul_rn(0.5f, pw));
+    o.y = __fsub_rn(pcy, __fmul_rn(0.5f, ph));
+    o.z = __fadd_rn(pcx, __fmul_rn(0.5f, pw));
+    o.w = __fadd_rn(pcy, __fmul_rn(0.5f, ph));
+    if (!(det_finite(o.x) && det_finite(o.y) && det_finite(o.z) && det_finite(o.w))) atomicOr(flags, LOCOV_DETECT_FLAG_NONFINITE);
+    const int img = det_image_of(g, r);
+    const float W = g.w[img], H = g.h[img];
+    o.x = fminf(fmaxf(o.x, 0.f), W);
+    o.y = fminf(fmaxf(o.y, 0.f), H);
+    o.z = fminf(fmaxf(o.z, 0.f), W);
+    o.w = fminf(fmaxf(o.w, 0.f), H);
+    boxes[r] = o;
+}
+
+__device__ __forceinline__ bool det_iou_gt(const float4 a, const float4 b, float thr)        // (= nms.hip's iou_gt)
+{
+    const float left = fmaxf(a.x, b.x), right = fminf(a.z, b.z);
+    const float top = fmaxf(a.y, b.y), bottom = fminf(a.w, b.w);
+    const float w = fmaxf(right - left, 0.f), h = fmaxf(bottom - top, 0.f);
+    const float inter = w * h;
+    const float sa = (a.z - a.x) * (a.w - a.y), sb = (b.z - b.x) * (b.w - b.y);
+    return inter / (sa + sb - inter) > thr;
+}
+
+template <int kThreads>
+__device__ __forceinline__ void det_bitonic_sort(unsigned long long *key, int P, int tid)
+{
+    for (int size = 2; size <= P; size <<= 1)
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            for (int t = tid; t < (P >> 1); t += kThreads) {
+                const int lo = 2 * t - (t & (stride - 1)), hi = lo + stride;
+                const bool ascending = (lo & size) == 0;
+                const unsigned long long a = key[lo], b = key[hi];
+                if ((a > b) == ascending) {
+                    key[lo] = b;
+                    key[hi] = a;
+                }
+            }
+            __syncthreads();
+        }
+}
+
+}  // namespace
+}  // namespace locov

@@ -1,0 +1,604 @@
+// Detection post-processing of the evaluation call for any candidate count (LVIS-style thresholds), on the device, ONE host read.
+//
+// detect.hip sorts an image's candidates in LDS and so takes at most LOCOV_DETECT_MAX_CANDIDATES of them: enough at COCO's
+// SCORE_THRESH_TEST 0.05, far too few at Detectron2's LVIS setting (SCORE_THRESH_TEST 1e-4, DETECTIONS_PER_IMAGE 300), where one
+// image of 1 000 proposals x 1 203 classes has 2e5..1.2e6 candidates.  The torch chain then takes batched_nms's per-class Python loop
+// (thousands of launches, host waits per class).  This file computes the same detections, bit for bit, with the structure that
+// class-agnostic box regression gives: every class's candidate of proposal j has the SAME box, proposal j's.
+//
+// What the chain does per image (roi_heads/box_emb_head.py: fast_rcnn_inference -> batched_nms), which is what this file reproduces:
+//   n < per_class_above candidates: ONE NMS over boxes shifted by class * (max coordinate over the image's candidates + 1); the IoU
+//       is taken on the shifted fp32 coordinates (classes never suppress each other, so the greedy sweep runs per class segment);
+//   n >= per_class_above: a separate NMS per class on the unshifted boxes -- the IoU of two candidates is then the IoU of their two
+//       proposals, one R x R bit matrix per image serves every class;
+//   inside a class: descending score, ties by row; survivors merged by (descending score, row, class), the first `topk` kept.
+//
+//   det_decode_clip_kernel   (detect_common.h) apply_deltas + clip, one thread per proposal
+//   dw_count_kernel          a workgroup per (64 rows of an image, 256 columns): candidates per (image, class); non-finite
+//                            probabilities; the max coordinate over the image's candidate boxes (batched_nms's shift unit)
+//   dw_scan_kernel           one workgroup: segment offsets per (image, class), candidates per image, the branch of each image
+//   dw_emit_kernel           same tiling as the count: keys  ~score << 14 | row  into the (image, class) segments
+//   dw_segsort_kernel        a workgroup per segment: bitonic sort in LDS (descending score, ties by row)
+//   dw_overlap_kernel        per-class images: the row x row IoU bit matrix; shifted images: per candidate, which earlier candidates
+//                            of its class overlap it (IoU on the SHIFTED boxes)
+//   dw_sweep_kernel          a wave per segment: the greedy sweep over the segment with the kept set in registers; survivors are
+//                            compacted to the segment's front as  ~score << 29 | row << 15 | class  (the merge order)
+//   dw_select_kernel x 6     radix select, 11 bits a pass, chip-wide histograms; the last workgroup of an image picks the digit:
+//                            ends as soon as the keys below a threshold number at least top-k and at most kDwCap
+//   dw_gather_kernel         those keys into one buffer per image
+//   dw_topk_kernel           a workgroup per image: bitonic sort of the <= kDwCap winners in LDS, the first top-k out.
+#include "detect_common.h"
+
+namespace locov {
+
+constexpr int kDwRowBits = 14, kDwClsBits = 15;
+constexpr unsigned long long kDwRowMask = (1ull << kDwRowBits) - 1ull;
+constexpr int kDwChunkRows = 64;                // rows per count / emit workgroup
+constexpr int kDwCap = 16384;                   // winners the last launch sorts in LDS (128 KB)
+constexpr int kDwDigit = 11, kDwBins = 1 << kDwDigit, kDwPasses = 6;     // 61-bit merge keys: 5 x 11 + 6 bits
+constexpr int kDwClassChunk = 32;               // classes per select / gather workgroup
+constexpr int kDwMaxImages = LOCOV_LABEL_MAX_IMAGES;
+
+struct DwPlan {
+    int n_img, K, pca;
+    int cbase[kDwMaxImages + 1];                // row chunks of image i: [cbase[i], cbase[i + 1])
+    int W[kDwMaxImages];                        // 64-bit words of a row / candidate overlap set of image i: ceil(rows / 64)
+    int64_t mbase[kDwMaxImages];                // word offset of image i's row x row matrix (rows * W words)
+    int64_t ovbase[kDwMaxImages];               // word offset of image i's candidate overlap words (cap * W words)
+};
+
+struct DwImage {                                // per image, zeroed at the start of a call
+    int n;                                      // candidates
+    int base;                                   // first candidate slot of the image
+    int per_class;                              // n >= per_class_above
+    unsigned umax;                              // bits of the max coordinate over the candidate boxes (+0.0 start)
+    int surv;                                   // survivors of the NMS
+    int done;                                   // the select has found its threshold
+    int below;                                  // keys below the current prefix (all winners)
+    int gcount;                                 // keys gathered
+    unsigned long long pre, thresh;             // radix prefix; winners are the keys < thresh
+    int arrive[kDwPasses];                      // select workgroups finished, per pass
+    int pad[14];
+};
+static_assert(sizeof(DwImage) == 128, "DwImage: 128 bytes per image (the documented workspace formula)");
+
+struct DwWork {
+    float4 *boxes;                              // [R] decoded, clipped
+    DwImage *info;                              // [n_img]
+    int *hist;                                  // [kDwPasses][n_img][kDwBins]
+    int *cnt, *kept, *seg_off, *cursor;         // [n_img * K] candidates / survivors / first slot / emit cursor per segment
+    unsigned long long *gbuf;                   // [n_img][kDwCap]
+    unsigned long long *M, *ov, *keys;
+    int *flags;
+};
+
+__device__ __forceinline__ int dw_chunk_image(const DwPlan &p, int chunk)
+{
+    int lo = 0, hi = p.n_img - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (p.cbase[mid] <= chunk) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+// a workgroup per (64 rows, 256 columns); every one of the K + 1 columns must be finite
+__global__ __launch_bounds__(256) void dw_count_kernel(const float *__restrict__ probs, int64_t ld, float thr, DetGeom g, DwPlan p, DwWork w)
+{
+    __shared__ unsigned long long rows_hit;
+    const int tid = threadIdx.x, lane = tid & 63, chunk = blockIdx.x, c = blockIdx.y * 256 + tid, K = p.K;
+    const int img = dw_chunk_image(p, chunk);
+    const int r0 = g.roff[img] + (chunk - p.cbase[img]) * kDwChunkRows, r1 = min(r0 + kDwChunkRows, g.roff[img + 1]);
+    if (tid == 0) rows_hit = 0;
+    __syncthreads();
+    int n = 0;
+    unsigned long long mask = 0;
+    bool bad = false;
+    if (c <= K)
+        for (int r = r0; r < r1; r++) {
+            const float v = probs[(int64_t)r * ld + c];
+            bad |= !det_finite(v);
+            if (c < K && v > thr) {
+                n++;
+                mask |= 1ull << (r - r0);
+            }
+        }
+    if (__ballot(bad) != 0ull && lane == 0) atomicOr(w.flags, LOCOV_DETECT_FLAG_NONFINITE);
+    if (n) atomicAdd(&w.cnt[img * K + c], n);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mask |= __shfl_xor(mask, o);
+    if (lane == 0 && mask) atomicOr(&rows_hit, mask);
+    __syncthreads();
+    if (tid < 64) {                             // batched_nms's max coordinate: over the boxes of rows with a candidate
+        float mx = -__builtin_inff();
+        if (tid < r1 - r0 && ((rows_hit >> tid) & 1ull)) {
+            const float4 b = w.boxes[r0 + tid];
+            mx = fmaxf(fmaxf(b.x, b.y), fmaxf(b.z, b.w)) + 0.f;       // (+ 0: a -0 max becomes +0; max + 1 is the same)
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+        if (tid == 0 && mx >= 0.f) atomicMax(&w.info[img].umax, __float_as_uint(mx));
+    }
+}
+
+// one workgroup: per image, the exclusive scan of its class counts (segments in (image, class) order), its candidates and branch
+__global__ __launch_bounds__(1024) void dw_scan_kernel(DwPlan p, DwWork w)
+{
+    __shared__ int wave_sum[16];
+    __shared__ int carry;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, K = p.K;
+    if (tid == 0) carry = 0;
+    __syncthreads();
+    for (int img = 0; img < p.n_img; img++) {
+        const int base = carry;
+        for (int c0 = 0; c0 < K; c0 += 1024) {
+            const int c = c0 + tid;
+            const int v = c < K ? w.cnt[img * K + c] : 0;
+            int incl = v;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const int t = __shfl_up(incl, o);
+                if (lane >= o) incl += t;
+            }
+            if (lane == 63) wave_sum[wave] = incl;
+            __syncthreads();
+            int before = carry;
+            for (int q = 0; q < wave; q++) before += wave_sum[q];
+            if (c < K) w.seg_off[img * K + c] = w.cursor[img * K + c] = before + incl - v;
+            __syncthreads();
+            if (tid == 1023) carry = before + incl;
+            __syncthreads();
+        }
+        if (tid == 0) {
+            const int n = carry - base;
+            w.info[img].n = n;
+            w.info[img].base = base;
+            w.info[img].per_class = n >= p.pca ? 1 : 0;
+        }
+    }
+}
+
+// same tiling as dw_count_kernel: a thread's candidates of its column (class) in the 64 rows, behind a per-class cursor
+__global__ __launch_bounds__(256) void dw_emit_kernel(const float *__restrict__ probs, int64_t ld, float thr, DetGeom g, DwPlan p, DwWork w)
+{
+    const int tid = threadIdx.x, chunk = blockIdx.x, c = blockIdx.y * 256 + tid, K = p.K;
+    if (c >= K) return;
+    const int img = dw_chunk_image(p, chunk);
+    const int r0 = g.roff[img] + (chunk - p.cbase[img]) * kDwChunkRows, r1 = min(r0 + kDwChunkRows, g.roff[img + 1]);
+    unsigned long long mask = 0;
+    for (int r = r0; r < r1; r++)
+        if (probs[(int64_t)r * ld + c] > thr) mask |= 1ull << (r - r0);
+    if (!mask) return;
+    int at = atomicAdd(&w.cursor[img * K + c], __popcll(mask));
+    while (mask) {
+        const int j = __ffsll((long long)mask) - 1;
+        mask &= mask - 1ull;
+        const float v = probs[(int64_t)(r0 + j) * ld + c];
+        w.keys[at++] = ((unsigned long long)(~__float_as_uint(v)) << kDwRowBits) | (unsigned long long)(r0 + j - g.roff[img]);
+    }
+}
+
+// a workgroup per (image, class) segment; the LDS holds the next power of two above the largest image's rows
+__global__ __launch_bounds__(256) void dw_segsort_kernel(DwWork w)
+{
+    extern __shared__ unsigned long long skey[];
+    const int seg = blockIdx.x, tid = threadIdx.x;
+    const int m = w.cnt[seg];
+    if (m <= 1) return;
+    int P = 2;
+    while (P < m) P <<= 1;
+    unsigned long long *keys = w.keys + w.seg_off[seg];
+    for (int i = tid; i < P; i += 256) skey[i] = i < m ? keys[i] : ~0ull;
+    __syncthreads();
+    det_bitonic_sort<256>(skey, P, tid);
+    for (int i = tid; i < m; i += 256) keys[i] = skey[i];
+}
+
+// per-class images: bit k of word wd of row j = IoU(box j, box 64 wd + k) > thr (the unshifted boxes; IoU is symmetric bit for bit).
+// shifted images: a thread per candidate: bit j of its word wd = its class's candidate 64 wd + j (an earlier one) overlaps it on
+// the shifted boxes.
+__global__ __launch_bounds__(256) void dw_overlap_kernel(DetGeom g, DwPlan p, DwWork w, float nms_thr)
+{
+    const int img = blockIdx.y, t = blockIdx.x * 256 + threadIdx.x, W = p.W[img], K = p.K;
+    const int rows = g.roff[img + 1] - g.roff[img];
+    const float4 *gb = w.boxes + g.roff[img];
+    const DwImage &inf = w.info[img];
+    if (inf.per_class) {
+        if (t >= rows * W) return;
+        const int j = t / W, wd = t - j * W;
+        const float4 a = gb[j];
+        const int lim = min(64, rows - 64 * wd);
+        unsigned long long bits = 0;
+        for (int k = 0; k < lim; k++) bits |= (unsigned long long)det_iou_gt(a, gb[64 * wd + k], nms_thr) << k;
+        w.M[p.mbase[img] + (int64_t)j * W + wd] = bits;
+        return;
+    }
+    if (t >= inf.n) return;
+    const int idx = inf.base + t;
+    const int *so = w.seg_off + img * K;
+    int lo = 0, hi = K - 1;                     // the segment of candidate idx: the last class starting at or before it
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (so[mid] <= idx) lo = mid;
+        else hi = mid - 1;
+    }
+    const int s = so[lo], pos = idx - s;
+    const float off = (float)lo * (__uint_as_float(inf.umax) + 1.f);
+    float4 b = gb[(int)(w.keys[idx] & kDwRowMask)];
+    b.x += off;
+    b.y += off;
+    b.z += off;
+    b.w += off;
+    unsigned long long *out = w.ov + p.ovbase[img] + (int64_t)t * W;
+    for (int wd = 0; 64 * wd < pos; wd++) {
+        const int lim = min(64, pos - 64 * wd);
+        unsigned long long bits = 0;
+        for (int j = 0; j < lim; j++) {
+            float4 e = gb[(int)(w.keys[s + 64 * wd + j] & kDwRowMask)];
+            e.x += off;
+            e.y += off;
+            e.z += off;
+            e.w += off;
+            bits |= (unsigned long long)det_iou_gt(e, b, nms_thr) << j;
+        }
+        out[wd] = bits;
+    }
+}
+
+// a wave per segment: the greedy sweep in the segment's order.  Candidate a is kept iff none of the KEPT candidates overlaps it:
+// the kept set lives in registers (lane l holds words l, l + 64, ...: bits by row for per-class images, by segment position for
+// shifted ones), a candidate's overlap words are loaded 8 candidates ahead.  Survivors go to the segment's front in merge-key form.
+template <int NQ>
+__global__ __launch_bounds__(256) void dw_sweep_kernel(DwPlan p, DwWork w)
+{
+    const int lane = threadIdx.x & 63;
+    const int seg = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (seg >= p.n_img * p.K) return;
+    const int m = w.cnt[seg];
+    if (m == 0) return;                         // (kept[] starts at zero)
+    const int img = seg / p.K, cls = seg - img * p.K, s = w.seg_off[seg], W = p.W[img];
+    const bool per_class = w.info[img].per_class != 0;
+    const unsigned long long *Mi = w.M + p.mbase[img];
+    const unsigned long long *ovs = w.ov + p.ovbase[img] + (int64_t)(s - w.info[img].base) * W;
+    unsigned long long *keys = w.keys + s;
+    unsigned long long kept[NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; q++) kept[q] = 0;
+    int nk = 0;
+    for (int a0 = 0; a0 < m; a0 += 64) {
+        const int nb = min(64, m - a0);
+        const unsigned long long mykey = lane < nb ? keys[a0 + lane] : 0ull;
+        for (int b0 = 0; b0 < nb; b0 += 8) {
+            unsigned long long v[8][NQ];
+#pragma unroll
+            for (int i = 0; i < 8; i++) {
+                const int a = a0 + b0 + i;
+                const unsigned long long ka = __shfl(mykey, (b0 + i) & 63);
+                const int row = (int)(ka & kDwRowMask);
+#pragma unroll
+                for (int q = 0; q < NQ; q++) {
+                    const int wd = lane + 64 * q;
+                    v[i][q] = 0;
+                    if (b0 + i < nb) {
+                        if (per_class) {
+                            if (wd < W) v[i][q] = Mi[(int64_t)row * W + wd];
+                        } else if (64 * wd < a) {
+                            v[i][q] = ovs[(int64_t)a * W + wd];
+                        }
+                    }
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < 8; i++) {
+                if (b0 + i >= nb) break;
+                bool hit = false;
+#pragma unroll
+                for (int q = 0; q < NQ; q++) hit |= (v[i][q] & kept[q]) != 0ull;
+                if (__ballot(hit) == 0ull) {
+                    const unsigned long long ka = __shfl(mykey, b0 + i);
+                    const int idx = per_class ? (int)(ka & kDwRowMask) : a0 + b0 + i;
+#pragma unroll
+                    for (int q = 0; q < NQ; q++)
+                        if ((idx >> 6) == lane + 64 * q) kept[q] |= 1ull << (idx & 63);
+                    if (lane == 0)
+                        keys[nk] = ((ka >> kDwRowBits) << (kDwRowBits + kDwClsBits)) | ((ka & kDwRowMask) << kDwClsBits) | (unsigned long long)cls;
+                    nk++;
+                }
+            }
+        }
+    }
+    if (lane == 0) {
+        w.kept[seg] = nk;
+        atomicAdd(&w.info[img].surv, nk);
+    }
+}
+
+__device__ __forceinline__ int dw_lo_bit(int pass) { return pass < kDwPasses - 1 ? 61 - kDwDigit * (pass + 1) : 0; }
+__device__ __forceinline__ int dw_digits(int pass) { return pass < kDwPasses - 1 ? kDwDigit : 61 - kDwDigit * (kDwPasses - 1); }
+
+// pass `pass` of the radix select of an image's top-k (only images with more than kDwCap survivors): a histogram of the next digit
+// of the keys under the current prefix, chip-wide; the last workgroup of the image to finish reads it and picks the digit
+__global__ __launch_bounds__(256) void dw_select_kernel(DwPlan p, DwWork w, int topk, int pass)
+{
+    __shared__ int h[kDwBins];
+    __shared__ int wave_sum[4];
+    __shared__ int last, pick_bin, pick_cum, pick_n;
+    const int img = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, K = p.K;
+    DwImage &inf = w.info[img];
+    if (inf.surv <= kDwCap || inf.done) return;           // (uniform over the image's workgroups)
+    const int lo = dw_lo_bit(pass), nd = dw_digits(pass);
+    const unsigned long long pre = inf.pre;
+    for (int b = tid; b < kDwBins; b += 256) h[b] = 0;
+    __syncthreads();
+    const int c1 = min(K, (int)(blockIdx.x + 1) * kDwClassChunk);
+    for (int c = blockIdx.x * kDwClassChunk; c < c1; c++) {
+        const int n = w.kept[img * K + c];
+        const unsigned long long *keys = w.keys + w.seg_off[img * K + c];
+        for (int j = tid; j < n; j += 256) {
+            const unsigned long long k = keys[j];
+            if ((k >> (lo + nd)) == pre) atomicAdd(&h[(int)(k >> lo) & ((1 << nd) - 1)], 1);
+        }
+    }
+    __syncthreads();
+    int *gh = w.hist + ((int64_t)pass * p.n_img + img) * kDwBins;
+    for (int b = tid; b < kDwBins; b += 256)
+        if (h[b]) atomicAdd(&gh[b], h[b]);
+    __threadfence();
+    __syncthreads();
+    if (tid == 0) last = atomicAdd(&inf.arrive[pass], 1) == (int)gridDim.x - 1;
+    __syncthreads();
+    if (!last) return;
+    __threadfence();
+    // the last workgroup: find the bin of the need-th key under the prefix
+    constexpr int kPer = kDwBins / 256;
+    int v[kPer], sum = 0;
+#pragma unroll
+    for (int q = 0; q < kPer; q++) {
+        v[q] = __hip_atomic_load(&gh[tid * kPer + q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        sum += v[q];
+    }
+    int incl = sum;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int t = __shfl_up(incl, o);
+        if (lane >= o) incl += t;
+    }
+    if (lane == 63) wave_sum[wave] = incl;
+    __syncthreads();
+    int cum = incl - sum;
+    for (int q = 0; q < wave; q++) cum += wave_sum[q];
+    const int k = min(topk, inf.surv), need = k - inf.below;
+#pragma unroll
+    for (int q = 0; q < kPer; q++) {
+        if (cum < need && need <= cum + v[q]) {
+            pick_bin = tid * kPer + q;
+            pick_cum = cum;
+            pick_n = v[q];
+        }
+        cum += v[q];
+    }
+    __syncthreads();
+    if (tid == 0) {
+        const int b = pick_bin, below = inf.below + pick_cum;
+        const unsigned long long np = (pre << nd) | (unsigned long long)b;
+        if (below + pick_n <= kDwCap) {
+            inf.thresh = (np + 1ull) << lo;
+            inf.done = 1;
+        } else {
+            inf.pre = np;
+            inf.below = below;
+        }
+    }
+}
+
+// the winners' candidates: every survivor (at most kDwCap of them) or the survivors below the select's threshold
+__global__ __launch_bounds__(256) void dw_gather_kernel(DwPlan p, DwWork w)
+{
+    const int img = blockIdx.y, tid = threadIdx.x, lane = tid & 63, K = p.K;
+    DwImage &inf = w.info[img];
+    const unsigned long long T = inf.surv <= kDwCap ? ~0ull : inf.thresh;
+    unsigned long long *out = w.gbuf + (int64_t)img * kDwCap;
+    const int c1 = min(K, (int)(blockIdx.x + 1) * kDwClassChunk);
+    for (int c = blockIdx.x * kDwClassChunk; c < c1; c++) {
+        const int n = w.kept[img * K + c];
+        const unsigned long long *keys = w.keys + w.seg_off[img * K + c];
+        for (int j0 = 0; j0 < n; j0 += 256) {
+            const int j = j0 + tid;
+            const unsigned long long k = j < n ? keys[j] : ~0ull;
+            const bool take = j < n && k < T;
+            const unsigned long long b = __ballot(take);
+            if (!b) continue;
+            int at = 0;
+            if (lane == 0) at = atomicAdd(&inf.gcount, __popcll(b));
+            at = __shfl(at, 0);
+            if (take) out[at + __popcll(b & ((1ull << lane) - 1ull))] = k;
+        }
+    }
+}
+
+__global__ __launch_bounds__(1024) void dw_topk_kernel(DetGeom g, DwWork w, int topk, float4 *__restrict__ out_boxes, float *__restrict__ out_scores,
+                                                       int64_t *__restrict__ out_classes, int64_t *__restrict__ out_rows, int *__restrict__ counts)
+{
+    extern __shared__ unsigned long long tkey[];
+    const int img = blockIdx.x, tid = threadIdx.x;
+    const int n = w.info[img].gcount, k = min(topk, w.info[img].surv);
+    if (n == 0) {
+        if (tid == 0) counts[img] = 0;
+        return;
+    }
+    int P = 2;
+    while (P < n) P <<= 1;
+    const unsigned long long *in = w.gbuf + (int64_t)img * kDwCap;
+    for (int i = tid; i < P; i += 1024) tkey[i] = i < n ? in[i] : ~0ull;
+    __syncthreads();
+    det_bitonic_sort<1024>(tkey, P, tid);
+    const float4 *gb = w.boxes + g.roff[img];
+    for (int j = tid; j < k; j += 1024) {
+        const unsigned long long key = tkey[j];
+        const int cls = (int)(key & ((1ull << kDwClsBits) - 1ull)), row = (int)((key >> kDwClsBits) & kDwRowMask);
+        const int64_t slot = (int64_t)img * topk + j;
+        out_boxes[slot] = gb[row];
+        out_scores[slot] = __uint_as_float(~(unsigned)(key >> (kDwRowBits + kDwClsBits)));
+        out_classes[slot] = cls;
+        out_rows[slot] = row;
+    }
+    if (tid == 0) counts[img] = k;
+}
+
+// the plan of a call and its workspace size, from host data only; < 0 on an argument error (set_error has run)
+static int64_t dw_plan(const int *row_offsets, int n_images, int K, int per_class_above, DwPlan *p, const char *who)
+{
+    LOCOV_REQUIRE(n_images >= 0 && n_images <= kDwMaxImages, "%s: too many images (0..%d per call)", who, kDwMaxImages);
+    if (n_images == 0) return 0;
+    LOCOV_REQUIRE(row_offsets, "%s: null row_offsets", who);
+    LOCOV_REQUIRE(K >= 1 && K < (1 << kDwClsBits), "%s: too many classes (1..%d)", who, (1 << kDwClsBits) - 1);
+    LOCOV_REQUIRE(row_offsets[0] == 0, "%s: offsets start at 0", who);
+    p->n_img = n_images;
+    p->K = K;
+    p->pca = per_class_above;
+    p->cbase[0] = 0;
+    int64_t R = 0, mw = 0, ow = 0;
+    for (int i = 0; i < n_images; i++) {
+        const int64_t rows = (int64_t)row_offsets[i + 1] - row_offsets[i];
+        LOCOV_REQUIRE(rows >= 0, "%s: offsets must be non-decreasing", who);
+        LOCOV_REQUIRE(rows < (1 << kDwRowBits), "%s: too many rows (at most %d proposals per image)", who, (1 << kDwRowBits) - 1);
+        const int64_t W = (rows + 63) / 64;
+        const int64_t cap = per_class_above <= 0 ? 0 : (per_class_above - 1 < rows * K ? per_class_above - 1 : rows * K);
+        p->W[i] = (int)W;
+        p->mbase[i] = mw;
+        p->ovbase[i] = ow;
+        mw += rows * W;
+        ow += cap * W;
+        p->cbase[i + 1] = p->cbase[i] + (int)((rows + kDwChunkRows - 1) / kDwChunkRows);
+        R += rows;
+    }
+    LOCOV_REQUIRE(R * K <= 0x7fffffff, "%s: too many candidate slots (rows x classes must stay below 2^31)", who);
+    if (R == 0) return 0;
+    const int64_t nK = (int64_t)n_images * K;
+    return 16 * R + 16 * nK + (int64_t)n_images * (128 + 4 * kDwPasses * kDwBins + 8 * kDwCap) + 8 * (mw + ow + R * K);
+}
+
+}  // namespace locov
+
+using namespace locov;
+
+extern "C" {
+
+int64_t locov_detect_postprocess_wide_workspace_bytes(const int *row_offsets, int n_images, int num_classes, int per_class_above)
+{
+    DwPlan p;
+    return dw_plan(row_offsets, n_images, num_classes, per_class_above, &p, "locov_detect_postprocess_wide_workspace_bytes");
+}
+
+int locov_detect_postprocess_wide(const float *probs, int64_t ld_probs, int num_classes, const float *deltas, const float *proposal_boxes,
+                                  const int *row_offsets, const float *image_hw, int n_images, float wx, float wy, float ww, float wh,
+                                  float scale_clamp, float score_thresh, float nms_thresh, int topk, int per_class_above, void *workspace,
+                                  int64_t workspace_bytes, float *out_boxes, float *out_scores, int64_t *out_classes, int64_t *out_rows,
+                                  int *counts_and_flags, locov_stream_t stream)
+{
+    const char *who = "locov_detect_postprocess_wide";
+    DwPlan p;
+    const int64_t need = dw_plan(row_offsets, n_images, num_classes, per_class_above, &p, who);
+    if (need < 0) return (int)need;
+    if (n_images == 0) return LOCOV_OK;
+    LOCOV_REQUIRE(image_hw, "%s: null image_hw", who);
+    LOCOV_REQUIRE(topk >= 1 && topk <= LOCOV_DETECT_MAX_CANDIDATES, "%s: topk out of range (1..%d)", who, LOCOV_DETECT_MAX_CANDIDATES);
+    LOCOV_REQUIRE(ld_probs >= (int64_t)num_classes + 1, "%s: ld_probs must cover the K + 1 columns", who);
+    LOCOV_REQUIRE(wx != 0.f && wy != 0.f && ww != 0.f && wh != 0.f, "%s: zero box weight", who);
+    LOCOV_REQUIRE(counts_and_flags, "%s: null pointer (counts_and_flags)", who);
+    const int64_t R = row_offsets[n_images];
+    LOCOV_REQUIRE(R == 0 || (probs && deltas && proposal_boxes && workspace && out_boxes && out_scores && out_classes && out_rows),
+                  "%s: null pointer", who);
+    LOCOV_REQUIRE(workspace_bytes >= need, "%s: workspace too small (%lld bytes, need %lld)", who, (long long)workspace_bytes, (long long)need);
+    LOCOV_REQUIRE(((uintptr_t)deltas | (uintptr_t)proposal_boxes | (uintptr_t)workspace | (uintptr_t)out_boxes) % 16 == 0,
+                  "%s: boxes / workspace must be 16-byte aligned", who);
+    DetGeom g{};
+    g.n_img = n_images;
+    for (int i = 0; i <= n_images; i++) g.roff[i] = row_offsets[i];
+    for (int i = 0; i < n_images; i++) {
+        g.h[i] = image_hw[2 * i];
+        g.w[i] = image_hw[2 * i + 1];
+    }
+    hipStream_t s = as_stream(stream);
+    hipError_t e = hipMemsetAsync(counts_and_flags, 0, sizeof(int) * (size_t)(n_images + 1), s);
+    if (e != hipSuccess) return set_error(LOCOV_ERR_LAUNCH, "%s: memset: %s", who, hipGetErrorString(e));
+    if (R == 0) return LOCOV_OK;
+    const int K = num_classes;
+    const int64_t nK = (int64_t)n_images * K;
+    char *ws = static_cast<char *>(workspace);
+    DwWork w;
+    w.boxes = reinterpret_cast<float4 *>(ws);
+    ws += 16 * R;
+    char *zero0 = ws;                                            // info, histograms, class counts, survivors: zeroed per call
+    w.info = reinterpret_cast<DwImage *>(ws);
+    ws += 128 * (int64_t)n_images;
+    w.hist = reinterpret_cast<int *>(ws);
+    ws += (int64_t)4 * kDwPasses * kDwBins * n_images;
+    w.cnt = reinterpret_cast<int *>(ws);
+    w.kept = w.cnt + nK;
+    const size_t zero_bytes = (size_t)(reinterpret_cast<char *>(w.kept + nK) - zero0);
+    w.seg_off = w.kept + nK;
+    w.cursor = w.seg_off + nK;
+    ws = reinterpret_cast<char *>(w.cursor + nK);
+    w.gbuf = reinterpret_cast<unsigned long long *>(ws);
+    ws += (int64_t)8 * kDwCap * n_images;
+    w.M = reinterpret_cast<unsigned long long *>(ws);
+    int64_t mw = 0, ow = 0;
+    for (int i = 0; i < n_images; i++) {
+        const int64_t rows = g.roff[i + 1] - g.roff[i];
+        mw += rows * p.W[i];
+        const int64_t cap = per_class_above <= 0 ? 0 : (per_class_above - 1 < rows * K ? per_class_above - 1 : rows * K);
+        ow += cap * p.W[i];
+    }
+    w.ov = w.M + mw;
+    w.keys = w.ov + ow;
+    w.flags = counts_and_flags + n_images;
+    e = hipMemsetAsync(zero0, 0, zero_bytes, s);
+    if (e != hipSuccess) return set_error(LOCOV_ERR_LAUNCH, "%s: memset: %s", who, hipGetErrorString(e));
+
+    static int attr_state[64] = {};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return set_error(LOCOV_ERR_LAUNCH, "%s: hipGetDevice", who);
+    const int lds_max = kDwCap * 8;
+    if (attr_state[dev] == 0)
+        attr_state[dev] = (hipFuncSetAttribute(reinterpret_cast<const void *>(dw_segsort_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                               lds_max) == hipSuccess &&
+                           hipFuncSetAttribute(reinterpret_cast<const void *>(dw_topk_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                               lds_max) == hipSuccess) ? 1 : -1;
+    if (attr_state[dev] != 1) return set_error(LOCOV_ERR_LAUNCH, "%s: cannot raise the dynamic LDS limit to %d bytes", who, lds_max);
+
+    const float inv_wx = 1.0f / wx, inv_wy = 1.0f / wy, inv_ww = 1.0f / ww, inv_wh = 1.0f / wh;
+    hipLaunchKernelGGL(det_decode_clip_kernel, dim3((unsigned)ceil_div(R, 256)), dim3(256), 0, s, reinterpret_cast<const float4 *>(deltas),
+                       reinterpret_cast<const float4 *>(proposal_boxes), (int)R, g, inv_wx, inv_wy, inv_ww, inv_wh, scale_clamp, w.boxes, w.flags);
+    const dim3 tiles((unsigned)p.cbase[n_images], (unsigned)ceil_div(K + 1, 256));
+    hipLaunchKernelGGL(dw_count_kernel, tiles, dim3(256), 0, s, probs, ld_probs, score_thresh, g, p, w);
+    hipLaunchKernelGGL(dw_scan_kernel, dim3(1), dim3(1024), 0, s, p, w);
+    hipLaunchKernelGGL(dw_emit_kernel, tiles, dim3(256), 0, s, probs, ld_probs, score_thresh, g, p, w);
+    int max_rows = 0;
+    int64_t max_items = 0;
+    for (int i = 0; i < n_images; i++) {
+        const int rows = g.roff[i + 1] - g.roff[i];
+        max_rows = rows > max_rows ? rows : max_rows;
+        const int64_t cap = per_class_above <= 0 ? 0 : (per_class_above - 1 < (int64_t)rows * K ? per_class_above - 1 : (int64_t)rows * K);
+        const int64_t items = (int64_t)rows * p.W[i] > cap ? (int64_t)rows * p.W[i] : cap;
+        max_items = items > max_items ? items : max_items;
+    }
+    int P = 2;
+    while (P < max_rows) P <<= 1;
+    hipLaunchKernelGGL(dw_segsort_kernel, dim3((unsigned)nK), dim3(256), (size_t)P * 8, s, w);
+    if (max_items > 0)
+        hipLaunchKernelGGL(dw_overlap_kernel, dim3((unsigned)ceil_div(max_items, 256), (unsigned)n_images), dim3(256), 0, s, g, p, w, nms_thresh);
+    if (max_rows <= 64 * 64)
+        hipLaunchKernelGGL(dw_sweep_kernel<1>, dim3((unsigned)ceil_div(nK, 4)), dim3(256), 0, s, p, w);
+    else
+        hipLaunchKernelGGL(dw_sweep_kernel<4>, dim3((unsigned)ceil_div(nK, 4)), dim3(256), 0, s, p, w);
+    const dim3 class_chunks((unsigned)ceil_div(K, kDwClassChunk), (unsigned)n_images);
+    for (int pass = 0; pass < kDwPasses; pass++) hipLaunchKernelGGL(dw_select_kernel, class_chunks, dim3(256), 0, s, p, w, topk, pass);
+    hipLaunchKernelGGL(dw_gather_kernel, class_chunks, dim3(256), 0, s, p, w);
+    hipLaunchKernelGGL(dw_topk_kernel, dim3((unsigned)n_images), dim3(1024), (size_t)lds_max, s, g, w, topk,
+                       reinterpret_cast<float4 *>(out_boxes), out_scores, out_classes, out_rows, counts_and_flags);
+    return check_launch(who);
+}
+
+}  // extern "C"

@@ -802,6 +802,15 @@ def detect_postprocess(probs: torch.Tensor, deltas: torch.Tensor, proposal_boxes
     Returns (boxes [B, topk, 4], scores [B, topk], classes [B, topk] int64, rows [B, topk] int64, counts: list of B ints), or None
     when the kernels flagged a case they do not take (non-finite values, more than DETECT_MAX_CANDIDATES candidates in an image):
     the caller then runs the torch chain."""
+    out, flags = _detect_postprocess_flags(probs, deltas, proposal_boxes, sizes, image_shapes, weights, scale_clamp, score_thresh,
+                                           nms_thresh, topk)
+    return None if flags else out
+
+
+def _detect_postprocess_flags(probs, deltas, proposal_boxes, sizes, image_shapes, weights, scale_clamp, score_thresh, nms_thresh, topk,
+                              per_class_above=None):
+    """detect_postprocess's work, with the flag word (DETECT_FLAG_*) returned next to the outputs instead of folded into None.
+    per_class_above=None: the LDS pipeline (locov_detect_postprocess); an int: the wide one (locov_detect_postprocess_wide)."""
     probs, deltas, proposal_boxes = _dev(probs, "probs"), _dev(deltas, "deltas"), _dev(proposal_boxes, "proposal_boxes")
     B, R, K = len(sizes), probs.shape[0], probs.shape[1] - 1
     if not (tuple(deltas.shape) == (R, 4) and tuple(proposal_boxes.shape) == (R, 4) and sum(sizes) == R and len(image_shapes) == B):
@@ -813,7 +822,13 @@ def detect_postprocess(probs: torch.Tensor, deltas: torch.Tensor, proposal_boxes
     dev = probs.device
     offs = (ctypes.c_int * (B + 1))(0, *itertools.accumulate(int(n) for n in sizes))
     hw = (ctypes.c_float * (2 * B))(*[float(v) for shape in image_shapes for v in shape[:2]])
-    nbytes = int(lib.locov_detect_postprocess_workspace_bytes(max(R, 1), B))
+    if per_class_above is None:
+        nbytes = int(lib.locov_detect_postprocess_workspace_bytes(max(R, 1), B))
+    else:
+        per_class_above = max(min(int(per_class_above), 2 ** 31 - 1), -2 ** 31)
+        nbytes = int(lib.locov_detect_postprocess_wide_workspace_bytes(offs, B, K, per_class_above))
+        if nbytes < 0:
+            check(nbytes, "locov_detect_postprocess_wide_workspace_bytes")
     ws = _workspace("detect", probs, nbytes)
     out_boxes = torch.empty((B, topk, 4), dtype=torch.float32, device=dev)
     out_scores = torch.empty((B, topk), dtype=torch.float32, device=dev)
@@ -822,10 +837,17 @@ def detect_postprocess(probs: torch.Tensor, deltas: torch.Tensor, proposal_boxes
     counts = torch.empty((B + 1,), dtype=torch.int32, device=dev)
     wx, wy, ww, wh = (float(w) for w in weights)
     with torch.cuda.device(dev):
-        check(lib.locov_detect_postprocess(_ptr(probs), probs.stride(0), K, _ptr(deltas), _ptr(proposal_boxes), offs, hw, B, wx, wy, ww, wh,
-                                           float(scale_clamp), float(score_thresh), float(nms_thresh), int(topk), _ptr(ws), ws.numel(),
-                                           _ptr(out_boxes), _ptr(out_scores), _ptr(out_classes), _ptr(out_rows), _ptr(counts),
-                                           _stream(probs)), "locov_detect_postprocess")
+        if per_class_above is None:
+            check(lib.locov_detect_postprocess(_ptr(probs), probs.stride(0), K, _ptr(deltas), _ptr(proposal_boxes), offs, hw, B, wx, wy, ww,
+                                               wh, float(scale_clamp), float(score_thresh), float(nms_thresh), int(topk), _ptr(ws),
+                                               ws.numel(), _ptr(out_boxes), _ptr(out_scores), _ptr(out_classes), _ptr(out_rows),
+                                               _ptr(counts), _stream(probs)), "locov_detect_postprocess")
+        else:
+            check(lib.locov_detect_postprocess_wide(_ptr(probs), probs.stride(0), K, _ptr(deltas), _ptr(proposal_boxes), offs, hw, B, wx,
+                                                    wy, ww, wh, float(scale_clamp), float(score_thresh), float(nms_thresh), int(topk),
+                                                    per_class_above, _ptr(ws), ws.numel(), _ptr(out_boxes), _ptr(out_scores),
+                                                    _ptr(out_classes), _ptr(out_rows), _ptr(counts), _stream(probs)),
+                  "locov_detect_postprocess_wide")
     # the ONE host read: B + 1 ints to pinned memory behind an event (the stream's later work stays queued)
     key = (dev, torch.cuda.current_stream(dev).cuda_stream)
     host = _DETECT_PINNED.get(key)
@@ -836,9 +858,18 @@ def detect_postprocess(probs: torch.Tensor, deltas: torch.Tensor, proposal_boxes
     ev.record(torch.cuda.current_stream(dev))
     ev.synchronize()
     vals = host[:B + 1].tolist()
-    if vals[B]:
-        return None
-    return out_boxes, out_scores, out_classes, out_rows, vals[:B]
+    return (out_boxes, out_scores, out_classes, out_rows, vals[:B]), vals[B]
+
+
+def detect_postprocess_wide(probs: torch.Tensor, deltas: torch.Tensor, proposal_boxes: torch.Tensor, sizes, image_shapes, weights,
+                            scale_clamp: float, score_thresh: float, nms_thresh: float, topk: int, per_class_above: int):
+    """detect_postprocess for ANY candidate count (csrc/detect_wide.hip): LVIS-style thresholds (1e-4 over 1 203 classes: up to
+    1.2e6 candidates per image) stay on the device with ONE host read.  per_class_above: batched_nms's switch -- an image with that
+    many candidates or more runs one NMS per class on the unshifted boxes, below it one NMS on the class-shifted boxes.
+    Returns what detect_postprocess returns; None only when the kernels flagged non-finite values (the caller runs the torch chain)."""
+    out, flags = _detect_postprocess_flags(probs, deltas, proposal_boxes, sizes, image_shapes, weights, scale_clamp, score_thresh,
+                                           nms_thresh, topk, per_class_above=per_class_above)
+    return None if flags else out
 
 
 # --------------------------------------------------------------------------------------

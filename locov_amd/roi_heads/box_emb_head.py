@@ -412,8 +412,9 @@ class FastRCNNOutputLayers(nn.Module):
     def _inference_fused(self, predictions, proposals):
         """predict_boxes + predict_probs + fast_rcnn_inference as ONE device pipeline (ops.detect_postprocess: csrc/detect.hip)
         for the case both reference configurations evaluate: class-agnostic box regression on device fp32 tensors, a top-k.
-        Returns None for anything else -- and when the kernels flag non-finite values or too many candidates -- so that the
-        caller runs the torch chain; the detections are bit-identical to that chain's (tests/test_gpu_postprocess.py)."""
+        Returns None for anything else -- and when the kernels flag non-finite values -- so that the caller runs the torch chain;
+        an image with more candidates than the LDS pipeline holds goes to ops.detect_postprocess_wide (csrc/detect_wide.hip).  The
+        detections are bit-identical to the chain's (tests/test_gpu_postprocess.py, tests/test_gpu_detect_wide.py)."""
         if not _FUSED_POSTPROCESS or not len(proposals):
             return None
         scores, deltas = predictions
@@ -428,11 +429,26 @@ class FastRCNNOutputLayers(nn.Module):
             return None
         image_shapes = [x.image_size for x in proposals]
         probs = F.softmax(scores, dim=-1)                                  # (torch's own softmax: predict_probs' values)
-        out = ops.detect_postprocess(probs, deltas, cat_rows(pieces), sizes, image_shapes, self.box2box_transform.weights,
-                                     self.box2box_transform.scale_clamp, self.test_score_thresh, self.test_nms_thresh,
-                                     self.test_topk_per_image)
+        args = (probs, deltas, cat_rows(pieces), sizes, image_shapes, self.box2box_transform.weights, self.box2box_transform.scale_clamp,
+                self.test_score_thresh, self.test_nms_thresh, self.test_topk_per_image)
+        # More candidates in an image than the LDS pipeline holds (LVIS-style thresholds): csrc/detect_wide.hip takes any count.  The
+        # predictor remembers such a setting, so that later calls skip the LDS attempt and its host read.
+        overflowed = getattr(self, "_detect_overflow", None)
+        if overflowed is None:
+            overflowed = self._detect_overflow = set()
+        setting = (float(self.test_score_thresh), int(self.test_topk_per_image), K)
+        out = None
+        if setting not in overflowed:
+            out, flags = ops._detect_postprocess_flags(*args)
+            if flags & ops._lib.DETECT_FLAG_NONFINITE:
+                return None
+            if flags & ops._lib.DETECT_FLAG_OVERFLOW:
+                overflowed.add(setting)
+                out = None
         if out is None:
-            return None
+            out = ops.detect_postprocess_wide(*args, per_class_above=_PER_CLASS_NMS_ABOVE)
+            if out is None:
+                return None
         boxes, det_scores, classes, rows, counts = out
         instances_cls, boxes_cls = boxes_class_of(proposals)
         results, kept = [], []
