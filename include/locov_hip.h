@@ -289,6 +289,21 @@ int locov_token_attention_fwd(const float *sim, int64_t R, int Ttot, const int *
                               int cosine, int hardmax, const float *gmin, float *scores,
                               float *att, locov_stream_t stream);
 
+/* The way back through the same lines under autograd (box_emb_grounding_head.py:152-183 with DETACH_CLASS_PREDICTOR off:
+ * loss_cls reaches emb_pred's input through the masked softmax / hardmax and the attention-weighted distance).  The attention
+ * is recomputed from sim and gmin; nothing else is saved by the forward.
+ *   grad_scores [R, K1]       upstream gradient of scores
+ *   grad_att [R, K1, Tmax]    upstream gradient of att, or null (the predictor drops the attention)
+ *   grad_sim [R, Ttot]        written completely: class k owns the columns [tok_off[k], tok_off[k] + max(num_tok[k], 1)) and
+ *                             the classes' ranges must partition [0, Ttot), so every element has exactly one writer (no atomics,
+ *                             no zeroed buffer, the same bits on every run).  A token-less class's column, and under cosine a
+ *                             NaN similarity (zeroed by the forward), get 0; gmin gets no gradient (detached in the reference);
+ *                             under hardmax the one-hot attention is a constant and grad_att contributes nothing. */
+int locov_token_attention_bwd(const float *sim, int64_t R, int Ttot, const int *tok_off,
+                              const int *num_tok, int K1, int Tmax, float temperature,
+                              int cosine, int hardmax, const float *gmin, const float *grad_scores,
+                              const float *grad_att, float *grad_sim, locov_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------
  * Opt-in reduced-precision form of the Res5 GEMMs (MODEL.ROI_BOX_HEAD.RES5_DTYPE: "bf16"; the default
  * and the parity path are fp32): bf16 operands on the bf16 MFMA pipe, fp32 accumulate, fp32 epilogue

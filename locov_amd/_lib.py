@@ -106,6 +106,7 @@ SIGNATURES = {
     "locov_grounding_fwd": (c_int, [_p, c_int, c_int, c_int, _p, _p, c_float, _p, _p, _p]),
     "locov_grounding_bwd": (c_int, [_p, c_int, c_int, c_int, _p, _p, c_float, _p, _p, _p, _p]),
     "locov_token_attention_fwd": (c_int, [_p, c_int64, c_int, _p, _p, c_int, c_int, c_float, c_int, c_int, _p, _p, _p, _p]),
+    "locov_token_attention_bwd": (c_int, [_p, c_int64, c_int, _p, _p, c_int, c_int, c_float, c_int, c_int, _p, _p, _p, _p, _p]),
     "locov_rownorm_fwd": (c_int, [_p, c_int64, c_int, c_int, c_float, _p, _p]),
     "locov_rownorm_bwd": (c_int, [_p, _p, c_int64, c_int, c_int, c_float, _p, _p]),
     "locov_pool_fc_bwd_workspace_bytes": (c_int64, [c_int64, c_int, c_int]),

@@ -1906,3 +1906,45 @@ def token_attention(sim: torch.Tensor, tok_off: torch.Tensor, num_tok: torch.Ten
                                                     float(temperature), int(cosine), int(hardmax), _ptr(gmin),
                                                     _ptr(scores), _ptr(att), _stream(sim)), "locov_token_attention_fwd")
     return scores, att
+
+
+class _TokenAttentionFn(torch.autograd.Function):
+    """token_attention() with locov_token_attention_bwd as its backward: the attention is recomputed from sim and gmin."""
+
+    @staticmethod
+    def forward(ctx, sim, tok_off, num_tok, tmax, temperature, gmin, cosine, hardmax):
+        sim = _dev(sim.detach(), "sim")
+        gmin = _dev(gmin.detach().reshape(1), "gmin")
+        ctx.save_for_backward(sim, tok_off, num_tok, gmin)
+        ctx.set_materialize_grads(False)                     # an unused attention sends None -> a null pointer, not zeros
+        ctx.args = (int(tmax), float(temperature), bool(cosine), bool(hardmax))
+        return token_attention(sim, tok_off, num_tok, tmax, temperature, gmin, cosine=cosine, hardmax=hardmax)
+
+    @staticmethod
+    def backward(ctx, g_scores, g_att):
+        sim, tok_off, num_tok, gmin = ctx.saved_tensors
+        tmax, temperature, cosine, hardmax = ctx.args
+        none = (None,) * 8
+        if g_scores is None and g_att is None:
+            return none
+        R, Ttot = sim.shape
+        K1 = num_tok.numel()
+        g_scores = _dev(g_scores, "grad_scores") if g_scores is not None else sim.new_zeros((R, K1))
+        g_att = _dev(g_att, "grad_att") if g_att is not None else None
+        tok_off, num_tok = _dev(tok_off, "tok_off", torch.int32), _dev(num_tok, "num_tok", torch.int32)
+        g_sim = torch.empty_like(sim)
+        with torch.cuda.device(sim.device):
+            check(_lib.load().locov_token_attention_bwd(_ptr(sim), R, Ttot, _ptr(tok_off), _ptr(num_tok), K1, tmax, temperature,
+                                                        int(cosine), int(hardmax), _ptr(gmin), _ptr(g_scores), _ptr(g_att),
+                                                        _ptr(g_sim), _stream(sim)), "locov_token_attention_bwd")
+        return (g_sim,) + none[1:]
+
+
+def token_attention_autograd(sim: torch.Tensor, tok_off: torch.Tensor, num_tok: torch.Tensor, tmax: int, temperature: float,
+                             gmin: torch.Tensor, cosine: bool = False, hardmax: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """token_attention(), differentiable in sim: scores and attention are both differentiable outputs, gmin is a constant
+    (the reference detaches it).  The classes' column ranges [tok_off[k], tok_off[k] + max(num_tok[k], 1)) must partition
+    [0, Ttot) -- GroundingModule.set_class_embeddings builds them so."""
+    if torch.is_grad_enabled() and sim.requires_grad:
+        return _TokenAttentionFn.apply(sim, tok_off, num_tok, tmax, temperature, gmin, cosine, hardmax)
+    return token_attention(sim.detach(), tok_off, num_tok, tmax, temperature, gmin.detach(), cosine=cosine, hardmax=hardmax)

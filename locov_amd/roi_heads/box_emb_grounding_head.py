@@ -9,7 +9,9 @@ never defined); `locov_amd.config.get_cfg()` defines the key, which makes the ya
 
 Device arithmetic: the token-similarity Linear is the f32 MFMA NT GEMM (`ops.linear`), everything
 after it is one kernel (`locov_token_attention_fwd`), instead of a per-class Python loop over padded tensors.
-Inference only (the reference builds it with frozen class tokens; the LSM configs never train through it).
+Training and inference: with gradients enabled `loss_cls` reaches the predictor's input through `locov_token_attention_bwd`,
+`locov_sim_gemm_bwd` (the class tokens stay frozen, as the reference builds them), `locov_rownorm_bwd` and `locov_pool_fc_bwd`
+-- the STT fine-tune (`configs/coco_stt.yaml`: DETACH_CLASS_PREDICTOR off, `emb_pred` frozen but passed through).
 """
 from __future__ import annotations
 
@@ -93,22 +95,30 @@ class GroundingModule(nn.Module):
         self._padded = any(w < tmax for w in width)
 
     # ------------------------------------------------------------------ forward (:199-225)
-    @torch.no_grad()
     def forward(self, image_emb: torch.Tensor):
-        """image_emb [R, D] -> (scores [R, K+1] = -global distance, token attention [R, K+1, Tmax])."""
+        """image_emb [R, D] -> (scores [R, K+1] = -global distance, token attention [R, K+1, Tmax]).  Differentiable in
+        image_emb (the token bank is frozen, :255-256); under torch.no_grad() / without a gradient to carry: the same kernels,
+        no autograd nodes."""
         if self.token_score is None:
             raise RuntimeError("set_class_embeddings() must be called before forward()")
-        sim = ops.linear(image_emb.detach(), self.token_score.weight, self.token_score.bias)      # :103 / :106
+        train = torch.is_grad_enabled() and image_emb.requires_grad
+        if train:       # grad_emb = grad_sim . class_emb (locov_sim_gemm_bwd); the bank gets none
+            sim = ops.sim_gemm_autograd(image_emb, self.token_score.weight, self.token_score.bias)     # :103 / :106
+        else:
+            sim = ops.linear(image_emb.detach(), self.token_score.weight, self.token_score.bias)      # :103 / :106
         cosine = self.local_metric == "cosine"
-        s = torch.nan_to_num(sim, nan=0.0, posinf=float("inf"), neginf=float("-inf")) if cosine else sim
-        # minimum of the reference's zero-padded [R, K+1, Tmax] similarity tensor (:167-169)
+        sim_d = sim.detach()
+        s = torch.nan_to_num(sim_d, nan=0.0, posinf=float("inf"), neginf=float("-inf")) if cosine else sim_d
+        # minimum of the reference's zero-padded [R, K+1, Tmax] similarity tensor (:167-169; `.min().detach()`: a constant)
         gmin = (s / self.temperature).min() if s.numel() else s.new_zeros(())
         if self._padded:
             gmin = torch.minimum(gmin, gmin.new_zeros(()))
         tmax = self.mask_emb.shape[1]
-        scores, att = ops.token_attention(sim, self._tok_off, self._tok_cnt, tmax, self.temperature, gmin,
-                                          cosine=cosine, hardmax=self.alignment == "hardmax")
+        scores, att = ops.token_attention_autograd(sim, self._tok_off, self._tok_cnt, tmax, self.temperature, gmin,
+                                                   cosine=cosine, hardmax=self.alignment == "hardmax")
         if self.return_similarity:
+            if train:   # the tuples follow from sim and carry its gradient (0 where a NaN was replaced, as torch.where's)
+                s = torch.where(torch.isnan(sim), torch.zeros_like(sim), sim) if cosine else sim
             loc_sim = s / self.temperature
             loc_dis = ((1 - s) if cosine else -s) / self.temperature
             return scores, att, (torch.split(loc_sim, self._split, dim=1), torch.split(loc_dis, self._split, dim=1))
@@ -172,18 +182,27 @@ class EmbeddingGroundingFastRCNNOutputLayers(FastRCNNOutputLayers):
         """(scores [R,K+1], proposal_deltas [R,4]) (:395-417)."""
         if x.dim() > 2:
             x = torch.flatten(x, start_dim=1)
-        proposal_deltas = hip_linear(x, self.bbox_pred)
-        if self.detach_cls_predictor:
-            with torch.no_grad():
-                scores = self.forward_cls_prediction(x.detach())
-        else:
-            scores = self.forward_cls_prediction(x)
-        return scores, proposal_deltas
+        if self.detach_cls_predictor or not self.embedding_based:
+            proposal_deltas = hip_linear(x, self.bbox_pred)
+            if self.detach_cls_predictor:                                 # :400-404: only bbox_pred carries a gradient
+                with torch.no_grad():
+                    scores = self.forward_cls_prediction(x.detach())
+            else:
+                scores = self.forward_cls_prediction(x)
+            return scores, proposal_deltas
+        needs_grad = torch.is_grad_enabled() and (x.requires_grad or self.bbox_pred.weight.requires_grad
+                                                  or self.emb_pred.weight.requires_grad)
+        if needs_grad:
+            # both FCs read x: one autograd node, one backward call (locov_pool_fc_bwd) that accumulates grad_x across them
+            emb, proposal_deltas = ops.pool_fc_autograd(x, self.emb_pred.weight, self.emb_pred.bias, self.bbox_pred.weight,
+                                                        self.bbox_pred.bias)
+            return self.forward_cls_prediction(x, emb=emb), proposal_deltas
+        return self.forward_cls_prediction(x), hip_linear(x, self.bbox_pred)
 
-    def forward_cls_prediction(self, x):                                  # :419-427
+    def forward_cls_prediction(self, x, emb=None):                        # :419-427 (emb: emb_pred(x) when already formed)
         if not self.embedding_based:
             return self.cls_score(x)
-        x = hip_linear(x, self.emb_pred)
+        x = hip_linear(x, self.emb_pred) if emb is None else emb
         if self.normalize_emb:
             x = _rownorm(x, ops.NORM_L2)
         scores, _ = self.cls_score(x)
