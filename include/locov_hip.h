@@ -33,7 +33,7 @@ extern "C" {
 #endif
 
 /* 8: locov_detect_postprocess; later, additively: locov_grounding_ce_dist_fwd / _bwd, locov_distill_loss_fwd / _bwd,
- *    locov_detect_postprocess_wide (+ _workspace_bytes) */
+ *    locov_detect_postprocess_wide (+ _workspace_bytes), locov_regions_select / _gather_fwd / _gather_bwd */
 #define LOCOV_ABI_VERSION 8
 
 #define LOCOV_OK 0
@@ -876,6 +876,50 @@ int locov_roi_align_nhwc_bwd(const float *grad_rows, int64_t grad_ld, int N, int
                              const float *rois, int64_t R, int pooled_h, int pooled_w, float spatial_scale,
                              int sampling_ratio, int aligned, int bin_stride, int pos_major, float *grad_feat,
                              locov_stream_t stream);
+
+/* The grounding branches' region dictionaries (csrc/regions.hip): what ovr/modeling/meta_arch/distill_prop_mmss_gcnn.py:273-328
+ * (`input_image`: the whole-image grid) and :348-399 (`input_boxes`: the sampled boxes) assemble on the host with numpy loops, one
+ * fancy-index per image, pad_sequence and blocking torch.tensor(numpy).cuda() copies -- here one selection launch and one gather
+ * launch per branch, one scatter launch per branch backward, no host wait.
+ *
+ * locov_regions_select : per image i (one workgroup; B <= LOCOV_REGIONS_MAX_B, everything per-image is a HOST array passed on as
+ *     launch arguments), slot r receives the valid candidate with the r-th smallest (key, candidate index) pair -- the first
+ *     slots of a stable argsort of the keys over the valid candidates, which stands in for np.random.shuffle (:308, :358).
+ *       mode LOCOV_REGIONS_GRID     :302-320.  count_host[i] = gh * gw cells (row-major, grid_w = gw); a cell (y, x) is valid when
+ *                                   y < ext_a_host[i] and x < ext_b_host[i] (the extents of :281-284, formed by the caller);
+ *                                   image i fills min(limit, valid_i) slots (limit = SPATIAL_DROPOUT); loc = ((x + 0.5) /
+ *                                   ext_b, (y + 0.5) / ext_a) (:293-296).
+ *       mode LOCOV_REGIONS_GRID_ALL :285-300 without the subsampling of :302: n = mask_w = gh * gw, slot = cell, mask = the valid
+ *                                   extent, loc = 0 outside it; keys / indices / src_row / inv are not touched (may be NULL).
+ *       mode LOCOV_REGIONS_BOXES    :349-391.  count_host[i] = boxes of image i (all valid), boxes_host[i] = its [count, 4]
+ *                                   fp32 XYXY boxes (a HOST array of device pointers), ext_a_host / ext_b_host = image height /
+ *                                   width; n <= every count; loc = ((x0 + x1) / 2 / width, (y0 + y1) / 2 / height) (:368-383).
+ *     keys [sum count] float64 (finite), image after image.  Outputs: indices [B, n] int64 (candidate of each slot within its
+ *     image, -1 = padding), src_row [B, n] int32 (the same as a row of the concatenated candidates), inv [sum count] int32
+ *     (candidate -> output row i * n + slot, -1 = not selected; what the backward reads), mask [B, mask_w] uint8 (1 for the filled
+ *     slots: `new_mask` :305 has width SPATIAL_DROPOUT, which may exceed n), loc [B, n, 2] fp32 (0 for padding, as pad_sequence
+ *     writes), mvm [B, mvm_w] fp32 zeros (`mvm_mask`, :326 / :397).  The quotients are IEEE fp32 divisions.
+ *     More than LOCOV_REGIONS_MAX_CANDIDATES candidates in one image (the keys' LDS budget) -> LOCOV_ERR_UNSUPPORTED.
+ * locov_regions_gather_fwd : out [B * n, C] = the source row src_row names, zeros where it is -1 (pad_sequence, :314 / :385).
+ *     layout LOCOV_REGIONS_ROWS: source row s at src + s * ld (channels-last grid features, box features; 16-byte lanes when
+ *     C % 4 == 0 and everything is 16-byte aligned); LOCOV_REGIONS_NCHW: src is [B, C, hw] contiguous and s = i * hw + cell.
+ * locov_regions_gather_bwd : the gradient of that w.r.t. the source, in the source's layout: grad_src ([rows, C] with row pitch ld |
+ *     [rows / hw, C, hw]) is written EVERYWHERE exactly once -- row inv[s] of grad_out [B * n, C], or zero -- no memset, no atomic. */
+#define LOCOV_REGIONS_MAX_B 64
+#define LOCOV_REGIONS_MAX_CANDIDATES 4096
+#define LOCOV_REGIONS_GRID 0
+#define LOCOV_REGIONS_GRID_ALL 1
+#define LOCOV_REGIONS_BOXES 2
+#define LOCOV_REGIONS_ROWS 0
+#define LOCOV_REGIONS_NCHW 1
+int locov_regions_select(const double *keys, int mode, int B, const int *count_host, const int *ext_a_host,
+                         const int *ext_b_host, int grid_w, const float *const *boxes_host, int n, int limit, int mask_w,
+                         int mvm_w, int64_t *indices, int *src_row, int *inv, uint8_t *mask, float *loc, float *mvm,
+                         locov_stream_t stream);
+int locov_regions_gather_fwd(const float *src, int layout, int64_t ld, int B, int n, int C, int64_t hw, const int *src_row,
+                             float *out, locov_stream_t stream);
+int locov_regions_gather_bwd(const float *grad_out, int layout, int64_t ld, int64_t rows, int C, int64_t hw, const int *inv,
+                             float *grad_src, locov_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -29,6 +29,9 @@ LABEL_MAX_IMAGES, LABEL_MAX_THRESHOLDS, SAMPLE_MAX_PROPOSALS = 64, 6, 4096
 ABI_VERSION = 8
 DETECT_MAX_CANDIDATES, DETECT_FLAG_NONFINITE, DETECT_FLAG_OVERFLOW = 8192, 1, 2
 DISTILL_KD, DISTILL_JS, DISTILL_MSE, DISTILL_MAX_B = 0, 1, 2, 64
+REGIONS_MAX_B, REGIONS_MAX_CANDIDATES = 64, 4096
+REGIONS_GRID, REGIONS_GRID_ALL, REGIONS_BOXES = 0, 1, 2
+REGIONS_ROWS, REGIONS_NCHW = 0, 1
 
 _p = c_void_p  # device pointer
 
@@ -168,6 +171,10 @@ SIGNATURES = {
                                          c_int, c_int, _p, _p]),
     "locov_box_head_fwd": (c_int, [_p, c_int64, c_int, c_int, c_int, _p, _p, _p, _p, _p, _p, c_int, c_int,
                                    c_int, c_int, _p, _p, _p, _p, _p, _p]),
+    "locov_regions_select": (c_int, [_p, c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int), c_int, POINTER(c_void_p), c_int, c_int,
+                                     c_int, c_int, _p, _p, _p, _p, _p, _p, _p]),
+    "locov_regions_gather_fwd": (c_int, [_p, c_int, c_int64, c_int, c_int, c_int, c_int64, _p, _p, _p]),
+    "locov_regions_gather_bwd": (c_int, [_p, c_int, c_int64, c_int64, c_int, c_int64, _p, _p, _p]),
 }
 
 _lib = None

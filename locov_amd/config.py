@@ -132,6 +132,10 @@ def get_cfg() -> CfgNode:
                 # the Res5 calls that leaves the predictor's launches queued) and an out-of-range forward is repeated on the f32
                 # MFMA; "deferred" = never read inside the step, acted on on the device (a skipped step), read with the next labelling
                 "RES5_TRAIN_GUARD": "sync",
+                # extension: memory layout of EmbeddingProposalsRes5ROIHeads' visual_grid_features.  "nchw": contiguous NCHW (one
+                # transpose of Res5's pixel rows each way); "channels_last": the same logical [N, C5, H/2, W/2] tensor as a view of
+                # those rows, no transpose -- for callers that only gather regions from it (mmss_regions.grid_regions)
+                "GRID_FEATURES_LAYOUT": "nchw",
             },
             "RESNETS": {
                 "NUM_GROUPS": 1, "WIDTH_PER_GROUP": 64, "RES2_OUT_CHANNELS": 256,

@@ -1948,3 +1948,127 @@ def token_attention_autograd(sim: torch.Tensor, tok_off: torch.Tensor, num_tok: 
     if torch.is_grad_enabled() and sim.requires_grad:
         return _TokenAttentionFn.apply(sim, tok_off, num_tok, tmax, temperature, gmin, cosine, hardmax)
     return token_attention(sim.detach(), tok_off, num_tok, tmax, temperature, gmin.detach(), cosine=cosine, hardmax=hardmax)
+
+
+# -------------------------------------------------------------------------------------- grounding branches' regions
+REGIONS_MAX_B = _lib.REGIONS_MAX_B                        # LOCOV_REGIONS_MAX_B
+REGIONS_MAX_CANDIDATES = _lib.REGIONS_MAX_CANDIDATES      # LOCOV_REGIONS_MAX_CANDIDATES
+
+
+class RegionSelection(NamedTuple):
+    """What locov_regions_select wrote (see include/locov_hip.h)."""
+    indices: Optional[torch.Tensor]      # [B, n] int64: candidate of each slot within its image, -1 = padding
+    src_row: Optional[torch.Tensor]      # [B, n] int32: the same as a row of the concatenated candidates
+    inv: Optional[torch.Tensor]          # [sum count] int32: candidate -> output row, -1 = not selected
+    mask: torch.Tensor                   # [B, mask_w] uint8
+    loc: torch.Tensor                    # [B, n, 2] fp32
+    mvm: torch.Tensor                    # [B, mvm_w] fp32 zeros
+
+
+def regions_select(mode: str, keys: Optional[torch.Tensor], counts, ext_a, ext_b, n: int, limit: int, mask_w: int, mvm_w: int, *,
+                   grid_w: int = 1, boxes: Optional[Sequence[torch.Tensor]] = None, device=None) -> RegionSelection:
+    """distill_prop_mmss_gcnn.py:285-320 (mode "grid"; "grid_all" when :302 is not taken) / :349-391 (mode "boxes"): which candidate
+    fills which slot, the mask, the loc rows and the zero mvm_mask, in one launch (locov_regions_select).  counts / ext_a / ext_b
+    are host integers per image and travel as launch arguments; `keys` is one float64 per candidate on the device."""
+    modes = {"grid": _lib.REGIONS_GRID, "grid_all": _lib.REGIONS_GRID_ALL, "boxes": _lib.REGIONS_BOXES}
+    if mode not in modes:
+        raise ValueError(f"regions_select: unknown mode {mode!r} (one of {sorted(modes)})")
+    B = len(counts)
+    if not 1 <= B <= REGIONS_MAX_B:
+        raise ValueError(f"regions_select: 1 <= B <= {REGIONS_MAX_B}, got {B}")
+    if len(ext_a) != B or len(ext_b) != B:
+        raise ValueError("regions_select: counts, ext_a and ext_b must have one entry per image")
+    total = int(sum(int(c) for c in counts))
+    if mode != "grid_all":
+        keys = _dev(keys, "keys", torch.float64)
+        if keys.numel() != total:
+            raise ValueError(f"regions_select: keys must hold one value per candidate ({total}), got {tuple(keys.shape)}")
+        device = keys.device
+    elif device is None:
+        raise ValueError("regions_select: mode 'grid_all' needs the device")
+    device = torch.device(device)
+    ptrs = None
+    if mode == "boxes":
+        if boxes is None or len(boxes) != B:
+            raise ValueError("regions_select: mode 'boxes' needs one [Ri, 4] box tensor per image")
+        boxes = [_dev(b, "boxes") for b in boxes]
+        for b, c in zip(boxes, counts):
+            if tuple(b.shape) != (int(c), 4):
+                raise ValueError(f"regions_select: boxes must be [{int(c)}, 4], got {tuple(b.shape)}")
+        ptrs = (ctypes.c_void_p * B)(*[b.data_ptr() for b in boxes])
+    ints = lambda v: (ctypes.c_int * B)(*[int(x) for x in v])
+    new = lambda shape, dt: torch.empty(shape, dtype=dt, device=device)
+    sel = mode != "grid_all"
+    out = RegionSelection(new((B, n), torch.int64) if sel else None, new((B, n), torch.int32) if sel else None,
+                          new((total,), torch.int32) if sel else None, new((B, mask_w), torch.uint8), new((B, n, 2), torch.float32),
+                          new((B, mvm_w), torch.float32))
+    with torch.cuda.device(device):
+        check(_lib.load().locov_regions_select(_ptr(keys) if sel else None, modes[mode], B, ints(counts), ints(ext_a), ints(ext_b), int(grid_w),
+                                               ptrs, int(n), int(limit), int(mask_w), int(mvm_w), _ptr(out.indices), _ptr(out.src_row),
+                                               _ptr(out.inv), _ptr(out.mask), _ptr(out.loc), _ptr(out.mvm), _stream(out.loc)),
+              "locov_regions_select")
+    return out
+
+
+def _regions_layout(src: torch.Tensor):
+    """How locov_regions_gather_* address `src`: ("rows", ld) for a [R, C] matrix (stride(1) == 1) or a logical [B, C, gh, gw] tensor
+    in channels-last memory; ("nchw", hw) for a contiguous [B, C, gh, gw]; None otherwise."""
+    if src.dim() == 2:
+        return ("rows", src.stride(0)) if src.stride(1) == 1 and src.stride(0) >= src.shape[1] else None
+    if src.dim() == 4:
+        if src.is_contiguous():
+            return ("nchw", src.shape[2] * src.shape[3])
+        if src.permute(0, 2, 3, 1).is_contiguous():
+            return ("rows", src.shape[1])
+    return None
+
+
+class _RegionsGatherFn(torch.autograd.Function):
+    """out [B, n, C] = the source rows locov_regions_select chose, zeros in the padding slots (the fancy-index + pad_sequence of
+    distill_prop_mmss_gcnn.py:311-316 / :361,:385); backward: the source-shaped gradient in the source's own memory layout, every
+    element written once (the selected slot's gradient or zero)."""
+
+    @staticmethod
+    def forward(ctx, src, src_row, inv):
+        if not (src.is_cuda and src.dtype == torch.float32 and _regions_layout(src) is not None):
+            src = _dev(src, "features")                      # (raises off the device; else a contiguous copy)
+        layout, arg = _regions_layout(src) or (("rows", src.shape[1]) if src.dim() == 2 else ("nchw", src.shape[2] * src.shape[3]))
+        B, n = src_row.shape
+        C = src.shape[1]
+        out = torch.empty((B, n, C), dtype=torch.float32, device=src.device)
+        nchw = layout == "nchw"
+        with torch.cuda.device(src.device):
+            check(_lib.load().locov_regions_gather_fwd(_ptr(src), _lib.REGIONS_NCHW if nchw else _lib.REGIONS_ROWS, 0 if nchw else arg, B, n, C,
+                                                       arg if nchw else 0, _ptr(src_row), _ptr(out), _stream(src)), "locov_regions_gather_fwd")
+        ctx.save_for_backward(inv)
+        ctx.src = (tuple(src.shape), nchw)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        (inv,) = ctx.saved_tensors
+        shape, nchw = ctx.src
+        g = _dev(g, "grad_region_features")
+        C = shape[1]
+        if len(shape) == 2:
+            gs = out = torch.empty(shape, dtype=torch.float32, device=g.device)
+        elif nchw:
+            gs = out = torch.empty(shape, dtype=torch.float32, device=g.device)
+        else:                                                  # channels-last memory, handed back as the same logical NCHW view
+            gs = torch.empty((shape[0], shape[2], shape[3], C), dtype=torch.float32, device=g.device)
+            out = gs.permute(0, 3, 1, 2)
+        with torch.cuda.device(g.device):
+            check(_lib.load().locov_regions_gather_bwd(_ptr(g), _lib.REGIONS_NCHW if nchw else _lib.REGIONS_ROWS, 0 if nchw else C, inv.numel(), C,
+                                                       shape[2] * shape[3] if nchw else 0, _ptr(inv), _ptr(gs), _stream(g)),
+                  "locov_regions_gather_bwd")
+        return out, None, None
+
+
+def regions_gather(src: torch.Tensor, selection: RegionSelection) -> torch.Tensor:
+    """The selected rows of `src` -- [R, C] box features, or the logical [B, C, gh, gw] grid features in NCHW-contiguous or
+    channels-last memory -- as [B, n, C], padding slots zero.  Differentiable in `src` (locov_regions_gather_fwd / _bwd)."""
+    rows = src.shape[0] if src.dim() == 2 else src.shape[0] * src.shape[2] * src.shape[3] if src.dim() == 4 else -1
+    if rows != selection.inv.numel():
+        raise ValueError(f"regions_gather: the selection is over {selection.inv.numel()} candidates, the features hold {rows}")
+    return _RegionsGatherFn.apply(src, selection.src_row, selection.inv)

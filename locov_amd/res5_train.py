@@ -757,12 +757,16 @@ def grid_capacity(nhwc: torch.Tensor) -> int:
     return N * ((H + 1) // 2) * ((W + 1) // 2)
 
 
-def to_nchw(rows: torch.Tensor, N: int, OH: int, OW: int) -> torch.Tensor:
-    """Pixel rows [N*OH*OW, C] -> logical NCHW [N, C, OH, OW], differentiable."""
+def to_nchw(rows: torch.Tensor, N: int, OH: int, OW: int, channels_last: bool = False) -> torch.Tensor:
+    """Pixel rows [N*OH*OW, C] -> logical NCHW [N, C, OH, OW], differentiable: contiguous (one transpose launch, and one in
+    backward), or with `channels_last` a permuted view of the rows (no launch either way)."""
+    if channels_last:
+        return rows.view(N, OH, OW, rows.shape[1]).permute(0, 3, 1, 2)
     return _ToNCHW.apply(rows.view(N, OH, OW, rows.shape[1]))
 
 
-def res5_grid(stage, nhwc: torch.Tensor, split: bool = True, overflow_check: bool = True, on_overflow=None) -> torch.Tensor:
+def res5_grid(stage, nhwc: torch.Tensor, split: bool = True, overflow_check: bool = True, on_overflow=None,
+              channels_last: bool = False) -> torch.Tensor:
     """roi_emb_heads.py:323 -- the stage applied to the whole channels-last res4 map [N,H,W,Cin] -> logical NCHW
     [N, Cout, ceil(H/2), ceil(W/2)], differentiable in the map and the convolution weights.  Block 0's stride-2 1x1
     convolutions read the even pixels; the 3x3 convolutions run as implicit GEMMs over the (H/2 x W/2) grid."""
@@ -776,7 +780,7 @@ def res5_grid(stage, nhwc: torch.Tensor, split: bool = True, overflow_check: boo
         made["rows"] = grid_segment(step, nhwc)
         return step
     step = _guarded(stage, split, (on_overflow,) if overflow_check else None, nhwc.device, build)
-    return to_nchw(step.outputs([made["rows"]], [False])[0], N, OH, OW)
+    return to_nchw(step.outputs([made["rows"]], [False])[0], N, OH, OW, channels_last=channels_last)
 
 
 def res5_rois(stage, nhwc: torch.Tensor, rois: torch.Tensor, P: int, scale: float, sampling_ratio: int, aligned: bool,

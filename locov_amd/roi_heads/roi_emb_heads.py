@@ -41,8 +41,15 @@ class EmbeddingRes5ROIHeads(SampleAllROIHeads):
     def __init__(self, *, in_features: List[str], pooler: ROIPooler, res5: nn.Module, box_predictor: nn.Module,
                  mask_head: Optional[nn.Module] = None, output_shape: Optional[int] = 0,
                  res5_backend: str = "hip", res5_conv3x3: str = "winograd", res5_dtype: str = "f16x2",
-                 res5_overflow_check: bool = True, res5_train_guard: str = "sync", **kwargs):
+                 res5_overflow_check: bool = True, res5_train_guard: str = "sync", grid_features_layout: str = "nchw", **kwargs):
         super().__init__(**kwargs)
+        assert grid_features_layout in ("nchw", "channels_last"), \
+            f"GRID_FEATURES_LAYOUT must be 'nchw' or 'channels_last', got {grid_features_layout!r}"
+        # extension: memory layout of the LSM variant's visual_grid_features on the hand-written training path.  "nchw" (default):
+        # contiguous NCHW, one transpose of Res5's pixel rows forward and one backward; "channels_last": the same logical
+        # [N, C5, H/2, W/2] tensor as a permuted view of those rows (no transpose either way) -- what mmss_regions.grid_regions gathers
+        # from as contiguous rows
+        self.grid_features_layout = grid_features_layout
         assert res5_backend in ("hip", "miopen") and res5_conv3x3 in ("winograd", "direct") and res5_dtype in ("fp32", "f16x2", "bf16")
         # extension: "f16x2" = fp32 GEMMs formed from split f16 operand pairs on the f16 matrix pipe (fp32-level
         # accuracy, see csrc/gemm_split.hip); "bf16" = reduced-precision GEMM operands (not a parity configuration)
@@ -95,6 +102,7 @@ class EmbeddingRes5ROIHeads(SampleAllROIHeads):
         ret["res5_dtype"] = box_head.get("RES5_DTYPE", "f16x2") if hasattr(box_head, "get") else "f16x2"
         ret["res5_overflow_check"] = bool(box_head.get("RES5_OVERFLOW_CHECK", True)) if hasattr(box_head, "get") else True
         ret["res5_train_guard"] = box_head.get("RES5_TRAIN_GUARD", "sync") if hasattr(box_head, "get") else "sync"
+        ret["grid_features_layout"] = box_head.get("GRID_FEATURES_LAYOUT", "nchw") if hasattr(box_head, "get") else "nchw"
         return ret
 
     @classmethod
@@ -165,7 +173,7 @@ class EmbeddingRes5ROIHeads(SampleAllROIHeads):
         if nhwc is None:
             nhwc = res5_train.to_nhwc(feature)
         return res5_train.res5_grid(self.res5, nhwc, split=self.res5_dtype == "f16x2", overflow_check=self.res5_overflow_check,
-                                    on_overflow=self._warn_overflow)
+                                    on_overflow=self._warn_overflow, channels_last=self.grid_features_layout == "channels_last")
 
     def _shared_roi_transform(self, features: List[torch.Tensor], boxes: List[Boxes], pooled: bool = False,
                               nhwc: Optional[torch.Tensor] = None, rois: Optional[torch.Tensor] = None):
@@ -494,7 +502,8 @@ class EmbeddingProposalsRes5ROIHeads(EmbeddingRes5ROIHeads):
                     box = self._shared_roi_transform(feats, [x.proposal_boxes for x in props], pooled=True, nhwc=nhwc)   # :343-344
             keep = None
             if tguard is not None:
-                keep = self._close_train_guard(tguard, [grid, box])
+                # (GRID_FEATURES_LAYOUT "channels_last": the same memory through its contiguous [N, H, W, C] view)
+                keep = self._close_train_guard(tguard, [grid if grid.is_contiguous() else grid.permute(0, 2, 3, 1), box])
             elif guard is not None and guard.event is None:
                 guard.snapshot()                             # 4 bytes to pinned memory + an event, behind both Res5 calls
             predictions = self.box_predictor(box)                                    # :345
@@ -549,7 +558,7 @@ class EmbeddingProposalsRes5ROIHeads(EmbeddingRes5ROIHeads):
             rows, x0 = res5_train.grid_and_roi_segments(step, nhwc, rois, P, self.pooler.scales[0], self.pooler.sampling_ratio,
                                                         self.pooler.aligned, on_range_final=early)
             grid, box_features = step.outputs([rows, x0], [False, True])
-            return res5_train.to_nchw(grid, N, (H + 1) // 2, (W + 1) // 2), box_features, sampled
+            return self._grid_out(grid, N, (H + 1) // 2, (W + 1) // 2), box_features, sampled
         while True:
             dtype = self.res5_dtype
             step = res5_train.Res5Step(self.res5, dtype == "f16x2", nhwc.device,
@@ -567,7 +576,12 @@ class EmbeddingProposalsRes5ROIHeads(EmbeddingRes5ROIHeads):
         x0 = res5_train.roi_segment(step, nhwc, rois, P, self.pooler.scales[0], self.pooler.sampling_ratio, self.pooler.aligned,
                                     on_range_final=early)
         grid, box_features = step.outputs([rows, x0], [False, True])
-        return res5_train.to_nchw(grid, N, (H + 1) // 2, (W + 1) // 2), box_features, proposals
+        return self._grid_out(grid, N, (H + 1) // 2, (W + 1) // 2), box_features, proposals
+
+    def _grid_out(self, rows: torch.Tensor, N: int, OH: int, OW: int) -> torch.Tensor:
+        """Res5's pixel rows [N*OH*OW, C5] as visual_grid_features [N, C5, OH, OW] in the configured memory layout."""
+        from .. import res5_train
+        return res5_train.to_nchw(rows, N, OH, OW, channels_last=self.grid_features_layout == "channels_last")
 
     def inference_detection(self, features, proposals):
         """roi_emb_heads.py:351-360."""
