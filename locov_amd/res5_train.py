@@ -153,13 +153,13 @@ class Res5Step:
         nb = len(stage)
         for bi, blk in enumerate(stage):
             Y1, Y2, OUT = self.act[bi]
-            s1, b1 = stage._fold(blk.conv1)
-            s2, b2 = stage._fold(blk.conv2)
-            s3, b3 = stage._fold(blk.conv3)
+            s1, b1 = stage.operands.fold(blk.conv1)
+            s2, b2 = stage.operands.fold(blk.conv2)
+            s3, b3 = stage.operands.fold(blk.conv3)
             c2 = blk.conv2
             _linear(x, T.get(blk.conv1, "plain"), b1, scale=s1, relu=True, out=Y1[joint])
             if blk.shortcut is not None:
-                ss, bs = stage._fold(blk.shortcut)
+                ss, bs = stage.operands.fold(blk.shortcut)
                 sc = _linear(x, T.get(blk.shortcut, "plain"), bs, scale=ss)
             else:
                 sc = x
@@ -240,7 +240,7 @@ class Res5Step:
     def _bwd_guarded(self, fn):
         """Run one node's backward.  Split arithmetic: what can leave fp16's range here is not data -- the activations passed the
         forward's guard (the weight-gradient GEMMs and the Winograd transforms see the same tensors at the same scales) and every
-        gradient's operand scale is chosen on the device from its own max |g|.  Only a REMEMBERED weight scale (Res5Stage._split:
+        gradient's operand scale is chosen on the device from its own max |g|.  Only a REMEMBERED weight scale (Res5Operands:
         chosen again every 64 steps, 8x headroom) that stopped covering a weight could trip the guard -- the pack kernel raises
         it.  That is recorded in the stage's "bwd" guard and nothing is read inside autograd (a host read here would stall DDP's
         overlapped all-reduce).  Instead every node ends with a GradScaler-style skip decided ON THE DEVICE: when the word is set
@@ -285,7 +285,7 @@ class Res5Step:
             for seg in live:
                 want.append((c2, "uflip" if _wino_ok(seg.H, seg.W, c2.out_channels, c2.in_channels) and not _NO_WINO_BWD else "flip9"))
             for conv, tag in want:
-                if (id(conv), tag) not in T.ready:
+                if (conv, tag) not in T.ready:
                     T.get(conv, tag)
 
 
@@ -465,7 +465,7 @@ class Res5BlockFn(torch.autograd.Function):
         g, sg = Res5BlockFn._take_carry(step, g, "tail")
         sp, T, slot, wgrad_1x1, dgrad_1x1 = Res5BlockFn._helpers(ctx)
         y1, y2, _ = ctx.saved_tensors
-        s2, s3 = stage._fold(blk.conv2)[0], stage._fold(blk.conv3)[0]
+        s2, s3 = stage.operands.fold(blk.conv2)[0], stage.operands.fold(blk.conv3)[0]
         c2 = blk.conv2
         # conv3: dW3 = s3 * g^T y2 ; g2 = (g . s3 W3) [y2 > 0]         -- all segments, one launch each
         if need_w[1]:
@@ -565,12 +565,12 @@ class Res5BlockFn(torch.autograd.Function):
         g1, sg1, g, sg = Res5BlockFn._take_carry(step, g1, "head")
         sp, T, slot, wgrad_1x1, dgrad_1x1 = Res5BlockFn._helpers(ctx)
         x, _ = ctx.saved_tensors
-        s1 = stage._fold(blk.conv1)[0]
+        s1 = stage.operands.fold(blk.conv1)[0]
         # conv1 (+ shortcut): dW1 = s1 * g1^T x ; gx = (g1 . s1 W1 + shortcut path) [x > 0]
         if need_w[0]:
             gw[0] = wgrad_1x1(g1, sg1, x, s1).view_as(blk.conv1.weight)
         if has_sc:
-            ss = stage._fold(blk.shortcut)[0]
+            ss = stage.operands.fold(blk.shortcut)[0]
             if need_w[1]:
                 gw[1] = wgrad_1x1(g, sg, x, ss).view_as(blk.shortcut.weight)
         if not need_x:

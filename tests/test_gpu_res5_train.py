@@ -399,8 +399,8 @@ def test_a_stale_backward_weight_scale_never_reaches_the_parameters(pkg, oracle,
     on the device (locov_zero_if_raised), the word stays set for the next host read, and the step after that (scales chosen
     afresh) is correct again.  Operands from the step's ONE preparation launch (every other step): that launch runs under the
     FORWARD's guard, whose reader repeats the step on the f32 MFMA -- correct gradients at once -- and drops the scales."""
-    from locov_amd import res5 as res5_mod, res5_train
-    monkeypatch.setattr(res5_mod, "_ONE_LAUNCH_PREP", one_launch)
+    from locov_amd import res5_operands, res5_train
+    monkeypatch.setattr(res5_operands, "_ONE_LAUNCH_PREP", one_launch)
     R, (in_ch, mid, out_ch) = 21, (128, 64, 256)
     res5, params = _stage(pkg, oracle, in_ch, mid, out_ch, seed=5)
     gen = torch.Generator().manual_seed(23)
@@ -423,9 +423,9 @@ def test_a_stale_backward_weight_scale_never_reaches_the_parameters(pkg, oracle,
         for k in keys:
             named[k].add_(0.0)
     poisoned = 0
-    for key, (scale, _) in list(res5._scales.items()):
-        if isinstance(key[1], str):                              # (id(conv), "t" / "uflip" / "flip9"): the backward's operands
-            res5._scales[key] = (scale * 2.0 ** 14, 0)
+    for key, (scale, _) in list(res5.operands.scales.items()):
+        if key[1] in ("t", "uflip", "flip9"):                    # (conv, "t" / "uflip" / "flip9"): the backward's operands
+            res5.operands.scales[key] = (scale * 2.0 ** 14, 0)
             poisoned += 1
     assert poisoned >= 9
     gx, gw = step()
@@ -433,7 +433,7 @@ def test_a_stale_backward_weight_scale_never_reaches_the_parameters(pkg, oracle,
         # the f32 MFMA's results: two fp32 evaluations of one step (a ReLU tie may flip between them, see _float64_stage)
         rel_l2 = lambda a, b: float((a.double() - b.double()).norm() / b.double().norm().clamp_min(1e-30))
         assert rel_l2(gx, gx_ref) < 5e-3 and all(rel_l2(gw[k], gw_ref[k]) < 5e-3 for k in keys)
-        assert not res5.backward_guard_raised(x0.device) and not res5._scales
+        assert not res5.backward_guard_raised(x0.device) and not res5.operands.scales
         gx2, gw2 = step()
         assert torch.equal(gx2, gx_ref) and all(torch.equal(gw2[k], gw_ref[k]) for k in keys)
         return
@@ -851,16 +851,16 @@ def test_changing_map_sizes_in_one_process_match_the_stock_library_path(pkg, ora
 
 def test_operand_scales_are_refreshed_without_a_host_wait(pkg, oracle, monkeypatch):
     """Every REFRESH steps the remembered operand scales are chosen again from max |w| / max |s| sent to pinned memory behind an event
-    (TrainOperands._start_refresh / _adopt_refresh): the one-launch preparation is never left (the synchronous form sends every
+    (Res5Operands._start_refresh / _count_step): the one-launch preparation is never left (the synchronous form sends every
     REFRESH-th step to the host-read chain), the new scales cover their operands with the chain's headroom or one power of two
     less, and the training run stays what it is with scales that are never refreshed."""
-    from locov_amd import res5 as res5_mod
+    from locov_amd.res5_operands import Res5Operands
     ops = pkg.ops
     w = torch.randn(64, 32, 3, 3, generator=torch.Generator().manual_seed(1)).cuda()
-    assert float(ops.winograd_pack_weight(w).abs().max()) <= res5_mod.TrainOperands.WINO_GAIN * float(w.abs().max())
+    assert float(ops.winograd_pack_weight(w).abs().max()) <= Res5Operands.WINO_GAIN * float(w.abs().max())
     runs = {}
     for refresh in (2, 10 ** 9):
-        monkeypatch.setattr(res5_mod.TrainOperands, "REFRESH", refresh)
+        monkeypatch.setattr(Res5Operands, "REFRESH", refresh)
         heads, c_in = _train_heads(pkg, oracle, "hip", "f16x2")
         opt = torch.optim.SGD([p for p in heads.parameters() if p.requires_grad], lr=1e-3)
         feat = torch.randn(2, c_in, 50, 84, generator=torch.Generator().manual_seed(5)).cuda().requires_grad_(True)
@@ -869,10 +869,10 @@ def test_operand_scales_are_refreshed_without_a_host_wait(pkg, oracle, monkeypat
         for it in range(12):
             opt.zero_grad(set_to_none=True)
             torch.manual_seed(77 + it)
-            before = dict(heads.res5._scales)
+            before = dict(heads.res5.operands.scales)
             grid, box_feats, sampled, ls = heads(None, {"res4": feat}, props, targets)
-            ready.append(len(heads.res5.__dict__["_train_ops"][1].ready))
-            adopted += any(v[1] < before.get(k, (0, -1))[1] for k, v in heads.res5._scales.items())
+            ready.append(len(heads.res5.operands.latest.ready))
+            adopted += any(v[1] < before.get(k, (0, -1))[1] for k, v in heads.res5.operands.scales.items())
             loss = ls["loss_box_reg"] + ls["loss_cls"] + 1e-3 * grid.square().mean() + 1e-2 * torch.cat(box_feats).square().mean()
             loss.backward()
             losses.append(float(loss.detach()))
@@ -882,7 +882,7 @@ def test_operand_scales_are_refreshed_without_a_host_wait(pkg, oracle, monkeypat
         stage = heads.res5
         for blk in stage:
             for conv in (blk.conv1, blk.conv3):
-                rec = stage._scales[(id(conv), False)]
+                rec = stage.operands.scales[(conv, "plain")]
                 top = rec[0] * float(conv.weight.abs().max())
                 assert 2.0 ** 9 <= top < 2.0 ** 13, top
     assert runs[2][1] == [0] + [26] * 11 and runs[10 ** 9][1] == [0] + [26] * 11
@@ -895,10 +895,10 @@ def test_one_launch_operands_with_a_frozen_backbone(pkg, oracle):
     """A res4 map that needs no gradient (frozen backbone): block 0's data-gradient operands are never asked for, so the on-demand
     chain never learns their scales -- the one-launch preparation must still take over from the second step (it learns the
     missing scales itself), and the steps' losses and Res5 weight gradients equal those of the on-demand chain bit for bit."""
-    from locov_amd import res5 as res5_mod
+    from locov_amd import res5_operands
     runs = {}
     for one_launch in (False, True):
-        was, res5_mod._ONE_LAUNCH_PREP = res5_mod._ONE_LAUNCH_PREP, one_launch
+        was, res5_operands._ONE_LAUNCH_PREP = res5_operands._ONE_LAUNCH_PREP, one_launch
         try:
             heads, c_in = _train_heads(pkg, oracle, "hip", "f16x2")
             opt = torch.optim.SGD([p for p in heads.parameters() if p.requires_grad], lr=1e-3)
@@ -909,7 +909,7 @@ def test_one_launch_operands_with_a_frozen_backbone(pkg, oracle):
                 opt.zero_grad(set_to_none=True)
                 torch.manual_seed(77 + it)
                 grid, box_feats, sampled, losses = heads(None, {"res4": feat}, props, targets)
-                ready.append(len(heads.res5.__dict__["_train_ops"][1].ready))
+                ready.append(len(heads.res5.operands.latest.ready))
                 loss = losses["loss_box_reg"] + losses["loss_cls"] + 1e-3 * grid.square().mean() + 1e-2 * torch.cat(box_feats).square().mean()
                 loss.backward()
                 seen.append((float(loss.detach()), {k: p.grad.clone() for k, p in heads.named_parameters()
@@ -917,7 +917,7 @@ def test_one_launch_operands_with_a_frozen_backbone(pkg, oracle):
                 opt.step()
             torch.cuda.synchronize()
         finally:
-            res5_mod._ONE_LAUNCH_PREP = was
+            res5_operands._ONE_LAUNCH_PREP = was
         runs[one_launch] = (seen, ready)
     assert runs[False][1] == [0, 0, 0] and runs[True][1] == [0, 26, 26]
     for (la, ga), (lb, gb) in zip(runs[False][0], runs[True][0]):

@@ -589,7 +589,7 @@ def test_size_regime_past_32_bit_offsets(pkg, oracle, monkeypatch):
     assert np.abs(scores[:R].cpu().numpy() - want_scores).max() <= 1e-4
     # the 128x128 kernels on the same 4.8 GB operands
     monkeypatch.setenv("LOCOV_SPLIT_BIG", "0")
-    heads.res5.__dict__.pop("_warned", None)
+    heads.res5._warned.clear()
     with pytest.warns(RuntimeWarning, match="NOT fused"):
         bf128, scores128 = run(0, n_img)
     with warnings.catch_warnings():

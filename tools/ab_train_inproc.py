@@ -9,7 +9,7 @@ import gc
 import numpy as np
 import torch
 import bench
-from locov_amd import res5 as res5_mod
+from locov_amd import res5_operands
 
 rounds = 6
 argv = sys.argv[1:]
@@ -27,7 +27,7 @@ variants = {"sync,prep": ("sync", True), "deferred,prep": ("deferred", True), "s
 def use(name):
     guard, prep = variants[name]
     heads.res5_train_guard = guard
-    res5_mod._ONE_LAUNCH_PREP = prep
+    res5_operands._ONE_LAUNCH_PREP = prep
 
 
 times = {k: [] for k in variants}

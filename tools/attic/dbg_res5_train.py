@@ -36,7 +36,7 @@ g = ops.spatial_mean_bwd(gy.cuda(), o2, 49)
 g_ref = torch.where(ref_out > 0, (gy.double() / 49).repeat_interleave(49, 0), torch.zeros_like(ref_out))
 print("g err", T.rel_err(g, g_ref))
 blk = res5[2]
-w3, s3, _ = res5._packed(blk.conv3)
+s3, _ = res5.operands.fold(blk.conv3)
 dw3 = ops.gemm_tn(g, y2, s3)
 dw3_same = (g.double().t() @ y2.double()) * s3.double()[:, None]
 print("gemm_tn vs float64 on the same operands", T.rel_err(dw3, dw3_same))
