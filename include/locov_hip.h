@@ -33,7 +33,8 @@ extern "C" {
 #endif
 
 /* 8: locov_detect_postprocess; later, additively: locov_grounding_ce_dist_fwd / _bwd, locov_distill_loss_fwd / _bwd,
- *    locov_detect_postprocess_wide (+ _workspace_bytes), locov_regions_select / _gather_fwd / _gather_bwd */
+ *    locov_detect_postprocess_wide (+ _workspace_bytes), locov_regions_select / _gather_fwd / _gather_bwd,
+ *    locov_detect_postprocess_cs / _wide_cs (+ _workspace_bytes) */
 #define LOCOV_ABI_VERSION 8
 
 #define LOCOV_OK 0
@@ -539,6 +540,45 @@ int locov_detect_postprocess_wide(const float *probs, int64_t ld_probs, int num_
                                   float scale_clamp, float score_thresh, float nms_thresh, int topk, int per_class_above, void *workspace,
                                   int64_t workspace_bytes, float *out_boxes, float *out_scores, int64_t *out_classes, int64_t *out_rows,
                                   int *counts_and_flags, locov_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
+ * a-10c the two post-processing pipelines with CLASS-SPECIFIC box regression ([D2-upstream] MODEL.ROI_BOX_HEAD.CLS_AGNOSTIC_BBOX_REG
+ * False, Detectron2's default; the plain FastRCNNOutputLayers that build_box_predictor accepts, ovr/modeling/roi_heads/
+ * box_emb_head.py:239-249).  Replaces the same call site: ovr/modeling/roi_heads/roi_emb_heads.py:280,357 -> fast_rcnn_inference on
+ * boxes [R, 4K].  Arguments as locov_detect_postprocess / locov_detect_postprocess_wide, plus
+ *   deltas [R, ld_deltas] fp32, 16-byte aligned, ld_deltas a multiple of 4 and >= 4 x box_classes;
+ *   box_classes: 1 = class-agnostic (bit for bit the result of the entry point without _cs) or num_classes: candidate (r, c) has the
+ *   box apply_deltas(deltas[r, 4c : 4c + 4], proposal r) clipped to its image.  Any other value: LOCOV_ERR_INVALID_ARG.
+ * With box_classes = num_classes: batched_nms's shift unit is the maximum coordinate over the candidates' OWN boxes + 1; the shifted
+ * branch takes the IoU on each candidate's own shifted box, the per-class branch on the candidates' own unshifted boxes (a wave per
+ * (image, class) segment tests the pairs inside its greedy sweep: no row x row matrix); out_boxes holds the candidate's own box;
+ * NONFINITE is raised when ANY of the R x K decoded boxes is inf / NaN before clipping, a candidate's or not (the chain tests the
+ * whole [R, 4K] tensor), or any of the K + 1 probabilities of a row.  Orders, outputs, OVERFLOW and the limits are unchanged;
+ * R x K < 2^31 holds for both pipelines.
+ *   workspaces, from host data only; 0 for empty input, < 0 on an argument error.  With B = box_classes:
+ *     locov_detect_postprocess_cs_workspace_bytes(R, n_images, num_classes, ld_deltas, box_classes)
+ *         = align16(R (16 B + 8) + 4 ceil4(n_images)) + 4 522 000 n_images + 64
+ *       (decoded boxes [R, B], row counts and offsets, candidates per image; per image the 8 192-slot lists and overlap bit sets);
+ *     locov_detect_postprocess_wide_cs_workspace_bytes(row_offsets, n_images, num_classes, per_class_above, ld_deltas, box_classes)
+ *         = 16 R B + 16 n K + 180 352 n + 8 (M + sum_i cap_i W_i + R K),   M = sum_i R_i W_i for B = 1, 0 for B = K > 1
+ *       (W_i, cap_i, n as for locov_detect_postprocess_wide_workspace_bytes).
+ * ------------------------------------------------------------------------------------- */
+int64_t locov_detect_postprocess_cs_workspace_bytes(int64_t R, int n_images, int num_classes, int64_t ld_deltas, int box_classes);
+
+int locov_detect_postprocess_cs(const float *probs, int64_t ld_probs, int num_classes, const float *deltas, int64_t ld_deltas, int box_classes,
+                                const float *proposal_boxes, const int *row_offsets, const float *image_hw, int n_images, float wx, float wy,
+                                float ww, float wh, float scale_clamp, float score_thresh, float nms_thresh, int topk, void *workspace,
+                                int64_t workspace_bytes, float *out_boxes, float *out_scores, int64_t *out_classes, int64_t *out_rows,
+                                int *counts_and_flags, locov_stream_t stream);
+
+int64_t locov_detect_postprocess_wide_cs_workspace_bytes(const int *row_offsets, int n_images, int num_classes, int per_class_above,
+                                                         int64_t ld_deltas, int box_classes);
+
+int locov_detect_postprocess_wide_cs(const float *probs, int64_t ld_probs, int num_classes, const float *deltas, int64_t ld_deltas,
+                                     int box_classes, const float *proposal_boxes, const int *row_offsets, const float *image_hw, int n_images,
+                                     float wx, float wy, float ww, float wh, float scale_clamp, float score_thresh, float nms_thresh, int topk,
+                                     int per_class_above, void *workspace, int64_t workspace_bytes, float *out_boxes, float *out_scores,
+                                     int64_t *out_classes, int64_t *out_rows, int *counts_and_flags, locov_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * a-12  LSM grounding: word<->region alignment -> [caption, image] cost matrices.

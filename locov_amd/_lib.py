@@ -106,6 +106,13 @@ SIGNATURES = {
     "locov_detect_postprocess_wide_workspace_bytes": (c_int64, [POINTER(c_int), c_int, c_int, c_int]),
     "locov_detect_postprocess_wide": (c_int, [_p, c_int64, c_int, _p, _p, POINTER(c_int), POINTER(c_float), c_int, c_float, c_float, c_float,
                                               c_float, c_float, c_float, c_float, c_int, c_int, _p, c_int64, _p, _p, _p, _p, _p, _p]),
+    "locov_detect_postprocess_cs_workspace_bytes": (c_int64, [c_int64, c_int, c_int, c_int64, c_int]),
+    "locov_detect_postprocess_cs": (c_int, [_p, c_int64, c_int, _p, c_int64, c_int, _p, POINTER(c_int), POINTER(c_float), c_int, c_float, c_float,
+                                            c_float, c_float, c_float, c_float, c_float, c_int, _p, c_int64, _p, _p, _p, _p, _p, _p]),
+    "locov_detect_postprocess_wide_cs_workspace_bytes": (c_int64, [POINTER(c_int), c_int, c_int, c_int, c_int64, c_int]),
+    "locov_detect_postprocess_wide_cs": (c_int, [_p, c_int64, c_int, _p, c_int64, c_int, _p, POINTER(c_int), POINTER(c_float), c_int, c_float,
+                                                 c_float, c_float, c_float, c_float, c_float, c_float, c_int, c_int, _p, c_int64, _p, _p, _p,
+                                                 _p, _p, _p]),
     "locov_grounding_fwd": (c_int, [_p, c_int, c_int, c_int, _p, _p, c_float, _p, _p, _p]),
     "locov_grounding_bwd": (c_int, [_p, c_int, c_int, c_int, _p, _p, c_float, _p, _p, _p, _p]),
     "locov_token_attention_fwd": (c_int, [_p, c_int64, c_int, _p, _p, c_int, c_int, c_float, c_int, c_int, _p, _p, _p, _p]),

@@ -21,6 +21,10 @@
 //   det_nms_topk_kernel      a workgroup per image: the greedy sweep as a fix-point over kept / undecided bit sets; second sort of
 //                            the survivors by (descending score, row, class) = the reference's order; top-k out.
 //
+// Class-specific regression (locov_detect_postprocess_cs, box_classes = K: deltas [R, 4K]) decodes a box per (proposal, class)
+// (det_decode_clip_cs_kernel) and has the sort / top-k kernels read candidate (row, class)'s own box: boxes[row * bk + class * cs] with
+// (bk, cs) = (K, 1), where the class-agnostic call has (1, 0).  Nothing else differs.
+//
 // Candidate order, tie-breaking and every fp32 operation equal the torch chain's (tests/test_gpu_postprocess.py: bit-identical
 // detections).  What the kernels cannot take is flagged on the device and read by the caller with the counts (its ONE host
 // read): non-finite boxes / scores (the reference drops such proposals with a warning) and an image with more candidates than
@@ -130,8 +134,9 @@ struct DetLists {                       // per-image work lists in the workspace
     unsigned long long *ov;             // [n_img][kDetOvWords]        bit j of word w of candidate i: candidate cstart + 64 w + j overlaps it
 };
 
+// boxes [R, bk]: candidate (row, class) has box  row * bk + class * cs  of its image -- (bk, cs) = (1, 0) class-agnostic, (K, 1) class-specific
 __global__ __launch_bounds__(kDetThreads) void det_sort_kernel(DetLists L, const int *__restrict__ img_count, const float4 *__restrict__ boxes,
-                                                               DetGeom g, int *__restrict__ flags)
+                                                               DetGeom g, int bk, int cs, int *__restrict__ flags)
 {
     extern __shared__ unsigned long long key[];                  // P keys
     __shared__ float red[kDetThreads / 64];
@@ -150,11 +155,11 @@ __global__ __launch_bounds__(kDetThreads) void det_sort_kernel(DetLists L, const
     __syncthreads();
     det_bitonic_sort<kDetThreads>(key, P, tid);                               // class-major; inside a class: descending score, ties by row
     constexpr unsigned long long kRowMask = (1ull << kRowBits) - 1ull;
-    const float4 *gbox = boxes + g.roff[img];
+    const float4 *gbox = boxes + (int64_t)g.roff[img] * bk;
     // batched_nms's coordinate offset: class * (max coordinate of the image's candidate boxes + 1)
     float m = -__builtin_inff();
     for (int i = tid; i < n; i += kDetThreads) {
-        const float4 b = gbox[(int)(key[i] & kRowMask)];
+        const float4 b = gbox[(int)(key[i] & kRowMask) * bk + (int)(key[i] >> (kRowBits + kScoreBits)) * cs];
         m = fmaxf(m, fmaxf(fmaxf(b.x, b.y), fmaxf(b.z, b.w)));
     }
 #pragma unroll
@@ -184,7 +189,7 @@ __global__ __launch_bounds__(kDetThreads) void det_sort_kernel(DetLists L, const
                 if (key[mid] < first_of_class) lo = mid + 1;
                 else hi = mid;
             }
-            float4 b = gbox[(int)(k & kRowMask)];
+            float4 b = gbox[(int)(k & kRowMask) * bk + cls * cs];
             const float off = (float)cls * shift_unit;
             b.x += off;
             b.y += off;
@@ -244,7 +249,7 @@ __device__ __forceinline__ unsigned long long det_window64(const unsigned *bits,
 }
 
 __global__ __launch_bounds__(kDetThreads) void det_nms_topk_kernel(DetLists L, const int *__restrict__ img_count, const float4 *__restrict__ boxes,
-                                                                   DetGeom g, int topk, float4 *__restrict__ out_boxes, float *__restrict__ out_scores,
+                                                                   DetGeom g, int bk, int cs, int topk, float4 *__restrict__ out_boxes, float *__restrict__ out_scores,
                                                                    int64_t *__restrict__ out_classes, int64_t *__restrict__ out_rows,
                                                                    int *__restrict__ counts)
 {
@@ -321,13 +326,13 @@ __global__ __launch_bounds__(kDetThreads) void det_nms_topk_kernel(DetLists L, c
     det_bitonic_sort<kDetThreads>(key, P, tid);
     const int n_keep = n_keep_s;
     const int count = n_keep < topk ? n_keep : topk;
-    const float4 *gbox = boxes + g.roff[img];
+    const float4 *gbox = boxes + (int64_t)g.roff[img] * bk;
     for (int j = tid; j < count; j += kDetThreads) {
         const unsigned long long k = key[j];
         const int cls = (int)(k & ((1ull << kClsBits) - 1ull)), row = (int)((k >> kClsBits) & kRowMask);
         const unsigned nscore = (unsigned)(k >> (kRowBits + kClsBits));
         const int64_t slot = (int64_t)img * topk + j;
-        out_boxes[slot] = gbox[row];
+        out_boxes[slot] = gbox[row * bk + cls * cs];
         out_scores[slot] = __uint_as_float(~nscore);
         out_classes[slot] = cls;
         out_rows[slot] = row;
@@ -339,63 +344,73 @@ __global__ __launch_bounds__(kDetThreads) void det_nms_topk_kernel(DetLists L, c
 
 using namespace locov;
 
-extern "C" {
-
 static int64_t det_align16(int64_t v) { return (v + 15) & ~(int64_t)15; }
 
-int64_t locov_detect_postprocess_workspace_bytes(int64_t R, int n_images)
+// box_classes boxes per proposal (1, or num_classes for class-specific regression) in rows of ld_deltas floats
+static int det_check_box_classes(int num_classes, int64_t ld_deltas, int box_classes, const char *who)
+{
+    LOCOV_REQUIRE(box_classes == 1 || box_classes == num_classes, "%s: box_classes must be 1 or num_classes (%d), got %d", who, num_classes,
+                  box_classes);
+    LOCOV_REQUIRE(ld_deltas >= 4 * (int64_t)box_classes && ld_deltas % 4 == 0,
+                  "%s: ld_deltas must cover the 4 x box_classes columns and be a multiple of 4", who);
+    return LOCOV_OK;
+}
+
+static int64_t det_workspace_bytes(int64_t R, int n_images, int box_classes)
 {
     if (R <= 0 || n_images <= 0) return 0;
-    // clipped boxes [R, 4] fp32, row counts [R], row offsets [R], candidates per image [n_images]; then per image: keys, class starts,
-    // overlap-word offsets, shifted boxes (kDetMaxCand each) and the overlap bit sets (kDetOvWords 64-bit words: 4.3 MB)
-    const int64_t head = det_align16(R * 24 + (int64_t)((n_images + 3) & ~3) * 4);
+    // clipped boxes [R, box_classes, 4] fp32, row counts [R], row offsets [R], candidates per image [n_images]; then per image: keys,
+    // class starts, overlap-word offsets, shifted boxes (kDetMaxCand each) and the overlap bit sets (kDetOvWords 64-bit words: 4.3 MB)
+    const int64_t head = det_align16(R * (16 * (int64_t)box_classes + 8) + (int64_t)((n_images + 3) & ~3) * 4);
     const int64_t per_image = (int64_t)kDetMaxCand * (8 + 4 + 16) + (int64_t)(kDetMaxCand + 4) * 4 + (int64_t)kDetOvWords * 8;
     return head + (int64_t)n_images * per_image + 64;
 }
 
-int locov_detect_postprocess(const float *probs, int64_t ld_probs, int num_classes, const float *deltas, const float *proposal_boxes,
-                             const int *row_offsets, const float *image_hw, int n_images, float wx, float wy, float ww, float wh,
-                             float scale_clamp, float score_thresh, float nms_thresh, int topk, void *workspace, int64_t workspace_bytes,
-                             float *out_boxes, float *out_scores, int64_t *out_classes, int64_t *out_rows, int *counts_and_flags,
-                             locov_stream_t stream)
+static int det_run(const char *who, const float *probs, int64_t ld_probs, int num_classes, const float *deltas, int64_t ld_deltas,
+                   int box_classes, const float *proposal_boxes, const int *row_offsets, const float *image_hw, int n_images, float wx,
+                   float wy, float ww, float wh, float scale_clamp, float score_thresh, float nms_thresh, int topk, void *workspace,
+                   int64_t workspace_bytes, float *out_boxes, float *out_scores, int64_t *out_classes, int64_t *out_rows,
+                   int *counts_and_flags, locov_stream_t stream)
 {
-    LOCOV_REQUIRE(n_images >= 0 && n_images <= LOCOV_LABEL_MAX_IMAGES, "locov_detect_postprocess: 0..%d images per call", LOCOV_LABEL_MAX_IMAGES);
+    LOCOV_REQUIRE(n_images >= 0 && n_images <= LOCOV_LABEL_MAX_IMAGES, "%s: 0..%d images per call", who, LOCOV_LABEL_MAX_IMAGES);
     if (n_images == 0) return LOCOV_OK;
-    LOCOV_REQUIRE(row_offsets && image_hw, "locov_detect_postprocess: null host array");
-    LOCOV_REQUIRE(num_classes >= 1 && num_classes < (1 << kClsBits), "locov_detect_postprocess: 1..%d classes", (1 << kClsBits) - 1);
-    LOCOV_REQUIRE(topk >= 1 && topk <= kDetMaxCand, "locov_detect_postprocess: 1 <= topk <= %d", kDetMaxCand);
-    LOCOV_REQUIRE(ld_probs >= (int64_t)num_classes + 1, "locov_detect_postprocess: ld_probs must cover the K + 1 columns");
-    LOCOV_REQUIRE(wx != 0.f && wy != 0.f && ww != 0.f && wh != 0.f, "locov_detect_postprocess: zero box weight");
+    LOCOV_REQUIRE(row_offsets && image_hw, "%s: null host array", who);
+    LOCOV_REQUIRE(num_classes >= 1 && num_classes < (1 << kClsBits), "%s: 1..%d classes", who, (1 << kClsBits) - 1);
+    if (int rc = det_check_box_classes(num_classes, ld_deltas, box_classes, who)) return rc;
+    LOCOV_REQUIRE(topk >= 1 && topk <= kDetMaxCand, "%s: 1 <= topk <= %d", who, kDetMaxCand);
+    LOCOV_REQUIRE(ld_probs >= (int64_t)num_classes + 1, "%s: ld_probs must cover the K + 1 columns", who);
+    LOCOV_REQUIRE(wx != 0.f && wy != 0.f && ww != 0.f && wh != 0.f, "%s: zero box weight", who);
     DetGeom g{};
     g.n_img = n_images;
     for (int i = 0; i <= n_images; i++) {
         g.roff[i] = row_offsets[i];
-        LOCOV_REQUIRE(g.roff[i] >= 0 && (i == 0 || g.roff[i] >= g.roff[i - 1]), "locov_detect_postprocess: offsets must be non-decreasing");
-        LOCOV_REQUIRE(i == 0 || g.roff[i] - g.roff[i - 1] < (1 << kRowBits), "locov_detect_postprocess: at most %d proposals per image",
-                      (1 << kRowBits) - 1);
+        LOCOV_REQUIRE(g.roff[i] >= 0 && (i == 0 || g.roff[i] >= g.roff[i - 1]), "%s: offsets must be non-decreasing", who);
+        LOCOV_REQUIRE(i == 0 || g.roff[i] - g.roff[i - 1] < (1 << kRowBits), "%s: at most %d proposals per image", who, (1 << kRowBits) - 1);
     }
-    LOCOV_REQUIRE(g.roff[0] == 0, "locov_detect_postprocess: offsets start at 0");
+    LOCOV_REQUIRE(g.roff[0] == 0, "%s: offsets start at 0", who);
     for (int i = 0; i < n_images; i++) {
         g.h[i] = image_hw[2 * i];
         g.w[i] = image_hw[2 * i + 1];
     }
     const int64_t R = g.roff[n_images];
-    LOCOV_REQUIRE(counts_and_flags, "locov_detect_postprocess: null pointer");
+    const int bk = box_classes, cs = box_classes > 1 ? 1 : 0;
+    LOCOV_REQUIRE(R * bk <= 0x7fffffff, "%s: rows x box_classes must stay below 2^31", who);
+    LOCOV_REQUIRE(counts_and_flags, "%s: null pointer", who);
     LOCOV_REQUIRE(R == 0 || (probs && deltas && proposal_boxes && workspace && out_boxes && out_scores && out_classes && out_rows),
-                  "locov_detect_postprocess: null pointer");
-    LOCOV_REQUIRE(R == 0 || workspace_bytes >= locov_detect_postprocess_workspace_bytes(R, n_images), "locov_detect_postprocess: workspace too small");
+                  "%s: null pointer", who);
+    LOCOV_REQUIRE(R == 0 || workspace_bytes >= det_workspace_bytes(R, n_images, bk), "%s: workspace too small", who);
     LOCOV_REQUIRE(((uintptr_t)deltas | (uintptr_t)proposal_boxes | (uintptr_t)workspace | (uintptr_t)out_boxes) % 16 == 0,
-                  "locov_detect_postprocess: boxes / workspace must be 16-byte aligned");
+                  "%s: boxes / workspace must be 16-byte aligned", who);
     hipStream_t s = as_stream(stream);
     hipError_t e = hipMemsetAsync(counts_and_flags, 0, sizeof(int) * (size_t)(n_images + 1), s);
-    if (e != hipSuccess) return set_error(LOCOV_ERR_LAUNCH, "locov_detect_postprocess: memset: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return set_error(LOCOV_ERR_LAUNCH, "%s: memset: %s", who, hipGetErrorString(e));
     if (R == 0) return LOCOV_OK;
     char *ws = static_cast<char *>(workspace);
     float4 *boxes = reinterpret_cast<float4 *>(ws);
-    int *row_count = reinterpret_cast<int *>(ws + R * 16);
+    int *row_count = reinterpret_cast<int *>(ws + R * bk * 16);
     int *row_off = row_count + R;
     int *img_count = row_off + R;
-    char *lists = ws + det_align16(R * 24 + (int64_t)((n_images + 3) & ~3) * 4);
+    char *lists = ws + det_align16(R * (16 * (int64_t)bk + 8) + (int64_t)((n_images + 3) & ~3) * 4);
     DetLists L;
     L.keys = reinterpret_cast<unsigned long long *>(lists);
     L.cbox = reinterpret_cast<float4 *>(lists + (int64_t)n_images * kDetMaxCand * 8);
@@ -406,8 +421,13 @@ int locov_detect_postprocess(const float *probs, int64_t ld_probs, int num_class
     int *flags = counts_and_flags + n_images;
     // (torch divides a tensor by a python scalar by multiplying with the reciprocal formed in fp32)
     const float inv_wx = 1.0f / wx, inv_wy = 1.0f / wy, inv_ww = 1.0f / ww, inv_wh = 1.0f / wh;
-    hipLaunchKernelGGL(det_decode_clip_kernel, dim3((unsigned)ceil_div(R, 256)), dim3(256), 0, s, reinterpret_cast<const float4 *>(deltas),
-                       reinterpret_cast<const float4 *>(proposal_boxes), (int)R, g, inv_wx, inv_wy, inv_ww, inv_wh, scale_clamp, boxes, flags);
+    if (bk == 1 && ld_deltas == 4)
+        hipLaunchKernelGGL(det_decode_clip_kernel, dim3((unsigned)ceil_div(R, 256)), dim3(256), 0, s, reinterpret_cast<const float4 *>(deltas),
+                           reinterpret_cast<const float4 *>(proposal_boxes), (int)R, g, inv_wx, inv_wy, inv_ww, inv_wh, scale_clamp, boxes, flags);
+    else
+        hipLaunchKernelGGL(det_decode_clip_cs_kernel, dim3((unsigned)ceil_div(R * bk, 256)), dim3(256), 0, s, deltas, ld_deltas,
+                           reinterpret_cast<const float4 *>(proposal_boxes), (int)R, bk, g, inv_wx, inv_wy, inv_ww, inv_wh, scale_clamp, boxes,
+                           flags);
     hipLaunchKernelGGL(det_count_kernel, dim3((unsigned)ceil_div(R, 4)), dim3(256), 0, s, probs, ld_probs, num_classes, (int)R, score_thresh,
                        row_count, flags);
     hipLaunchKernelGGL(det_scan_kernel, dim3(1), dim3(kDetThreads), 0, s, row_count, g, row_off, img_count);
@@ -417,23 +437,58 @@ int locov_detect_postprocess(const float *probs, int64_t ld_probs, int num_class
     const size_t lds = (size_t)kDetMaxCand * 8;
     static int attr_state[64] = {};
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return set_error(LOCOV_ERR_LAUNCH, "locov_detect_postprocess: hipGetDevice");
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return set_error(LOCOV_ERR_LAUNCH, "%s: hipGetDevice", who);
     if (attr_state[dev] == 0)
         attr_state[dev] = (hipFuncSetAttribute(reinterpret_cast<const void *>(det_sort_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                                (int)lds) == hipSuccess &&
                            hipFuncSetAttribute(reinterpret_cast<const void *>(det_nms_topk_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                                (int)lds) == hipSuccess) ? 1 : -1;
-    if (attr_state[dev] != 1) return set_error(LOCOV_ERR_LAUNCH, "locov_detect_postprocess: cannot raise the dynamic LDS limit to %zu bytes", lds);
-    hipLaunchKernelGGL(det_sort_kernel, dim3((unsigned)n_images), dim3(kDetThreads), lds, s, L, img_count, boxes, g, flags);
+    if (attr_state[dev] != 1) return set_error(LOCOV_ERR_LAUNCH, "%s: cannot raise the dynamic LDS limit to %zu bytes", who, lds);
+    hipLaunchKernelGGL(det_sort_kernel, dim3((unsigned)n_images), dim3(kDetThreads), lds, s, L, img_count, boxes, g, bk, cs, flags);
     // (a class holds at most one candidate per proposal: its predecessors fit ceil(rows of the largest image / 64) words)
     int max_rows = 0;
     for (int i = 0; i < n_images; i++) max_rows = g.roff[i + 1] - g.roff[i] > max_rows ? g.roff[i + 1] - g.roff[i] : max_rows;
     const int pair_words = (int)ceil_div(max_rows < kDetMaxCand ? max_rows : kDetMaxCand, 64);
     hipLaunchKernelGGL(det_pairs_kernel, dim3(kDetMaxCand / 256, (unsigned)n_images, (unsigned)pair_words), dim3(256), 0, s, L, img_count,
                        nms_thresh);
-    hipLaunchKernelGGL(det_nms_topk_kernel, dim3((unsigned)n_images), dim3(kDetThreads), lds, s, L, img_count, boxes, g, topk,
+    hipLaunchKernelGGL(det_nms_topk_kernel, dim3((unsigned)n_images), dim3(kDetThreads), lds, s, L, img_count, boxes, g, bk, cs, topk,
                        reinterpret_cast<float4 *>(out_boxes), out_scores, out_classes, out_rows, counts_and_flags);
-    return check_launch("locov_detect_postprocess");
+    return check_launch(who);
+}
+
+extern "C" {
+
+int64_t locov_detect_postprocess_workspace_bytes(int64_t R, int n_images) { return det_workspace_bytes(R, n_images, 1); }
+
+int64_t locov_detect_postprocess_cs_workspace_bytes(int64_t R, int n_images, int num_classes, int64_t ld_deltas, int box_classes)
+{
+    const char *who = "locov_detect_postprocess_cs_workspace_bytes";
+    LOCOV_REQUIRE(num_classes >= 1 && num_classes < (1 << kClsBits), "%s: 1..%d classes", who, (1 << kClsBits) - 1);
+    if (int rc = det_check_box_classes(num_classes, ld_deltas, box_classes, who)) return rc;
+    LOCOV_REQUIRE(R <= 0 || R * box_classes <= 0x7fffffff, "%s: rows x box_classes must stay below 2^31", who);
+    return det_workspace_bytes(R, n_images, box_classes);
+}
+
+int locov_detect_postprocess(const float *probs, int64_t ld_probs, int num_classes, const float *deltas, const float *proposal_boxes,
+                             const int *row_offsets, const float *image_hw, int n_images, float wx, float wy, float ww, float wh,
+                             float scale_clamp, float score_thresh, float nms_thresh, int topk, void *workspace, int64_t workspace_bytes,
+                             float *out_boxes, float *out_scores, int64_t *out_classes, int64_t *out_rows, int *counts_and_flags,
+                             locov_stream_t stream)
+{
+    return det_run("locov_detect_postprocess", probs, ld_probs, num_classes, deltas, 4, 1, proposal_boxes, row_offsets, image_hw, n_images, wx,
+                   wy, ww, wh, scale_clamp, score_thresh, nms_thresh, topk, workspace, workspace_bytes, out_boxes, out_scores, out_classes,
+                   out_rows, counts_and_flags, stream);
+}
+
+int locov_detect_postprocess_cs(const float *probs, int64_t ld_probs, int num_classes, const float *deltas, int64_t ld_deltas, int box_classes,
+                                const float *proposal_boxes, const int *row_offsets, const float *image_hw, int n_images, float wx, float wy,
+                                float ww, float wh, float scale_clamp, float score_thresh, float nms_thresh, int topk, void *workspace,
+                                int64_t workspace_bytes, float *out_boxes, float *out_scores, int64_t *out_classes, int64_t *out_rows,
+                                int *counts_and_flags, locov_stream_t stream)
+{
+    return det_run("locov_detect_postprocess_cs", probs, ld_probs, num_classes, deltas, ld_deltas, box_classes, proposal_boxes, row_offsets,
+                   image_hw, n_images, wx, wy, ww, wh, scale_clamp, score_thresh, nms_thresh, topk, workspace, workspace_bytes, out_boxes,
+                   out_scores, out_classes, out_rows, counts_and_flags, stream);
 }
 
 }  // extern "C"

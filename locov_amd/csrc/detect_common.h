@@ -26,14 +26,10 @@ __device__ __forceinline__ int det_image_of(const DetGeom &g, int r)
 
 __device__ __forceinline__ bool det_finite(float v) { return fabsf(v) <= 3.402823466e38f; }        // false for NaN / inf
 
-// Box2BoxTransform.apply_deltas (class-agnostic: one box per proposal) + Boxes.clip, rounded as the torch ops round
-__global__ __launch_bounds__(256) void det_decode_clip_kernel(const float4 *__restrict__ deltas, const float4 *__restrict__ props, int R,
-                                                              DetGeom g, float inv_wx, float inv_wy, float inv_ww, float inv_wh,
-                                                              float scale_clamp, float4 *__restrict__ boxes, int *__restrict__ flags)
+// Box2BoxTransform.apply_deltas of one delta quadruple on its proposal, rounded as the torch ops round (pre-clip)
+__device__ __forceinline__ float4 det_apply_deltas(const float4 d, const float4 b, float inv_wx, float inv_wy, float inv_ww, float inv_wh,
+                                                   float scale_clamp)
 {
-    const int r = blockIdx.x * 256 + threadIdx.x;
-    if (r >= R) return;
-    const float4 d = deltas[r], b = props[r];
     const float widths = __fsub_rn(b.z, b.x), heights = __fsub_rn(b.w, b.y);
     const float ctr_x = __fadd_rn(b.x, __fmul_rn(0.5f, widths)), ctr_y = __fadd_rn(b.y, __fmul_rn(0.5f, heights));
     const float dx = __fmul_rn(d.x, inv_wx), dy = __fmul_rn(d.y, inv_wy);
@@ -47,14 +43,46 @@ __global__ __launch_bounds__(256) void det_decode_clip_kernel(const float4 *__re
     o.y = __fsub_rn(pcy, __fmul_rn(0.5f, ph));
     o.z = __fadd_rn(pcx, __fmul_rn(0.5f, pw));
     o.w = __fadd_rn(pcy, __fmul_rn(0.5f, ph));
-    if (!(det_finite(o.x) && det_finite(o.y) && det_finite(o.z) && det_finite(o.w))) atomicOr(flags, LOCOV_DETECT_FLAG_NONFINITE);
-    const int img = det_image_of(g, r);
-    const float W = g.w[img], H = g.h[img];
+    return o;
+}
+
+__device__ __forceinline__ float4 det_clip(float4 o, float W, float H)         // Boxes.clip
+{
     o.x = fminf(fmaxf(o.x, 0.f), W);
     o.y = fminf(fmaxf(o.y, 0.f), H);
     o.z = fminf(fmaxf(o.z, 0.f), W);
     o.w = fminf(fmaxf(o.w, 0.f), H);
-    boxes[r] = o;
+    return o;
+}
+
+// Box2BoxTransform.apply_deltas (class-agnostic: one box per proposal) + Boxes.clip, rounded as the torch ops round
+__global__ __launch_bounds__(256) void det_decode_clip_kernel(const float4 *__restrict__ deltas, const float4 *__restrict__ props, int R,
+                                                              DetGeom g, float inv_wx, float inv_wy, float inv_ww, float inv_wh,
+                                                              float scale_clamp, float4 *__restrict__ boxes, int *__restrict__ flags)
+{
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= R) return;
+    const float4 o = det_apply_deltas(deltas[r], props[r], inv_wx, inv_wy, inv_ww, inv_wh, scale_clamp);
+    if (!(det_finite(o.x) && det_finite(o.y) && det_finite(o.z) && det_finite(o.w))) atomicOr(flags, LOCOV_DETECT_FLAG_NONFINITE);
+    const int img = det_image_of(g, r);
+    boxes[r] = det_clip(o, g.w[img], g.h[img]);
+}
+
+// The same with a box per (proposal, class): deltas [R, ld] holds K quadruples a row, boxes [R, K].  A thread per (r, c); EVERY
+// decoded box is checked for inf / NaN, a candidate's or not (the torch chain tests the whole [R, 4K] tensor).  R x K < 2^31.
+__global__ __launch_bounds__(256) void det_decode_clip_cs_kernel(const float *__restrict__ deltas, int64_t ld, const float4 *__restrict__ props,
+                                                                 int R, int K, DetGeom g, float inv_wx, float inv_wy, float inv_ww,
+                                                                 float inv_wh, float scale_clamp, float4 *__restrict__ boxes,
+                                                                 int *__restrict__ flags)
+{
+    const unsigned t = blockIdx.x * 256u + threadIdx.x;
+    if (t >= (unsigned)R * (unsigned)K) return;
+    const int r = (int)(t / (unsigned)K), c = (int)(t - (unsigned)r * (unsigned)K);
+    const float4 d = *reinterpret_cast<const float4 *>(deltas + (int64_t)r * ld + 4 * c);
+    const float4 o = det_apply_deltas(d, props[r], inv_wx, inv_wy, inv_ww, inv_wh, scale_clamp);
+    if (!(det_finite(o.x) && det_finite(o.y) && det_finite(o.z) && det_finite(o.w))) atomicOr(flags, LOCOV_DETECT_FLAG_NONFINITE);
+    const int img = det_image_of(g, r);
+    boxes[t] = det_clip(o, g.w[img], g.h[img]);
 }
 
 __device__ __forceinline__ bool det_iou_gt(const float4 a, const float4 b, float thr)        // (= nms.hip's iou_gt)

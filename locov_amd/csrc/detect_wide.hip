@@ -13,7 +13,12 @@
 //       proposals, one R x R bit matrix per image serves every class;
 //   inside a class: descending score, ties by row; survivors merged by (descending score, row, class), the first `topk` kept.
 //
-//   det_decode_clip_kernel   (detect_common.h) apply_deltas + clip, one thread per proposal
+// Class-specific regression (locov_detect_postprocess_wide_cs with box_classes = K: deltas [R, 4K], boxes [R, K]) keeps the segments,
+// the orders and the top-k and changes which box a candidate has -- its OWN: the shift unit is the maximum over the candidates' own
+// boxes; the shifted branch reads each candidate's own box; the per-class branch has no matrix to share and tests its pairs inside the
+// sweep (dw_sweep_cs_kernel).  The class-agnostic kernels are template instances of their own and run as before.
+//
+//   det_decode_clip_kernel   (detect_common.h) apply_deltas + clip, one thread per proposal (_cs: per (proposal, class))
 //   dw_count_kernel          a workgroup per (64 rows of an image, 256 columns): candidates per (image, class); non-finite
 //                            probabilities; the max coordinate over the image's candidate boxes (batched_nms's shift unit)
 //   dw_scan_kernel           one workgroup: segment offsets per (image, class), candidates per image, the branch of each image
@@ -23,6 +28,8 @@
 //                            of its class overlap it (IoU on the SHIFTED boxes)
 //   dw_sweep_kernel          a wave per segment: the greedy sweep over the segment with the kept set in registers; survivors are
 //                            compacted to the segment's front as  ~score << 29 | row << 15 | class  (the merge order)
+//   dw_sweep_cs_kernel       class-specific boxes, per-class images: a wave per segment, 64 candidates a step -- IoU against the
+//                            survivors so far, then among themselves, resolved in candidate order; same survivor layout
 //   dw_select_kernel x 6     radix select, 11 bits a pass, chip-wide histograms; the last workgroup of an image picks the digit:
 //                            ends as soon as the keys below a threshold number at least top-k and at most kDwCap
 //   dw_gather_kernel         those keys into one buffer per image
@@ -41,6 +48,7 @@ constexpr int kDwMaxImages = LOCOV_LABEL_MAX_IMAGES;
 
 struct DwPlan {
     int n_img, K, pca;
+    int bk, cs;                                 // boxes per proposal (1 or K) and 0 / 1: candidate (row, class) has box row * bk + class * cs
     int cbase[kDwMaxImages + 1];                // row chunks of image i: [cbase[i], cbase[i + 1])
     int W[kDwMaxImages];                        // 64-bit words of a row / candidate overlap set of image i: ceil(rows / 64)
     int64_t mbase[kDwMaxImages];                // word offset of image i's row x row matrix (rows * W words)
@@ -63,7 +71,7 @@ struct DwImage {                                // per image, zeroed at the star
 static_assert(sizeof(DwImage) == 128, "DwImage: 128 bytes per image (the documented workspace formula)");
 
 struct DwWork {
-    float4 *boxes;                              // [R] decoded, clipped
+    float4 *boxes;                              // [R, bk] decoded, clipped
     DwImage *info;                              // [n_img]
     int *hist;                                  // [kDwPasses][n_img][kDwBins]
     int *cnt, *kept, *seg_off, *cursor;         // [n_img * K] candidates / survivors / first slot / emit cursor per segment
@@ -83,7 +91,9 @@ __device__ __forceinline__ int dw_chunk_image(const DwPlan &p, int chunk)
     return lo;
 }
 
-// a workgroup per (64 rows, 256 columns); every one of the K + 1 columns must be finite
+// a workgroup per (64 rows, 256 columns); every one of the K + 1 columns must be finite.  CS: class-specific boxes (an instance of
+// its own, so that the class-agnostic loop stays as it was)
+template <bool CS>
 __global__ __launch_bounds__(256) void dw_count_kernel(const float *__restrict__ probs, int64_t ld, float thr, DetGeom g, DwPlan p, DwWork w)
 {
     __shared__ unsigned long long rows_hit;
@@ -95,6 +105,7 @@ __global__ __launch_bounds__(256) void dw_count_kernel(const float *__restrict__
     int n = 0;
     unsigned long long mask = 0;
     bool bad = false;
+    float own = -__builtin_inff();              // class-specific boxes: the max coordinate over this thread's candidates' OWN boxes
     if (c <= K)
         for (int r = r0; r < r1; r++) {
             const float v = probs[(int64_t)r * ld + c];
@@ -102,10 +113,20 @@ __global__ __launch_bounds__(256) void dw_count_kernel(const float *__restrict__
             if (c < K && v > thr) {
                 n++;
                 mask |= 1ull << (r - r0);
+                if constexpr (CS) {
+                    const float4 b = w.boxes[(int64_t)r * K + c];
+                    own = fmaxf(own, fmaxf(fmaxf(b.x, b.y), fmaxf(b.z, b.w)) + 0.f);
+                }
             }
         }
     if (__ballot(bad) != 0ull && lane == 0) atomicOr(w.flags, LOCOV_DETECT_FLAG_NONFINITE);
     if (n) atomicAdd(&w.cnt[img * K + c], n);
+    if constexpr (CS) {                         // (a row has K different boxes: the maximum is over candidates, not over rows)
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) own = fmaxf(own, __shfl_xor(own, o));
+        if (lane == 0 && own >= 0.f) atomicMax(&w.info[img].umax, __float_as_uint(own));
+        return;
+    }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) mask |= __shfl_xor(mask, o);
     if (lane == 0 && mask) atomicOr(&rows_hit, mask);
@@ -198,14 +219,16 @@ __global__ __launch_bounds__(256) void dw_segsort_kernel(DwWork w)
 // per-class images: bit k of word wd of row j = IoU(box j, box 64 wd + k) > thr (the unshifted boxes; IoU is symmetric bit for bit).
 // shifted images: a thread per candidate: bit j of its word wd = its class's candidate 64 wd + j (an earlier one) overlaps it on
 // the shifted boxes.
+template <bool CS>
 __global__ __launch_bounds__(256) void dw_overlap_kernel(DetGeom g, DwPlan p, DwWork w, float nms_thr)
 {
+    const int bk = CS ? p.K : 1;                // candidate (row, class) has box row * bk + (CS ? class : 0)
     const int img = blockIdx.y, t = blockIdx.x * 256 + threadIdx.x, W = p.W[img], K = p.K;
     const int rows = g.roff[img + 1] - g.roff[img];
-    const float4 *gb = w.boxes + g.roff[img];
+    const float4 *gb = w.boxes + (int64_t)g.roff[img] * bk;
     const DwImage &inf = w.info[img];
     if (inf.per_class) {
-        if (t >= rows * W) return;
+        if (CS || t >= rows * W) return;      // (class-specific boxes: no row x row matrix, dw_sweep_cs_kernel tests the pairs itself)
         const int j = t / W, wd = t - j * W;
         const float4 a = gb[j];
         const int lim = min(64, rows - 64 * wd);
@@ -225,7 +248,7 @@ __global__ __launch_bounds__(256) void dw_overlap_kernel(DetGeom g, DwPlan p, Dw
     }
     const int s = so[lo], pos = idx - s;
     const float off = (float)lo * (__uint_as_float(inf.umax) + 1.f);
-    float4 b = gb[(int)(w.keys[idx] & kDwRowMask)];
+    float4 b = gb[(int)(w.keys[idx] & kDwRowMask) * bk + (CS ? lo : 0)];
     b.x += off;
     b.y += off;
     b.z += off;
@@ -235,7 +258,7 @@ __global__ __launch_bounds__(256) void dw_overlap_kernel(DetGeom g, DwPlan p, Dw
         const int lim = min(64, pos - 64 * wd);
         unsigned long long bits = 0;
         for (int j = 0; j < lim; j++) {
-            float4 e = gb[(int)(w.keys[s + 64 * wd + j] & kDwRowMask)];
+            float4 e = gb[(int)(w.keys[s + 64 * wd + j] & kDwRowMask) * bk + (CS ? lo : 0)];
             e.x += off;
             e.y += off;
             e.z += off;
@@ -249,7 +272,7 @@ __global__ __launch_bounds__(256) void dw_overlap_kernel(DetGeom g, DwPlan p, Dw
 // a wave per segment: the greedy sweep in the segment's order.  Candidate a is kept iff none of the KEPT candidates overlaps it:
 // the kept set lives in registers (lane l holds words l, l + 64, ...: bits by row for per-class images, by segment position for
 // shifted ones), a candidate's overlap words are loaded 8 candidates ahead.  Survivors go to the segment's front in merge-key form.
-template <int NQ>
+template <int NQ, bool CS>
 __global__ __launch_bounds__(256) void dw_sweep_kernel(DwPlan p, DwWork w)
 {
     const int lane = threadIdx.x & 63;
@@ -259,6 +282,7 @@ __global__ __launch_bounds__(256) void dw_sweep_kernel(DwPlan p, DwWork w)
     if (m == 0) return;                         // (kept[] starts at zero)
     const int img = seg / p.K, cls = seg - img * p.K, s = w.seg_off[seg], W = p.W[img];
     const bool per_class = w.info[img].per_class != 0;
+    if (CS && per_class) return;                // (dw_sweep_cs_kernel's segment)
     const unsigned long long *Mi = w.M + p.mbase[img];
     const unsigned long long *ovs = w.ov + p.ovbase[img] + (int64_t)(s - w.info[img].base) * W;
     unsigned long long *keys = w.keys + s;
@@ -307,6 +331,70 @@ __global__ __launch_bounds__(256) void dw_sweep_kernel(DwPlan p, DwWork w)
                 }
             }
         }
+    }
+    if (lane == 0) {
+        w.kept[seg] = nk;
+        atomicAdd(&w.info[img].surv, nk);
+    }
+}
+
+__device__ __forceinline__ float4 dw_lane_box(const float4 v, int j)           // lane j's box (j uniform over the wave)
+{
+    float4 e;
+    e.x = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v.x), j));
+    e.y = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v.y), j));
+    e.z = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v.z), j));
+    e.w = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v.w), j));
+    return e;
+}
+
+// Class-specific boxes, per-class images: a wave per segment, the greedy sweep with the pair tests inside (every candidate has its own
+// box, so no matrix is shared between the classes).  64 candidates a step, one per lane: first against the survivors of the earlier
+// steps (64 at a time, a survivor's box handed round from its lane), then among themselves -- lane l's bit set of the step's earlier
+// candidates that overlap it, resolved in candidate order with one ballot per survivor.  The IoU is taken on the unshifted boxes.
+// Survivors go to the segment's front in merge-key form, as dw_sweep_kernel leaves them; the wave reads them back from there.
+__global__ __launch_bounds__(256) void dw_sweep_cs_kernel(DetGeom g, DwPlan p, DwWork w, float nms_thr)
+{
+    const int lane = threadIdx.x & 63;
+    const int seg = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (seg >= p.n_img * p.K) return;
+    const int m = w.cnt[seg];
+    if (m == 0) return;
+    const int img = seg / p.K, cls = seg - img * p.K, K = p.K;
+    if (!w.info[img].per_class) return;
+    const float4 *gb = w.boxes + (int64_t)g.roff[img] * K + cls;          // the class's box of row r: gb[r * K]
+    unsigned long long *keys = w.keys + w.seg_off[seg];
+    const float4 none = make_float4(0.f, 0.f, 0.f, 0.f);
+    int nk = 0;
+    for (int a0 = 0; a0 < m; a0 += 64) {
+        const int nb = min(64, m - a0);
+        const bool have = lane < nb;
+        const unsigned long long mykey = have ? keys[a0 + lane] : 0ull;
+        const float4 mine = have ? gb[(int64_t)(int)(mykey & kDwRowMask) * K] : none;
+        bool dead = !have;
+        for (int k0 = 0; k0 < nk && __ballot(!dead) != 0ull; k0 += 64) {
+            const int nkk = min(64, nk - k0);
+            float4 kb = none;
+            if (lane < nkk) {
+                const unsigned long long kk = __hip_atomic_load(&keys[k0 + lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                kb = gb[(int64_t)(int)((kk >> kDwClsBits) & kDwRowMask) * K];
+            }
+            for (int j = 0; j < nkk; j++) dead |= det_iou_gt(dw_lane_box(kb, j), mine, nms_thr);
+        }
+        unsigned long long earlier = 0;         // bit j: the step's candidate j < lane overlaps mine
+        for (int j = 0; j < nb - 1; j++) earlier |= (unsigned long long)(j < lane && det_iou_gt(dw_lane_box(mine, j), mine, nms_thr)) << j;
+        unsigned long long alive = __ballot(!dead), keep = 0;
+        while (alive) {
+            const int j = __ffsll((long long)alive) - 1;
+            keep |= 1ull << j;
+            alive &= ~(1ull << j) & ~__ballot(((earlier >> j) & 1ull) != 0ull);
+        }
+        if ((keep >> lane) & 1ull)              // (slot <= a0 + lane: never a candidate that is still to be read)
+            __hip_atomic_store(&keys[nk + __popcll(keep & ((1ull << lane) - 1ull))],
+                               ((mykey >> kDwRowBits) << (kDwRowBits + kDwClsBits)) | ((mykey & kDwRowMask) << kDwClsBits) | (unsigned long long)cls,
+                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        nk += __popcll(keep);
+        __threadfence();                        // the next step's lanes read what other lanes wrote here
     }
     if (lane == 0) {
         w.kept[seg] = nk;
@@ -417,7 +505,7 @@ __global__ __launch_bounds__(256) void dw_gather_kernel(DwPlan p, DwWork w)
     }
 }
 
-__global__ __launch_bounds__(1024) void dw_topk_kernel(DetGeom g, DwWork w, int topk, float4 *__restrict__ out_boxes, float *__restrict__ out_scores,
+__global__ __launch_bounds__(1024) void dw_topk_kernel(DetGeom g, DwWork w, int w_bk, int w_cs, int topk, float4 *__restrict__ out_boxes, float *__restrict__ out_scores,
                                                        int64_t *__restrict__ out_classes, int64_t *__restrict__ out_rows, int *__restrict__ counts)
 {
     extern __shared__ unsigned long long tkey[];
@@ -433,12 +521,12 @@ __global__ __launch_bounds__(1024) void dw_topk_kernel(DetGeom g, DwWork w, int 
     for (int i = tid; i < P; i += 1024) tkey[i] = i < n ? in[i] : ~0ull;
     __syncthreads();
     det_bitonic_sort<1024>(tkey, P, tid);
-    const float4 *gb = w.boxes + g.roff[img];
+    const float4 *gb = w.boxes + (int64_t)g.roff[img] * w_bk;
     for (int j = tid; j < k; j += 1024) {
         const unsigned long long key = tkey[j];
         const int cls = (int)(key & ((1ull << kDwClsBits) - 1ull)), row = (int)((key >> kDwClsBits) & kDwRowMask);
         const int64_t slot = (int64_t)img * topk + j;
-        out_boxes[slot] = gb[row];
+        out_boxes[slot] = gb[row * w_bk + cls * w_cs];
         out_scores[slot] = __uint_as_float(~(unsigned)(key >> (kDwRowBits + kDwClsBits)));
         out_classes[slot] = cls;
         out_rows[slot] = row;
@@ -447,14 +535,20 @@ __global__ __launch_bounds__(1024) void dw_topk_kernel(DetGeom g, DwWork w, int 
 }
 
 // the plan of a call and its workspace size, from host data only; < 0 on an argument error (set_error has run)
-static int64_t dw_plan(const int *row_offsets, int n_images, int K, int per_class_above, DwPlan *p, const char *who)
+static int64_t dw_plan(const int *row_offsets, int n_images, int K, int per_class_above, int64_t ld_deltas, int box_classes, DwPlan *p,
+                       const char *who)
 {
     LOCOV_REQUIRE(n_images >= 0 && n_images <= kDwMaxImages, "%s: too many images (0..%d per call)", who, kDwMaxImages);
     if (n_images == 0) return 0;
     LOCOV_REQUIRE(row_offsets, "%s: null row_offsets", who);
     LOCOV_REQUIRE(K >= 1 && K < (1 << kDwClsBits), "%s: too many classes (1..%d)", who, (1 << kDwClsBits) - 1);
+    LOCOV_REQUIRE(box_classes == 1 || box_classes == K, "%s: box_classes must be 1 or num_classes (%d), got %d", who, K, box_classes);
+    LOCOV_REQUIRE(ld_deltas >= 4 * (int64_t)box_classes && ld_deltas % 4 == 0,
+                  "%s: ld_deltas must cover the 4 x box_classes columns and be a multiple of 4", who);
     LOCOV_REQUIRE(row_offsets[0] == 0, "%s: offsets start at 0", who);
     p->n_img = n_images;
+    p->bk = box_classes;
+    p->cs = box_classes > 1 ? 1 : 0;
     p->K = K;
     p->pca = per_class_above;
     p->cbase[0] = 0;
@@ -468,7 +562,7 @@ static int64_t dw_plan(const int *row_offsets, int n_images, int K, int per_clas
         p->W[i] = (int)W;
         p->mbase[i] = mw;
         p->ovbase[i] = ow;
-        mw += rows * W;
+        mw += p->cs ? 0 : rows * W;             // (class-specific boxes: no row x row matrix)
         ow += cap * W;
         p->cbase[i + 1] = p->cbase[i] + (int)((rows + kDwChunkRows - 1) / kDwChunkRows);
         R += rows;
@@ -476,30 +570,21 @@ static int64_t dw_plan(const int *row_offsets, int n_images, int K, int per_clas
     LOCOV_REQUIRE(R * K <= 0x7fffffff, "%s: too many candidate slots (rows x classes must stay below 2^31)", who);
     if (R == 0) return 0;
     const int64_t nK = (int64_t)n_images * K;
-    return 16 * R + 16 * nK + (int64_t)n_images * (128 + 4 * kDwPasses * kDwBins + 8 * kDwCap) + 8 * (mw + ow + R * K);
+    return 16 * R * p->bk + 16 * nK + (int64_t)n_images * (128 + 4 * kDwPasses * kDwBins + 8 * kDwCap) + 8 * (mw + ow + R * K);
 }
 
 }  // namespace locov
 
 using namespace locov;
 
-extern "C" {
-
-int64_t locov_detect_postprocess_wide_workspace_bytes(const int *row_offsets, int n_images, int num_classes, int per_class_above)
+static int dw_run(const char *who, const float *probs, int64_t ld_probs, int num_classes, const float *deltas, int64_t ld_deltas,
+                  int box_classes, const float *proposal_boxes, const int *row_offsets, const float *image_hw, int n_images, float wx, float wy,
+                  float ww, float wh, float scale_clamp, float score_thresh, float nms_thresh, int topk, int per_class_above, void *workspace,
+                  int64_t workspace_bytes, float *out_boxes, float *out_scores, int64_t *out_classes, int64_t *out_rows, int *counts_and_flags,
+                  locov_stream_t stream)
 {
     DwPlan p;
-    return dw_plan(row_offsets, n_images, num_classes, per_class_above, &p, "locov_detect_postprocess_wide_workspace_bytes");
-}
-
-int locov_detect_postprocess_wide(const float *probs, int64_t ld_probs, int num_classes, const float *deltas, const float *proposal_boxes,
-                                  const int *row_offsets, const float *image_hw, int n_images, float wx, float wy, float ww, float wh,
-                                  float scale_clamp, float score_thresh, float nms_thresh, int topk, int per_class_above, void *workspace,
-                                  int64_t workspace_bytes, float *out_boxes, float *out_scores, int64_t *out_classes, int64_t *out_rows,
-                                  int *counts_and_flags, locov_stream_t stream)
-{
-    const char *who = "locov_detect_postprocess_wide";
-    DwPlan p;
-    const int64_t need = dw_plan(row_offsets, n_images, num_classes, per_class_above, &p, who);
+    const int64_t need = dw_plan(row_offsets, n_images, num_classes, per_class_above, ld_deltas, box_classes, &p, who);
     if (need < 0) return (int)need;
     if (n_images == 0) return LOCOV_OK;
     LOCOV_REQUIRE(image_hw, "%s: null image_hw", who);
@@ -529,7 +614,7 @@ int locov_detect_postprocess_wide(const float *probs, int64_t ld_probs, int num_
     char *ws = static_cast<char *>(workspace);
     DwWork w;
     w.boxes = reinterpret_cast<float4 *>(ws);
-    ws += 16 * R;
+    ws += 16 * R * p.bk;
     char *zero0 = ws;                                            // info, histograms, class counts, survivors: zeroed per call
     w.info = reinterpret_cast<DwImage *>(ws);
     ws += 128 * (int64_t)n_images;
@@ -547,7 +632,7 @@ int locov_detect_postprocess_wide(const float *probs, int64_t ld_probs, int num_
     int64_t mw = 0, ow = 0;
     for (int i = 0; i < n_images; i++) {
         const int64_t rows = g.roff[i + 1] - g.roff[i];
-        mw += rows * p.W[i];
+        mw += p.cs ? 0 : rows * p.W[i];
         const int64_t cap = per_class_above <= 0 ? 0 : (per_class_above - 1 < rows * K ? per_class_above - 1 : rows * K);
         ow += cap * p.W[i];
     }
@@ -569,10 +654,19 @@ int locov_detect_postprocess_wide(const float *probs, int64_t ld_probs, int num_
     if (attr_state[dev] != 1) return set_error(LOCOV_ERR_LAUNCH, "%s: cannot raise the dynamic LDS limit to %d bytes", who, lds_max);
 
     const float inv_wx = 1.0f / wx, inv_wy = 1.0f / wy, inv_ww = 1.0f / ww, inv_wh = 1.0f / wh;
-    hipLaunchKernelGGL(det_decode_clip_kernel, dim3((unsigned)ceil_div(R, 256)), dim3(256), 0, s, reinterpret_cast<const float4 *>(deltas),
-                       reinterpret_cast<const float4 *>(proposal_boxes), (int)R, g, inv_wx, inv_wy, inv_ww, inv_wh, scale_clamp, w.boxes, w.flags);
+    if (p.bk == 1 && ld_deltas == 4)
+        hipLaunchKernelGGL(det_decode_clip_kernel, dim3((unsigned)ceil_div(R, 256)), dim3(256), 0, s, reinterpret_cast<const float4 *>(deltas),
+                           reinterpret_cast<const float4 *>(proposal_boxes), (int)R, g, inv_wx, inv_wy, inv_ww, inv_wh, scale_clamp, w.boxes,
+                           w.flags);
+    else
+        hipLaunchKernelGGL(det_decode_clip_cs_kernel, dim3((unsigned)ceil_div(R * p.bk, 256)), dim3(256), 0, s, deltas, ld_deltas,
+                           reinterpret_cast<const float4 *>(proposal_boxes), (int)R, p.bk, g, inv_wx, inv_wy, inv_ww, inv_wh, scale_clamp,
+                           w.boxes, w.flags);
     const dim3 tiles((unsigned)p.cbase[n_images], (unsigned)ceil_div(K + 1, 256));
-    hipLaunchKernelGGL(dw_count_kernel, tiles, dim3(256), 0, s, probs, ld_probs, score_thresh, g, p, w);
+    if (p.cs)
+        hipLaunchKernelGGL(dw_count_kernel<true>, tiles, dim3(256), 0, s, probs, ld_probs, score_thresh, g, p, w);
+    else
+        hipLaunchKernelGGL(dw_count_kernel<false>, tiles, dim3(256), 0, s, probs, ld_probs, score_thresh, g, p, w);
     hipLaunchKernelGGL(dw_scan_kernel, dim3(1), dim3(1024), 0, s, p, w);
     hipLaunchKernelGGL(dw_emit_kernel, tiles, dim3(256), 0, s, probs, ld_probs, score_thresh, g, p, w);
     int max_rows = 0;
@@ -581,24 +675,72 @@ int locov_detect_postprocess_wide(const float *probs, int64_t ld_probs, int num_
         const int rows = g.roff[i + 1] - g.roff[i];
         max_rows = rows > max_rows ? rows : max_rows;
         const int64_t cap = per_class_above <= 0 ? 0 : (per_class_above - 1 < (int64_t)rows * K ? per_class_above - 1 : (int64_t)rows * K);
-        const int64_t items = (int64_t)rows * p.W[i] > cap ? (int64_t)rows * p.W[i] : cap;
+        const int64_t cells = p.cs ? 0 : (int64_t)rows * p.W[i];
+        const int64_t items = cells > cap ? cells : cap;
         max_items = items > max_items ? items : max_items;
     }
     int P = 2;
     while (P < max_rows) P <<= 1;
     hipLaunchKernelGGL(dw_segsort_kernel, dim3((unsigned)nK), dim3(256), (size_t)P * 8, s, w);
-    if (max_items > 0)
-        hipLaunchKernelGGL(dw_overlap_kernel, dim3((unsigned)ceil_div(max_items, 256), (unsigned)n_images), dim3(256), 0, s, g, p, w, nms_thresh);
-    if (max_rows <= 64 * 64)
-        hipLaunchKernelGGL(dw_sweep_kernel<1>, dim3((unsigned)ceil_div(nK, 4)), dim3(256), 0, s, p, w);
-    else
-        hipLaunchKernelGGL(dw_sweep_kernel<4>, dim3((unsigned)ceil_div(nK, 4)), dim3(256), 0, s, p, w);
+    const dim3 ov_grid((unsigned)ceil_div(max_items, 256), (unsigned)n_images), sweep_grid((unsigned)ceil_div(nK, 4));
+    if (!p.cs) {
+        if (max_items > 0) hipLaunchKernelGGL(dw_overlap_kernel<false>, ov_grid, dim3(256), 0, s, g, p, w, nms_thresh);
+        if (max_rows <= 64 * 64)
+            hipLaunchKernelGGL((dw_sweep_kernel<1, false>), sweep_grid, dim3(256), 0, s, p, w);
+        else
+            hipLaunchKernelGGL((dw_sweep_kernel<4, false>), sweep_grid, dim3(256), 0, s, p, w);
+    } else {                                                     // (shifted images, then the per-class images' segments)
+        if (max_items > 0) hipLaunchKernelGGL(dw_overlap_kernel<true>, ov_grid, dim3(256), 0, s, g, p, w, nms_thresh);
+        if (max_rows <= 64 * 64)
+            hipLaunchKernelGGL((dw_sweep_kernel<1, true>), sweep_grid, dim3(256), 0, s, p, w);
+        else
+            hipLaunchKernelGGL((dw_sweep_kernel<4, true>), sweep_grid, dim3(256), 0, s, p, w);
+        hipLaunchKernelGGL(dw_sweep_cs_kernel, sweep_grid, dim3(256), 0, s, g, p, w, nms_thresh);
+    }
     const dim3 class_chunks((unsigned)ceil_div(K, kDwClassChunk), (unsigned)n_images);
     for (int pass = 0; pass < kDwPasses; pass++) hipLaunchKernelGGL(dw_select_kernel, class_chunks, dim3(256), 0, s, p, w, topk, pass);
     hipLaunchKernelGGL(dw_gather_kernel, class_chunks, dim3(256), 0, s, p, w);
-    hipLaunchKernelGGL(dw_topk_kernel, dim3((unsigned)n_images), dim3(1024), (size_t)lds_max, s, g, w, topk,
+    hipLaunchKernelGGL(dw_topk_kernel, dim3((unsigned)n_images), dim3(1024), (size_t)lds_max, s, g, w, p.bk, p.cs, topk,
                        reinterpret_cast<float4 *>(out_boxes), out_scores, out_classes, out_rows, counts_and_flags);
     return check_launch(who);
+}
+
+extern "C" {
+
+int64_t locov_detect_postprocess_wide_workspace_bytes(const int *row_offsets, int n_images, int num_classes, int per_class_above)
+{
+    DwPlan p;
+    return dw_plan(row_offsets, n_images, num_classes, per_class_above, 4, 1, &p, "locov_detect_postprocess_wide_workspace_bytes");
+}
+
+int64_t locov_detect_postprocess_wide_cs_workspace_bytes(const int *row_offsets, int n_images, int num_classes, int per_class_above,
+                                                         int64_t ld_deltas, int box_classes)
+{
+    DwPlan p;
+    return dw_plan(row_offsets, n_images, num_classes, per_class_above, ld_deltas, box_classes, &p,
+                   "locov_detect_postprocess_wide_cs_workspace_bytes");
+}
+
+int locov_detect_postprocess_wide(const float *probs, int64_t ld_probs, int num_classes, const float *deltas, const float *proposal_boxes,
+                                  const int *row_offsets, const float *image_hw, int n_images, float wx, float wy, float ww, float wh,
+                                  float scale_clamp, float score_thresh, float nms_thresh, int topk, int per_class_above, void *workspace,
+                                  int64_t workspace_bytes, float *out_boxes, float *out_scores, int64_t *out_classes, int64_t *out_rows,
+                                  int *counts_and_flags, locov_stream_t stream)
+{
+    return dw_run("locov_detect_postprocess_wide", probs, ld_probs, num_classes, deltas, 4, 1, proposal_boxes, row_offsets, image_hw, n_images,
+                  wx, wy, ww, wh, scale_clamp, score_thresh, nms_thresh, topk, per_class_above, workspace, workspace_bytes, out_boxes,
+                  out_scores, out_classes, out_rows, counts_and_flags, stream);
+}
+
+int locov_detect_postprocess_wide_cs(const float *probs, int64_t ld_probs, int num_classes, const float *deltas, int64_t ld_deltas,
+                                     int box_classes, const float *proposal_boxes, const int *row_offsets, const float *image_hw, int n_images,
+                                     float wx, float wy, float ww, float wh, float scale_clamp, float score_thresh, float nms_thresh, int topk,
+                                     int per_class_above, void *workspace, int64_t workspace_bytes, float *out_boxes, float *out_scores,
+                                     int64_t *out_classes, int64_t *out_rows, int *counts_and_flags, locov_stream_t stream)
+{
+    return dw_run("locov_detect_postprocess_wide_cs", probs, ld_probs, num_classes, deltas, ld_deltas, box_classes, proposal_boxes,
+                  row_offsets, image_hw, n_images, wx, wy, ww, wh, scale_clamp, score_thresh, nms_thresh, topk, per_class_above, workspace,
+                  workspace_bytes, out_boxes, out_scores, out_classes, out_rows, counts_and_flags, stream);
 }
 
 }  // extern "C"

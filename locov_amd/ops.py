@@ -797,8 +797,9 @@ def detect_postprocess(probs: torch.Tensor, deltas: torch.Tensor, proposal_boxes
     """The detection post-processing of a batch on the device (csrc/detect.hip): box decoding, clipping, score threshold,
     class-wise NMS, top-k -- seven launches and ONE host read (the detections per image + the flag word) instead of the torch
     chain's ~100 launches and four reads.
-    probs [R, K + 1] = softmax of the logits, deltas / proposal_boxes [R, 4] (class-agnostic regression), sizes: rows per image,
-    image_shapes: (height, width) per image, weights: Box2BoxTransform's.
+    probs [R, K + 1] = softmax of the logits, proposal_boxes [R, 4], deltas [R, 4] (class-agnostic regression) or [R, 4K]
+    (class-specific: candidate (r, c) has the box decoded from deltas[r, 4c:4c + 4]), sizes: rows per image, image_shapes:
+    (height, width) per image, weights: Box2BoxTransform's.
     Returns (boxes [B, topk, 4], scores [B, topk], classes [B, topk] int64, rows [B, topk] int64, counts: list of B ints), or None
     when the kernels flagged a case they do not take (non-finite values, more than DETECT_MAX_CANDIDATES candidates in an image):
     the caller then runs the torch chain."""
@@ -810,23 +811,34 @@ def detect_postprocess(probs: torch.Tensor, deltas: torch.Tensor, proposal_boxes
 def _detect_postprocess_flags(probs, deltas, proposal_boxes, sizes, image_shapes, weights, scale_clamp, score_thresh, nms_thresh, topk,
                               per_class_above=None):
     """detect_postprocess's work, with the flag word (DETECT_FLAG_*) returned next to the outputs instead of folded into None.
-    per_class_above=None: the LDS pipeline (locov_detect_postprocess); an int: the wide one (locov_detect_postprocess_wide)."""
+    per_class_above=None: the LDS pipeline (locov_detect_postprocess); an int: the wide one (locov_detect_postprocess_wide).
+    deltas [R, 4K] with K > 1 go to the class-specific entry points (locov_detect_postprocess_cs / _wide_cs)."""
     probs, deltas, proposal_boxes = _dev(probs, "probs"), _dev(deltas, "deltas"), _dev(proposal_boxes, "proposal_boxes")
     B, R, K = len(sizes), probs.shape[0], probs.shape[1] - 1
-    if not (tuple(deltas.shape) == (R, 4) and tuple(proposal_boxes.shape) == (R, 4) and sum(sizes) == R and len(image_shapes) == B):
-        raise ValueError("detect_postprocess: inconsistent shapes")
+    if not (deltas.dim() == 2 and deltas.shape[0] == R and deltas.shape[1] in (4, 4 * K) and tuple(proposal_boxes.shape) == (R, 4)
+            and sum(sizes) == R and len(image_shapes) == B):
+        raise ValueError("detect_postprocess: inconsistent shapes (deltas must be [R, 4] or [R, 4K])")
+    box_classes = deltas.shape[1] // 4
     if not (0 < B <= DETECT_MAX_IMAGES and 1 <= K <= DETECT_MAX_CLASSES and 1 <= topk <= DETECT_MAX_TOPK
-            and max(sizes, default=0) <= DETECT_MAX_ROWS_PER_IMAGE):
-        raise ValueError("detect_postprocess: outside the kernels' limits (images, classes, rows per image or top-k)")
+            and max(sizes, default=0) <= DETECT_MAX_ROWS_PER_IMAGE and R * box_classes < 2 ** 31):
+        raise ValueError("detect_postprocess: outside the kernels' limits (images, classes, rows per image, rows x classes or top-k)")
     lib = _lib.load()
     dev = probs.device
     offs = (ctypes.c_int * (B + 1))(0, *itertools.accumulate(int(n) for n in sizes))
     hw = (ctypes.c_float * (2 * B))(*[float(v) for shape in image_shapes for v in shape[:2]])
     if per_class_above is None:
-        nbytes = int(lib.locov_detect_postprocess_workspace_bytes(max(R, 1), B))
+        if box_classes == 1:
+            nbytes = int(lib.locov_detect_postprocess_workspace_bytes(max(R, 1), B))
+        else:
+            nbytes = int(lib.locov_detect_postprocess_cs_workspace_bytes(max(R, 1), B, K, deltas.stride(0), box_classes))
+            if nbytes < 0:
+                check(nbytes, "locov_detect_postprocess_cs_workspace_bytes")
     else:
         per_class_above = max(min(int(per_class_above), 2 ** 31 - 1), -2 ** 31)
-        nbytes = int(lib.locov_detect_postprocess_wide_workspace_bytes(offs, B, K, per_class_above))
+        if box_classes == 1:
+            nbytes = int(lib.locov_detect_postprocess_wide_workspace_bytes(offs, B, K, per_class_above))
+        else:
+            nbytes = int(lib.locov_detect_postprocess_wide_cs_workspace_bytes(offs, B, K, per_class_above, deltas.stride(0), box_classes))
         if nbytes < 0:
             check(nbytes, "locov_detect_postprocess_wide_workspace_bytes")
     ws = _workspace("detect", probs, nbytes)
@@ -837,7 +849,19 @@ def _detect_postprocess_flags(probs, deltas, proposal_boxes, sizes, image_shapes
     counts = torch.empty((B + 1,), dtype=torch.int32, device=dev)
     wx, wy, ww, wh = (float(w) for w in weights)
     with torch.cuda.device(dev):
-        if per_class_above is None:
+        if box_classes > 1 and per_class_above is None:
+            check(lib.locov_detect_postprocess_cs(_ptr(probs), probs.stride(0), K, _ptr(deltas), deltas.stride(0), box_classes,
+                                                  _ptr(proposal_boxes), offs, hw, B, wx, wy, ww, wh, float(scale_clamp), float(score_thresh),
+                                                  float(nms_thresh), int(topk), _ptr(ws), ws.numel(), _ptr(out_boxes), _ptr(out_scores),
+                                                  _ptr(out_classes), _ptr(out_rows), _ptr(counts), _stream(probs)),
+                  "locov_detect_postprocess_cs")
+        elif box_classes > 1:
+            check(lib.locov_detect_postprocess_wide_cs(_ptr(probs), probs.stride(0), K, _ptr(deltas), deltas.stride(0), box_classes,
+                                                       _ptr(proposal_boxes), offs, hw, B, wx, wy, ww, wh, float(scale_clamp),
+                                                       float(score_thresh), float(nms_thresh), int(topk), per_class_above, _ptr(ws),
+                                                       ws.numel(), _ptr(out_boxes), _ptr(out_scores), _ptr(out_classes), _ptr(out_rows),
+                                                       _ptr(counts), _stream(probs)), "locov_detect_postprocess_wide_cs")
+        elif per_class_above is None:
             check(lib.locov_detect_postprocess(_ptr(probs), probs.stride(0), K, _ptr(deltas), _ptr(proposal_boxes), offs, hw, B, wx, wy, ww,
                                                wh, float(scale_clamp), float(score_thresh), float(nms_thresh), int(topk), _ptr(ws),
                                                ws.numel(), _ptr(out_boxes), _ptr(out_scores), _ptr(out_classes), _ptr(out_rows),

@@ -411,16 +411,19 @@ class FastRCNNOutputLayers(nn.Module):
 
     def _inference_fused(self, predictions, proposals):
         """predict_boxes + predict_probs + fast_rcnn_inference as ONE device pipeline (ops.detect_postprocess: csrc/detect.hip)
-        for the case both reference configurations evaluate: class-agnostic box regression on device fp32 tensors, a top-k.
+        for class-agnostic (deltas [R, 4]: what both reference configurations evaluate) or class-specific (deltas [R, 4K]: Detectron2's
+        default, the plain Fast R-CNN baseline) box regression on device fp32 tensors, with a top-k.
         Returns None for anything else -- and when the kernels flag non-finite values -- so that the caller runs the torch chain;
         an image with more candidates than the LDS pipeline holds goes to ops.detect_postprocess_wide (csrc/detect_wide.hip).  The
-        detections are bit-identical to the chain's (tests/test_gpu_postprocess.py, tests/test_gpu_detect_wide.py)."""
+        detections are bit-identical to the chain's (tests/test_gpu_postprocess.py, tests/test_gpu_detect_wide.py,
+        tests/test_gpu_detect_class_specific.py)."""
         if not _FUSED_POSTPROCESS or not len(proposals):
             return None
         scores, deltas = predictions
         sizes = [len(p) for p in proposals]
         K = scores.shape[1] - 1
-        if not (scores.is_cuda and scores.dtype == torch.float32 and deltas.dtype == torch.float32 and deltas.dim() == 2 and deltas.shape[1] == 4
+        if not (scores.is_cuda and scores.dtype == torch.float32 and deltas.dtype == torch.float32 and deltas.dim() == 2
+                and deltas.shape[1] in (4, 4 * K) and deltas.shape[0] == scores.shape[0] and scores.shape[0] * (deltas.shape[1] // 4) < 2 ** 31
                 and scores.shape[0] == sum(sizes) > 0 and len(sizes) <= ops.DETECT_MAX_IMAGES and 1 <= K <= ops.DETECT_MAX_CLASSES
                 and 1 <= self.test_topk_per_image <= ops.DETECT_MAX_TOPK and max(sizes) <= ops.DETECT_MAX_ROWS_PER_IMAGE):
             return None
@@ -436,7 +439,7 @@ class FastRCNNOutputLayers(nn.Module):
         overflowed = getattr(self, "_detect_overflow", None)
         if overflowed is None:
             overflowed = self._detect_overflow = set()
-        setting = (float(self.test_score_thresh), int(self.test_topk_per_image), K)
+        setting = (float(self.test_score_thresh), int(self.test_topk_per_image), K)      # (candidates are counted on the scores alone)
         out = None
         if setting not in overflowed:
             out, flags = ops._detect_postprocess_flags(*args)
