@@ -477,6 +477,30 @@ int locov_box_reg_loss(const float *proposal_boxes, const float *gt_boxes, const
                        float smooth_l1_beta, float *loss, float *dpred, locov_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * a-11  the classification loss of the training heads and its training statistics from ONE pass over the logits.  Replaces the
+ * torch-op chain of [D2-upstream] FastRCNNOutputLayers.losses' `cross_entropy(scores, gt_classes, reduction="mean")`, which the
+ * reference's predictors inherit (ovr/modeling/roi_heads/box_emb_head.py:60 and box_emb_grounding_head.py:259: both subclass
+ * FastRCNNOutputLayers and define no losses of their own; roi_emb_heads.py:266,347 call it), and gathers the counts of [D2-upstream,
+ * unverified] _log_classification_stats, which upstream's losses() calls first.
+ *   scores [R, ld] fp32 with ld >= C columns per row (a column block of a wider matrix is fine; no alignment is required -- 16-byte
+ *   loads are used when base, ld and C allow them, with the same bits either way), gt_classes [R] int64, ignore_index: torch's -100.
+ *   loss [1]: mean over the rows that count (label in [0, C) and not ignore_index) of logsumexp(row) - row[label], max-subtracted;
+ *   NaN when no row counts, as torch's.
+ *   dscores [R, C] contiguous or NULL: d loss / d scores = (softmax - onehot) / n_valid, exact zeros in the rows that do not count.
+ *   NULL (the scores need no gradient): nothing of that size is written.
+ *   stats [6] int64 or NULL: num_instances (= R), num_fg, num_accurate, fg_num_accurate, num_false_negative, num_invalid with
+ *   pred = argmax(row) (lowest index among equal maxima), bg = C - 1, foreground = 0 <= label < bg; num_accurate: pred == label;
+ *   fg_num_accurate: the same over the foreground rows; num_false_negative: foreground rows with pred == bg; num_invalid: labels
+ *   that are neither in [0, C) nor ignore_index (torch asserts on the device for these; here the row is treated as ignored).
+ *   workspace: locov_cls_loss_workspace_bytes(R) bytes, 8-byte aligned: one partial per block, added in block order by a second
+ *   small launch -- no atomics, the same inputs give the same bits.  No host read.
+ * ------------------------------------------------------------------------------------- */
+int64_t locov_cls_loss_workspace_bytes(int64_t R);
+
+int locov_cls_loss(const float *scores, int64_t ld, const int64_t *gt_classes, int64_t R, int C, int64_t ignore_index,
+                   void *workspace, int64_t workspace_bytes, float *loss, float *dscores, int64_t *stats, locov_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * a-10  greedy NMS on the device.  Replaces [D2-upstream] torchvision.ops.nms as reached from
  * box_predictor.inference -> fast_rcnn_inference -> batched_nms
  * (ovr/modeling/roi_heads/roi_emb_heads.py:280,357).

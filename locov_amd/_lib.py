@@ -92,6 +92,8 @@ SIGNATURES = {
     "locov_sample_proposals": (c_int, [_p, _p, _p, _p, _p, _p, _p, _p, POINTER(c_int), POINTER(c_int), c_int, c_int, c_int, c_int64,
                                        _p, _p, _p, _p, _p, _p, _p, _p]),
     "locov_box_reg_loss": (c_int, [_p, _p, _p, c_int64, _p, c_int64, c_int64, c_float, c_float, c_float, c_float, c_float, _p, _p, _p]),
+    "locov_cls_loss_workspace_bytes": (c_int64, [c_int64]),
+    "locov_cls_loss": (c_int, [_p, c_int64, _p, c_int64, c_int, c_int64, _p, c_int64, _p, _p, _p, _p]),
     "locov_grounding_ce_fwd": (c_int, [_p, _p, _p, _p, c_int, c_int, c_int, _p, _p]),
     "locov_grounding_ce_bwd": (c_int, [_p, _p, _p, _p, c_int, c_int, c_int, _p, _p, _p, _p, _p, _p, _p]),
     "locov_grounding_ce_dist_fwd": (c_int, [_p, _p, _p, _p, c_int, c_int, c_int, _p, _p, _p, _p]),

@@ -1691,6 +1691,61 @@ def box_reg_loss(pred_deltas: torch.Tensor, proposal_boxes: torch.Tensor, gt_box
     return _BoxRegLossFn.apply(pred_deltas.float(), proposal_boxes, gt_boxes, gt_classes, num_classes, tuple(weights), smooth_l1_beta)
 
 
+CLS_STATS = ("num_instances", "num_fg", "num_accurate", "fg_num_accurate", "num_false_negative", "num_invalid")
+
+
+class _ClsLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, scores, gt_classes, ignore_index, want_stats):
+        R, C = scores.shape
+        # a column block of a wider matrix is read in place (any row stride, any base alignment)
+        if not (scores.stride(1) == 1 and scores.stride(0) >= C):
+            scores = scores.contiguous()
+        cls = gt_classes if gt_classes.is_contiguous() else gt_classes.contiguous()
+        dev = scores.device
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        stats = torch.empty(len(CLS_STATS), dtype=torch.int64, device=dev) if want_stats else None
+        dscores = torch.empty((R, C), dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
+        lib = _lib.load()
+        ws = _workspace("cls_loss", scores, lib.locov_cls_loss_workspace_bytes(R))
+        with torch.cuda.device(dev):
+            check(lib.locov_cls_loss(scores.data_ptr(), scores.stride(0), cls.data_ptr(), R, C, ignore_index, ws.data_ptr(), ws.numel(),
+                                     loss.data_ptr(), _ptr(dscores), _ptr(stats), _stream(scores)), "locov_cls_loss")
+        ctx.dscores = dscores
+        ctx.set_materialize_grads(False)                     # (no zeros for the statistics' "gradient")
+        if stats is None:
+            return loss
+        ctx.mark_non_differentiable(stats)
+        return loss, stats
+
+    @staticmethod
+    def backward(ctx, g, *_):
+        return (ctx.dscores * g if ctx.dscores is not None and g is not None else None), None, None, None
+
+
+def cls_loss(scores: torch.Tensor, gt_classes: torch.Tensor, ignore_index: int = -100,
+             want_stats: bool = True) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """[D2-upstream] FastRCNNOutputLayers.losses' cross_entropy(scores, gt_classes, reduction="mean") and the counts of
+    _log_classification_stats from one pass over the logits (locov_cls_loss: a row kernel and a small finishing launch).
+    scores [R, C] fp32 on the device (R > 0; rows may be a column block of a wider matrix), gt_classes [R] int64.  Returns
+    (loss, stats): the 0-dim loss, differentiable in scores -- the gradient is made by the same pass, backward only multiplies it by
+    the incoming gradient -- and the int64 [6] device tensor of CLS_STATS (None without want_stats).  Nothing is read to the host."""
+    if not isinstance(scores, torch.Tensor) or not isinstance(gt_classes, torch.Tensor):
+        raise TypeError("cls_loss: scores and gt_classes must be torch.Tensors")
+    if not scores.is_cuda or gt_classes.device != scores.device:
+        raise LocovError(f"cls_loss: scores are on {scores.device}, gt_classes on {gt_classes.device}: the kernel only runs on a ROCm GPU "
+                         "(there is no CPU fallback)")
+    if scores.dtype != torch.float32 or gt_classes.dtype != torch.int64:
+        raise TypeError(f"cls_loss: scores must be torch.float32 and gt_classes torch.int64, got {scores.dtype} and {gt_classes.dtype}")
+    if scores.dim() != 2 or scores.shape[0] < 1 or scores.shape[1] < 1 or tuple(gt_classes.shape) != (scores.shape[0],):
+        raise ValueError(f"cls_loss: scores [R, C] with R, C >= 1 and gt_classes [R], got {tuple(scores.shape)} and "
+                         f"{tuple(gt_classes.shape)}")
+    if not torch.is_grad_enabled():
+        scores = scores.detach()                             # (no gradient buffer under no_grad)
+    res = _ClsLossFn.apply(scores, gt_classes, int(ignore_index), bool(want_stats))
+    return res if want_stats else (res, None)
+
+
 def rownorm(x: torch.Tensor, mode: int, eps: float = 1e-12) -> torch.Tensor:
     x = _dev(x, "x")
     R, D = x.shape

@@ -26,6 +26,7 @@ from torch.nn import functional as F
 from .. import ops
 from ..registry import configurable
 from ..structures import Boxes, Instances, ShapeSpec, boxes_class_of, cat_rows
+from .labelling import get_event_storage
 
 __all__ = ["Box2BoxTransform", "FastRCNNOutputLayers", "EmbeddingFastRCNNOutputLayers", "build_box_predictor",
            "fast_rcnn_inference", "batched_nms"]
@@ -297,6 +298,9 @@ class FastRCNNOutputLayers(nn.Module):
     """[D2-upstream] the parts of FastRCNNOutputLayers the reference inherits: the bbox_pred
     layer, losses(), inference(), predict_boxes(), predict_probs()."""
 
+    _cls_stats = None       # the last losses() call: the loss kernel's counts (a device tensor, not read) ...
+    _cls_last = None        # ... or, on the torch path, its (logits, gt_classes)
+
     @configurable
     def __init__(self, input_shape, *, box2box_transform, num_classes: int, test_score_thresh: float = 0.0,
                  test_nms_thresh: float = 0.5, test_topk_per_image: int = 100, cls_agnostic_bbox_reg: bool = False,
@@ -358,15 +362,60 @@ class FastRCNNOutputLayers(nn.Module):
             gt_boxes = cat_rows([(p.gt_boxes if p.has("gt_boxes") else p.proposal_boxes).tensor for p in proposals])
         else:
             proposal_boxes = gt_boxes = torch.empty((0, 4), device=proposal_deltas.device)
+        self._cls_stats = self._cls_last = None
         if gt_classes.numel() == 0:
             loss_cls = scores.sum() * 0.0
+        elif _FUSED_BOX_LOSS and scores.is_cuda and scores.dtype == torch.float32 and scores.dim() == 2:
+            # one pass over the logits (ops.cls_loss = locov_cls_loss): the loss, its gradient and the counts behind
+            # classification_stats(); the counts stay on the device until someone asks for them
+            loss_cls, self._cls_stats = ops.cls_loss(scores, gt_classes)
         else:
             loss_cls = F.cross_entropy(scores, gt_classes, reduction="mean")
+            self._cls_last = (scores.detach(), gt_classes)
         losses = {"loss_cls": loss_cls,
                   "loss_box_reg": self.box_reg_loss(proposal_boxes, gt_boxes, proposal_deltas, gt_classes,
                                                     boxes_validated=boxes_validated)}
         # (a weight of exactly 1 changes no bit: no launch for it, forward or backward)
         return {k: v if self.loss_weight.get(k, 1.0) == 1.0 else v * self.loss_weight[k] for k, v in losses.items()}
+
+    def classification_stats(self) -> Dict[str, float]:
+        """[D2-upstream, unverified] the scalars of _log_classification_stats for the last losses() call: cls_accuracy, and
+        fg_cls_accuracy / false_negative when the call had foreground rows.  ONE host read (losses() makes none: on the device the
+        counts come out of the loss kernel's pass; on the torch path they are formed here from the call's logits).  Empty before
+        the first call and after a call without proposals.  Labels that are neither a class nor the ignore index raise."""
+        if self._cls_stats is not None:
+            counts = self._cls_stats.tolist()
+        elif self._cls_last is not None:
+            pred_logits, gt_classes = self._cls_last
+            pred_classes = pred_logits.argmax(dim=1)
+            bg_class_ind = pred_logits.shape[1] - 1
+            fg_inds = (gt_classes >= 0) & (gt_classes < bg_class_ind)
+            hit = pred_classes == gt_classes
+            invalid = ((gt_classes < 0) | (gt_classes > bg_class_ind)) & (gt_classes != -100)
+            counts = torch.stack([fg_inds.sum(), hit.sum(), (hit & fg_inds).sum(), ((pred_classes == bg_class_ind) & fg_inds).sum(),
+                                  invalid.sum()]).tolist()
+            counts.insert(0, gt_classes.numel())
+        else:
+            return {}
+        num_instances, num_fg, num_accurate, fg_num_accurate, num_false_negative, num_invalid = counts
+        if num_invalid > 0:
+            raise ValueError(f"classification_stats: {num_invalid} of {num_instances} gt_classes are neither in "
+                             f"[0, num_classes] nor the ignore index")
+        stats = {"cls_accuracy": num_accurate / num_instances}
+        if num_fg > 0:
+            stats["fg_cls_accuracy"] = fg_num_accurate / num_fg
+            stats["false_negative"] = num_false_negative / num_fg
+        return stats
+
+    def log_classification_stats(self, prefix: str = "fast_rcnn", storage=None) -> Dict[str, float]:
+        """classification_stats() into the event storage as `{prefix}/cls_accuracy` etc. (Detectron2's when training under its
+        trainer, else the stand-in of labelling.py).  For a trainer hook at its log period: neither losses() nor forward() calls it."""
+        stats = self.classification_stats()
+        if stats:
+            storage = get_event_storage() if storage is None else storage
+            for k, v in stats.items():
+                storage.put_scalar(f"{prefix}/{k}", v)
+        return stats
 
     def box_reg_loss(self, proposal_boxes, gt_boxes, pred_deltas, gt_classes, boxes_validated: bool = False):
         """[D2-upstream] smooth-L1 over the foreground rows, normalised by ALL rows.  The foreground rows are selected by a
