@@ -501,6 +501,53 @@ int locov_cls_loss(const float *scores, int64_t ld, const int64_t *gt_classes, i
                    void *workspace, int64_t workspace_bytes, float *loss, float *dscores, int64_t *stats, locov_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * a-11  the federated class set of LVIS-style training, formed on the device in ONE launch without a host read.  Restates
+ * [D2-upstream, unverified] FastRCNNOutputLayers.get_fed_loss_classes (MODEL.ROI_BOX_HEAD.USE_FED_LOSS; public Detectron2, not part of
+ * the reference): `torch.unique(gt_classes)`, whose length is a device-to-host read, and `torch.multinomial(prob, num_fed - len(unique),
+ * replacement=False)`, whose data-dependent sample count is another.
+ *   gt_classes [R] int64 (any R >= 0), weights [K] fp32: the per-class sampling weights (upstream: image count to the power
+ *   FED_LOSS_FREQ_WEIGHT_POWER), rnd [K] fp32: strictly positive Exp(1) draws made by the caller, num_fed >= 0: the size the set is
+ *   filled up to (FED_LOSS_NUM_CLASSES), 1 <= K <= LOCOV_FED_LOSS_MAX_CLASSES.
+ *   A class c in [0, K] is present when some label equals it; the background label K counts towards the number present, as it does in
+ *   upstream's unique, but has no mask entry; labels outside [0, K] are skipped.  n_sample = max(0, num_fed - n_present).  Among the
+ *   classes in [0, K) that are not present and whose weight is finite and > 0, the n_sample largest keys weights[c] / rnd[c] -- a
+ *   correctly rounded fp32 division, so a torch restatement gives the same bits -- are sampled, equal keys going to the lower class
+ *   index.  Dividing by Exp(1) draws and taking the top n is a weighted sample without replacement: the distribution is
+ *   torch.multinomial's, the random stream is not.  With fewer such classes than n_sample all of them are taken (upstream's multinomial
+ *   raises there).
+ *   mask [K] bytes: present[c] || sampled[c];  counts [2] int32: {labels present, classes sampled}.  Both stay on the device.
+ *   One block: a presence bitmap in LDS, then a radix select over the keys and a scan for the equal keys at the cut.
+ * ------------------------------------------------------------------------------------- */
+#define LOCOV_FED_LOSS_MAX_CLASSES 32767
+int locov_fed_loss_classes(const int64_t *gt_classes, int64_t R, const float *weights, const float *rnd, int K, int num_fed,
+                           unsigned char *mask, int *counts, locov_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
+ * a-11  the per-class sigmoid classification loss of LVIS-style training, its gradient and the training statistics from ONE pass
+ * over the logits.  Replaces the torch-op chain of [D2-upstream, unverified] FastRCNNOutputLayers.sigmoid_cross_entropy_loss
+ * (MODEL.ROI_BOX_HEAD.USE_SIGMOID_CE; public Detectron2, not part of the reference): an [R, K + 1] zeros target, an index-put, a slice,
+ * binary_cross_entropy_with_logits, the class-mask broadcast and a sum; the counts are those of _log_classification_stats, which
+ * upstream logs whatever the loss type.
+ *   scores [R, ld] fp32 with C = K + 1 columns per row and ld >= C (a column block of a wider matrix is fine; no alignment is required
+ *   -- 16-byte loads are used when base, ld and C allow them, with the same bits either way), gt_classes [R] int64, class_mask [K]
+ *   bytes (locov_fed_loss_classes' mask) or NULL for every class.
+ *   loss [1]: sum over rows r and classes c < K of mask[c] * bce(x_rc, t_rc) / R with t_rc = 1 exactly when gt_classes[r] == c and
+ *   bce(x, t) = max(x, 0) - x t + log1p(exp(-|x|)).  The background column never enters the loss; a background label (K) makes its row
+ *   all-negative.
+ *   dscores [R, C] contiguous or NULL: d loss / d scores = mask[c] * (sigmoid(x) - t) / R for c < K, exactly 0 in the background column
+ *   and in masked-out classes.  NULL (the scores need no gradient): nothing of that size is written.
+ *   stats [6] int64 or NULL: locov_cls_loss' six counters in its order, from the argmax over all C columns (lowest index among equal
+ *   maxima).  A label outside [0, K] counts in num_invalid (upstream's index-put fails for it) and its row contributes nothing: no loss
+ *   terms and an exactly zero gradient; the divisor stays R.
+ *   workspace: locov_sigmoid_cls_loss_workspace_bytes(R) bytes, 8-byte aligned: one partial per block, added in block order by a
+ *   second small launch -- no atomics, the same inputs give the same bits.  No host read.
+ * ------------------------------------------------------------------------------------- */
+int64_t locov_sigmoid_cls_loss_workspace_bytes(int64_t R);
+
+int locov_sigmoid_cls_loss(const float *scores, int64_t ld, const int64_t *gt_classes, const unsigned char *class_mask, int64_t R, int C,
+                           void *workspace, int64_t workspace_bytes, float *loss, float *dscores, int64_t *stats, locov_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * a-10  greedy NMS on the device.  Replaces [D2-upstream] torchvision.ops.nms as reached from
  * box_predictor.inference -> fast_rcnn_inference -> batched_nms
  * (ovr/modeling/roi_heads/roi_emb_heads.py:280,357).

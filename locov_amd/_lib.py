@@ -28,6 +28,7 @@ ZERO_LIST_MAX = 24
 LABEL_MAX_IMAGES, LABEL_MAX_THRESHOLDS, SAMPLE_MAX_PROPOSALS = 64, 6, 4096
 ABI_VERSION = 8
 DETECT_MAX_CANDIDATES, DETECT_FLAG_NONFINITE, DETECT_FLAG_OVERFLOW = 8192, 1, 2
+FED_LOSS_MAX_CLASSES = 32767
 DISTILL_KD, DISTILL_JS, DISTILL_MSE, DISTILL_MAX_B = 0, 1, 2, 64
 REGIONS_MAX_B, REGIONS_MAX_CANDIDATES = 64, 4096
 REGIONS_GRID, REGIONS_GRID_ALL, REGIONS_BOXES = 0, 1, 2
@@ -94,6 +95,9 @@ SIGNATURES = {
     "locov_box_reg_loss": (c_int, [_p, _p, _p, c_int64, _p, c_int64, c_int64, c_float, c_float, c_float, c_float, c_float, _p, _p, _p]),
     "locov_cls_loss_workspace_bytes": (c_int64, [c_int64]),
     "locov_cls_loss": (c_int, [_p, c_int64, _p, c_int64, c_int, c_int64, _p, c_int64, _p, _p, _p, _p]),
+    "locov_fed_loss_classes": (c_int, [_p, c_int64, _p, _p, c_int, c_int, _p, _p, _p]),
+    "locov_sigmoid_cls_loss_workspace_bytes": (c_int64, [c_int64]),
+    "locov_sigmoid_cls_loss": (c_int, [_p, c_int64, _p, _p, c_int64, c_int, _p, c_int64, _p, _p, _p, _p]),
     "locov_grounding_ce_fwd": (c_int, [_p, _p, _p, _p, c_int, c_int, c_int, _p, _p]),
     "locov_grounding_ce_bwd": (c_int, [_p, _p, _p, _p, c_int, c_int, c_int, _p, _p, _p, _p, _p, _p, _p]),
     "locov_grounding_ce_dist_fwd": (c_int, [_p, _p, _p, _p, c_int, c_int, c_int, _p, _p, _p, _p]),

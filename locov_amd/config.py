@@ -110,6 +110,10 @@ def get_cfg() -> CfgNode:
                 "BBOX_REG_LOSS_TYPE": "smooth_l1",                 # [D2-upstream]
                 "BBOX_REG_LOSS_WEIGHT": 1.0,                       # [D2-upstream]
                 "SMOOTH_L1_BETA": 0.0,                             # [D2-upstream]
+                "USE_SIGMOID_CE": False,                           # [D2-upstream] per-class sigmoid cross-entropy instead of the softmax
+                "USE_FED_LOSS": False,                             # [D2-upstream] ... over a federated class set (needs USE_SIGMOID_CE)
+                "FED_LOSS_FREQ_WEIGHT_POWER": 0.5,                 # [D2-upstream] sampling weight = image count ** this
+                "FED_LOSS_NUM_CLASSES": 50,                        # [D2-upstream] size the class set is filled up to
                 "EMBEDDING_BASED": False,                          # config.py:124
                 "EMB_DIM": 768,                                    # config.py:126
                 "FREEZE_EMB_PRED": False,                          # config.py:129
@@ -144,4 +148,5 @@ def get_cfg() -> CfgNode:
             },
         },
         "TEST": {"DETECTIONS_PER_IMAGE": 100},                     # [D2-upstream]
+        "DATASETS": {"TRAIN": ()},                                 # [D2-upstream] (USE_FED_LOSS: whose class_image_count to read)
     })

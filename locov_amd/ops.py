@@ -1746,6 +1746,103 @@ def cls_loss(scores: torch.Tensor, gt_classes: torch.Tensor, ignore_index: int =
     return res if want_stats else (res, None)
 
 
+FED_LOSS_MAX_CLASSES = _lib.FED_LOSS_MAX_CLASSES
+
+
+def fed_loss_classes(gt_classes: torch.Tensor, weights: torch.Tensor, num_fed: int,
+                     rnd: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """[D2-upstream, unverified] FastRCNNOutputLayers.get_fed_loss_classes on the device (locov_fed_loss_classes: one launch, no host
+    read): the classes present among gt_classes [R] int64 plus, up to num_fed in all, classes sampled without replacement by
+    weights [K] fp32 -- the top keys weights / rnd with rnd [K] strictly positive Exp(1) draws.  Without rnd they are drawn here from
+    the device's default generator (one launch, no wait, reproducible under torch.manual_seed).  Returns (mask [K] uint8,
+    counts [2] int32 = {labels present, classes sampled}), both on the device."""
+    if not isinstance(gt_classes, torch.Tensor) or not isinstance(weights, torch.Tensor) or not isinstance(rnd, (torch.Tensor, type(None))):
+        raise TypeError("fed_loss_classes: gt_classes, weights and rnd must be torch.Tensors")
+    if not weights.is_cuda or gt_classes.device != weights.device or (rnd is not None and rnd.device != weights.device):
+        raise LocovError(f"fed_loss_classes: weights are on {weights.device}, gt_classes on {gt_classes.device}"
+                         + (f", rnd on {rnd.device}" if rnd is not None else "") + ": the kernel only runs on a ROCm GPU "
+                         "(there is no CPU fallback)")
+    if weights.dtype != torch.float32 or gt_classes.dtype != torch.int64 or (rnd is not None and rnd.dtype != torch.float32):
+        raise TypeError(f"fed_loss_classes: weights (and rnd) must be torch.float32 and gt_classes torch.int64, got {weights.dtype} and "
+                        f"{gt_classes.dtype}")
+    K = weights.shape[0] if weights.dim() == 1 else -1
+    if not 1 <= K <= FED_LOSS_MAX_CLASSES or gt_classes.dim() != 1 or (rnd is not None and tuple(rnd.shape) != (K,)):
+        raise ValueError(f"fed_loss_classes: weights [K] with 1 <= K <= {FED_LOSS_MAX_CLASSES}, rnd [K] and gt_classes [R], got "
+                         f"{tuple(weights.shape)}, {None if rnd is None else tuple(rnd.shape)} and {tuple(gt_classes.shape)}")
+    if int(num_fed) < 0:
+        raise ValueError(f"fed_loss_classes: num_fed must be >= 0, got {num_fed}")
+    dev = weights.device
+    if rnd is None:
+        rnd = torch.empty(K, dtype=torch.float32, device=dev).exponential_()
+    weights, rnd, cls = weights.detach().contiguous(), rnd.detach().contiguous(), gt_classes.contiguous()
+    mask = torch.empty(K, dtype=torch.uint8, device=dev)
+    counts = torch.empty(2, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        check(_lib.load().locov_fed_loss_classes(_ptr(cls), cls.shape[0], _ptr(weights), _ptr(rnd), K, int(num_fed), _ptr(mask),
+                                                 _ptr(counts), _stream(weights)), "locov_fed_loss_classes")
+    return mask, counts
+
+
+class _SigmoidClsLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, scores, gt_classes, class_mask, want_stats):
+        R, C = scores.shape
+        # a column block of a wider matrix is read in place (any row stride, any base alignment)
+        if not (scores.stride(1) == 1 and scores.stride(0) >= C):
+            scores = scores.contiguous()
+        cls = gt_classes if gt_classes.is_contiguous() else gt_classes.contiguous()
+        if class_mask is not None and not class_mask.is_contiguous():
+            class_mask = class_mask.contiguous()
+        dev = scores.device
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        stats = torch.empty(len(CLS_STATS), dtype=torch.int64, device=dev) if want_stats else None
+        dscores = torch.empty((R, C), dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
+        lib = _lib.load()
+        ws = _workspace("sigmoid_cls_loss", scores, lib.locov_sigmoid_cls_loss_workspace_bytes(R))
+        with torch.cuda.device(dev):
+            check(lib.locov_sigmoid_cls_loss(scores.data_ptr(), scores.stride(0), cls.data_ptr(), _ptr(class_mask), R, C, ws.data_ptr(),
+                                             ws.numel(), loss.data_ptr(), _ptr(dscores), _ptr(stats), _stream(scores)),
+                  "locov_sigmoid_cls_loss")
+        ctx.dscores = dscores
+        ctx.set_materialize_grads(False)                     # (no zeros for the statistics' "gradient")
+        if stats is None:
+            return loss
+        ctx.mark_non_differentiable(stats)
+        return loss, stats
+
+    @staticmethod
+    def backward(ctx, g, *_):
+        return (ctx.dscores * g if ctx.dscores is not None and g is not None else None), None, None, None
+
+
+def sigmoid_cls_loss(scores: torch.Tensor, gt_classes: torch.Tensor, class_mask: Optional[torch.Tensor] = None,
+                     want_stats: bool = True) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """[D2-upstream, unverified] FastRCNNOutputLayers.sigmoid_cross_entropy_loss and the counts of _log_classification_stats from one
+    pass over the logits (locov_sigmoid_cls_loss: a row kernel and a small finishing launch).  scores [R, K + 1] fp32 on the device
+    (R > 0; rows may be a column block of a wider matrix), gt_classes [R] int64 in [0, K], class_mask [K] uint8 (fed_loss_classes'
+    mask) or None for every class.  Returns (loss, stats): the 0-dim sum of the masked per-class binary cross-entropies over R,
+    differentiable in scores -- the gradient is made by the same pass, backward only multiplies it by the incoming gradient -- and the
+    int64 [6] device tensor of CLS_STATS (None without want_stats).  Nothing is read to the host."""
+    if not isinstance(scores, torch.Tensor) or not isinstance(gt_classes, torch.Tensor) \
+            or not isinstance(class_mask, (torch.Tensor, type(None))):
+        raise TypeError("sigmoid_cls_loss: scores, gt_classes and class_mask must be torch.Tensors")
+    if not scores.is_cuda or gt_classes.device != scores.device or (class_mask is not None and class_mask.device != scores.device):
+        raise LocovError(f"sigmoid_cls_loss: scores are on {scores.device}, gt_classes on {gt_classes.device}"
+                         + (f", class_mask on {class_mask.device}" if class_mask is not None else "")
+                         + ": the kernel only runs on a ROCm GPU (there is no CPU fallback)")
+    if scores.dtype != torch.float32 or gt_classes.dtype != torch.int64 or (class_mask is not None and class_mask.dtype != torch.uint8):
+        raise TypeError(f"sigmoid_cls_loss: scores must be torch.float32, gt_classes torch.int64 and class_mask torch.uint8, got "
+                        f"{scores.dtype}, {gt_classes.dtype} and {None if class_mask is None else class_mask.dtype}")
+    if scores.dim() != 2 or scores.shape[0] < 1 or scores.shape[1] < 2 or tuple(gt_classes.shape) != (scores.shape[0],) \
+            or (class_mask is not None and tuple(class_mask.shape) != (scores.shape[1] - 1,)):
+        raise ValueError(f"sigmoid_cls_loss: scores [R, K + 1] with R, K >= 1, gt_classes [R] and class_mask [K], got "
+                         f"{tuple(scores.shape)}, {tuple(gt_classes.shape)} and {None if class_mask is None else tuple(class_mask.shape)}")
+    if not torch.is_grad_enabled():
+        scores = scores.detach()                             # (no gradient buffer under no_grad)
+    res = _SigmoidClsLossFn.apply(scores, gt_classes, class_mask, bool(want_stats))
+    return res if want_stats else (res, None)
+
+
 def rownorm(x: torch.Tensor, mode: int, eps: float = 1e-12) -> torch.Tensor:
     x = _dev(x, "x")
     R, D = x.shape

@@ -134,12 +134,15 @@ class EmbeddingGroundingFastRCNNOutputLayers(FastRCNNOutputLayers):
                  smooth_l1_beta: float = 0.0, box_reg_loss_type: str = "smooth_l1",
                  loss_weight: Union[float, Dict[str, float]] = 1.0, emb_dim: int = 768, embedding_based: bool = True,
                  freeze_emb_pred: bool = True, normalize_emb: bool = False, detach_cls_predictor: bool = False,
-                 grounding_module: GroundingModule = None):
+                 grounding_module: GroundingModule = None, use_fed_loss: bool = False, use_sigmoid_ce: bool = False,
+                 get_fed_loss_cls_weights=None, fed_loss_num_classes: int = 50):
         FastRCNNOutputLayers.__init__(
             self, input_shape, box2box_transform=box2box_transform, num_classes=num_classes,
             test_score_thresh=test_score_thresh, test_nms_thresh=test_nms_thresh,
             test_topk_per_image=test_topk_per_image, cls_agnostic_bbox_reg=cls_agnostic_bbox_reg,
-            smooth_l1_beta=smooth_l1_beta, box_reg_loss_type=box_reg_loss_type, loss_weight=loss_weight)
+            smooth_l1_beta=smooth_l1_beta, box_reg_loss_type=box_reg_loss_type, loss_weight=loss_weight,
+            use_fed_loss=use_fed_loss, use_sigmoid_ce=use_sigmoid_ce, get_fed_loss_cls_weights=get_fed_loss_cls_weights,
+            fed_loss_num_classes=fed_loss_num_classes)
         if isinstance(input_shape, int):
             input_shape = ShapeSpec(channels=input_shape)
         num_inputs = input_shape.channels * (input_shape.width or 1) * (input_shape.height or 1)

@@ -16,7 +16,7 @@ from __future__ import annotations
 
 import math
 import os
-from typing import Dict, List, Tuple, Union
+from typing import Callable, Dict, List, Optional, Tuple, Union
 
 import numpy as np
 import torch
@@ -29,7 +29,7 @@ from ..structures import Boxes, Instances, ShapeSpec, boxes_class_of, cat_rows
 from .labelling import get_event_storage
 
 __all__ = ["Box2BoxTransform", "FastRCNNOutputLayers", "EmbeddingFastRCNNOutputLayers", "build_box_predictor",
-           "fast_rcnn_inference", "batched_nms"]
+           "fast_rcnn_inference", "batched_nms", "get_fed_loss_cls_weights"]
 
 _DEFAULT_SCALE_CLAMP = math.log(1000.0 / 16)
 _FUSED_BOX_LOSS = os.environ.get("LOCOV_FUSED_LOSSES", "1") != "0"          # (developer A/B switch: tools/attic/ab_fused_losses.py)
@@ -294,18 +294,59 @@ def hip_linear(x: torch.Tensor, layer: nn.Linear) -> torch.Tensor:
     return ops.linear_autograd(x, layer.weight, layer.bias)
 
 
+def get_fed_loss_cls_weights(dataset_names, freq_weight_power: float = 1.0) -> torch.Tensor:
+    """[D2-upstream, unverified] detectron2.data.detection_utils.get_fed_loss_cls_weights: the per-class sampling weights of the
+    federated loss, image count ** freq_weight_power in class-id order, from the `class_image_count` metadata of the (one) training
+    dataset.  The counts live in Detectron2's MetadataCatalog: without Detectron2 there is nowhere to read them from."""
+    if isinstance(dataset_names, str):
+        dataset_names = [dataset_names]
+    if len(dataset_names) != 1:
+        raise ValueError(f"get_fed_loss_cls_weights: the federated loss takes its class frequencies from exactly one training dataset, "
+                         f"got {list(dataset_names)}")
+    try:
+        from detectron2.data import MetadataCatalog
+    except ImportError as e:
+        raise RuntimeError("MODEL.ROI_BOX_HEAD.USE_FED_LOSS needs the per-class image counts of the training dataset "
+                           f"(MetadataCatalog.get({dataset_names[0]!r}).class_image_count), and Detectron2 is not importable: pass "
+                           "get_fed_loss_cls_weights=<a callable returning num_classes weights> to the box predictor instead") from e
+    meta = MetadataCatalog.get(dataset_names[0])
+    if not hasattr(meta, "class_image_count"):
+        raise RuntimeError(f"get_fed_loss_cls_weights: dataset {dataset_names[0]!r} has no class_image_count metadata")
+    counts = sorted(meta.class_image_count, key=lambda x: x["id"])
+    return torch.tensor([c["image_count"] for c in counts], dtype=torch.float32) ** freq_weight_power
+
+
+def fed_loss_classes_torch(gt_classes: torch.Tensor, weights: torch.Tensor, num_fed: int, rnd: torch.Tensor):
+    """ops.fed_loss_classes with torch ops (host reads allowed): [D2-upstream, unverified] get_fed_loss_classes with the multinomial
+    written as the top keys weights / rnd.  Returns (mask [K] uint8, counts [2] int32)."""
+    K = weights.shape[0]
+    present = torch.zeros(K + 1, dtype=torch.bool, device=weights.device)
+    present[gt_classes[(gt_classes >= 0) & (gt_classes <= K)]] = True
+    n_present = int(present.sum())
+    candidate = ~present[:K] & torch.isfinite(weights) & (weights > 0)
+    n_take = min(max(0, int(num_fed) - n_present), int(candidate.sum()))
+    key = torch.where(candidate, weights.float() / rnd, torch.full_like(rnd, -1.0))
+    order = torch.sort(key, descending=True, stable=True).indices            # (stable: equal keys go to the lower class index)
+    mask = present[:K].clone()
+    mask[order[:n_take]] = True
+    return mask.to(torch.uint8), torch.tensor([n_present, n_take], dtype=torch.int32, device=weights.device)
+
+
 class FastRCNNOutputLayers(nn.Module):
     """[D2-upstream] the parts of FastRCNNOutputLayers the reference inherits: the bbox_pred
     layer, losses(), inference(), predict_boxes(), predict_probs()."""
 
     _cls_stats = None       # the last losses() call: the loss kernel's counts (a device tensor, not read) ...
     _cls_last = None        # ... or, on the torch path, its (logits, gt_classes)
+    _fed_loss_mask = None   # the last losses() call with use_fed_loss: its class set ([K] uint8) and {labels present, classes sampled}
+    _fed_loss_counts = None
 
     @configurable
     def __init__(self, input_shape, *, box2box_transform, num_classes: int, test_score_thresh: float = 0.0,
                  test_nms_thresh: float = 0.5, test_topk_per_image: int = 100, cls_agnostic_bbox_reg: bool = False,
                  smooth_l1_beta: float = 0.0, box_reg_loss_type: str = "smooth_l1",
-                 loss_weight: Union[float, Dict[str, float]] = 1.0):
+                 loss_weight: Union[float, Dict[str, float]] = 1.0, use_fed_loss: bool = False, use_sigmoid_ce: bool = False,
+                 get_fed_loss_cls_weights: Optional[Callable] = None, fed_loss_num_classes: int = 50):
         super().__init__()
         if isinstance(input_shape, int):
             input_shape = ShapeSpec(channels=input_shape)
@@ -328,10 +369,30 @@ class FastRCNNOutputLayers(nn.Module):
         if isinstance(loss_weight, float):
             loss_weight = {"loss_cls": loss_weight, "loss_box_reg": loss_weight}
         self.loss_weight = dict(loss_weight)
+        # [D2-upstream, unverified] USE_SIGMOID_CE / USE_FED_LOSS: per-class sigmoid cross-entropy, optionally over a federated class set
+        self.use_fed_loss = use_fed_loss
+        self.use_sigmoid_ce = use_sigmoid_ce
+        self.fed_loss_num_classes = fed_loss_num_classes
+        if self.use_fed_loss:
+            assert self.use_sigmoid_ce, "Please use sigmoid cross entropy loss with federated loss"
+            fed_loss_cls_weights = torch.as_tensor(get_fed_loss_cls_weights(), dtype=torch.float32)
+            assert len(fed_loss_cls_weights) == num_classes, "Please check the provided fed_loss_cls_weights. Their size should match num_classes"
+            self.register_buffer("fed_loss_cls_weights", fed_loss_cls_weights, persistent=False)      # (no checkpoint key)
 
     @classmethod
     def from_config(cls, cfg, input_shape):
+        box_head = cfg.MODEL.ROI_BOX_HEAD
+        fed = {
+            "use_fed_loss": box_head.USE_FED_LOSS,
+            "use_sigmoid_ce": box_head.USE_SIGMOID_CE,
+            "fed_loss_num_classes": box_head.FED_LOSS_NUM_CLASSES,
+        }
+        if box_head.USE_FED_LOSS:
+            # (looked up in this module at call time: the function is the seam for a caller, or a test, with its own frequencies)
+            names, power = cfg.DATASETS.TRAIN, box_head.FED_LOSS_FREQ_WEIGHT_POWER
+            fed["get_fed_loss_cls_weights"] = lambda: globals()["get_fed_loss_cls_weights"](names, power)
         return {
+            **fed,
             "input_shape": input_shape,
             "box2box_transform": Box2BoxTransform(weights=cfg.MODEL.ROI_BOX_HEAD.BBOX_REG_WEIGHTS),
             "num_classes": cfg.MODEL.ROI_HEADS.NUM_CLASSES,
@@ -362,9 +423,11 @@ class FastRCNNOutputLayers(nn.Module):
             gt_boxes = cat_rows([(p.gt_boxes if p.has("gt_boxes") else p.proposal_boxes).tensor for p in proposals])
         else:
             proposal_boxes = gt_boxes = torch.empty((0, 4), device=proposal_deltas.device)
-        self._cls_stats = self._cls_last = None
+        self._cls_stats = self._cls_last = self._fed_loss_mask = self._fed_loss_counts = None
         if gt_classes.numel() == 0:
             loss_cls = scores.sum() * 0.0
+        elif self.use_sigmoid_ce:
+            loss_cls = self.sigmoid_cross_entropy_loss(scores, gt_classes)
         elif _FUSED_BOX_LOSS and scores.is_cuda and scores.dtype == torch.float32 and scores.dim() == 2:
             # one pass over the logits (ops.cls_loss = locov_cls_loss): the loss, its gradient and the counts behind
             # classification_stats(); the counts stay on the device until someone asks for them
@@ -377,6 +440,36 @@ class FastRCNNOutputLayers(nn.Module):
                                                     boxes_validated=boxes_validated)}
         # (a weight of exactly 1 changes no bit: no launch for it, forward or backward)
         return {k: v if self.loss_weight.get(k, 1.0) == 1.0 else v * self.loss_weight[k] for k, v in losses.items()}
+
+    def sigmoid_cross_entropy_loss(self, scores, gt_classes):
+        """[D2-upstream, unverified] the per-class sigmoid cross-entropy over the K foreground columns, with use_fed_loss only over
+        the federated class set, summed and divided by the number of rows.  Device fp32 logits: two launches of ours and the draw of
+        the Exp(1) keys, no host read (ops.fed_loss_classes, ops.sigmoid_cls_loss).  Otherwise the torch chain: upstream restated with
+        the same presence / key / top-n rule and the same draw, so that the two agree.  A label outside [0, K] gives its row no loss
+        term and no gradient (upstream's index-put fails there) and is counted for classification_stats()."""
+        K = scores.shape[1] - 1
+        rnd = None
+        if self.use_fed_loss:
+            assert K == self.fed_loss_cls_weights.shape[0], "fed_loss_cls_weights do not match the number of classes of the logits"
+            rnd = torch.empty(K, dtype=torch.float32, device=scores.device).exponential_()
+        if _FUSED_BOX_LOSS and scores.is_cuda and scores.dtype == torch.float32 and scores.dim() == 2:
+            mask = None
+            if self.use_fed_loss:
+                mask, self._fed_loss_counts = ops.fed_loss_classes(gt_classes, self.fed_loss_cls_weights, self.fed_loss_num_classes, rnd)
+                self._fed_loss_mask = mask
+            loss_cls, self._cls_stats = ops.sigmoid_cls_loss(scores, gt_classes, mask)
+            return loss_cls
+        N = scores.shape[0]
+        valid = (gt_classes >= 0) & (gt_classes <= K)
+        target = ((gt_classes[:, None] == torch.arange(K, device=scores.device)[None, :]) & valid[:, None]).to(scores.dtype)
+        cls_loss = F.binary_cross_entropy_with_logits(scores[:, :-1], target, reduction="none")
+        weight = valid[:, None].to(scores.dtype)
+        if self.use_fed_loss:
+            mask, self._fed_loss_counts = fed_loss_classes_torch(gt_classes, self.fed_loss_cls_weights, self.fed_loss_num_classes, rnd)
+            self._fed_loss_mask = mask
+            weight = weight * mask.view(1, K).to(scores.dtype)
+        self._cls_last = (scores.detach(), gt_classes)
+        return torch.sum(cls_loss * weight) / N
 
     def classification_stats(self) -> Dict[str, float]:
         """[D2-upstream, unverified] the scalars of _log_classification_stats for the last losses() call: cls_accuracy, and
@@ -391,7 +484,9 @@ class FastRCNNOutputLayers(nn.Module):
             bg_class_ind = pred_logits.shape[1] - 1
             fg_inds = (gt_classes >= 0) & (gt_classes < bg_class_ind)
             hit = pred_classes == gt_classes
-            invalid = ((gt_classes < 0) | (gt_classes > bg_class_ind)) & (gt_classes != -100)
+            invalid = (gt_classes < 0) | (gt_classes > bg_class_ind)
+            if not self.use_sigmoid_ce:                                   # (cross_entropy's ignore_index; the sigmoid loss has none)
+                invalid = invalid & (gt_classes != -100)
             counts = torch.stack([fg_inds.sum(), hit.sum(), (hit & fg_inds).sum(), ((pred_classes == bg_class_ind) & fg_inds).sum(),
                                   invalid.sum()]).tolist()
             counts.insert(0, gt_classes.numel())
@@ -480,7 +575,8 @@ class FastRCNNOutputLayers(nn.Module):
         if any(t.dtype != torch.float32 or not t.is_cuda for t in pieces):
             return None
         image_shapes = [x.image_size for x in proposals]
-        probs = F.softmax(scores, dim=-1)                                  # (torch's own softmax: predict_probs' values)
+        # (torch's own softmax / sigmoid: predict_probs' values)
+        probs = torch.sigmoid(scores) if self.use_sigmoid_ce else F.softmax(scores, dim=-1)
         args = (probs, deltas, cat_rows(pieces), sizes, image_shapes, self.box2box_transform.weights, self.box2box_transform.scale_clamp,
                 self.test_score_thresh, self.test_nms_thresh, self.test_topk_per_image)
         # More candidates in an image than the LDS pipeline holds (LVIS-style thresholds): csrc/detect_wide.hip takes any count.  The
@@ -525,7 +621,7 @@ class FastRCNNOutputLayers(nn.Module):
     def predict_probs(self, predictions, proposals):
         scores, _ = predictions
         num_inst_per_image = [len(p) for p in proposals]
-        probs = F.softmax(scores, dim=-1)
+        probs = torch.sigmoid(scores) if self.use_sigmoid_ce else F.softmax(scores, dim=-1)
         return probs.split(num_inst_per_image, dim=0)
 
 
@@ -541,12 +637,15 @@ class EmbeddingFastRCNNOutputLayers(FastRCNNOutputLayers):
                  loss_weight: Union[float, Dict[str, float]] = 1.0, emb_dim: int = 768,
                  embedding_based: bool = True, freeze_emb_pred: bool = True, normalize_emb: bool = False,
                  standardize_emb: bool = False, detach_cls_predictor: bool = False, sim_gemm_dtype: str = "fp32",
-                 fc_dtype: str = "fp32"):
+                 fc_dtype: str = "fp32", use_fed_loss: bool = False, use_sigmoid_ce: bool = False,
+                 get_fed_loss_cls_weights: Optional[Callable] = None, fed_loss_num_classes: int = 50):
         FastRCNNOutputLayers.__init__(
             self, input_shape, box2box_transform=box2box_transform, num_classes=num_classes,
             test_score_thresh=test_score_thresh, test_nms_thresh=test_nms_thresh,
             test_topk_per_image=test_topk_per_image, cls_agnostic_bbox_reg=cls_agnostic_bbox_reg,
-            smooth_l1_beta=smooth_l1_beta, box_reg_loss_type=box_reg_loss_type, loss_weight=loss_weight)
+            smooth_l1_beta=smooth_l1_beta, box_reg_loss_type=box_reg_loss_type, loss_weight=loss_weight,
+            use_fed_loss=use_fed_loss, use_sigmoid_ce=use_sigmoid_ce, get_fed_loss_cls_weights=get_fed_loss_cls_weights,
+            fed_loss_num_classes=fed_loss_num_classes)
         if isinstance(input_shape, int):
             input_shape = ShapeSpec(channels=input_shape)
         num_inputs = input_shape.channels * (input_shape.width or 1) * (input_shape.height or 1)
