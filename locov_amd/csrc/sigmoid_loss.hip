@@ -8,13 +8,10 @@
 //     than kept in LDS: 32 767 of them would take 128 KB, and a pass reads two floats per class.
 //   * locov_sigmoid_cls_loss -- [D2-upstream, unverified] FastRCNNOutputLayers.sigmoid_cross_entropy_loss together with the counts of
 //     _log_classification_stats, from ONE pass over the logits (a sigmoid needs no row maximum first): the loss terms, the gradient
-//     mask * (sigmoid - onehot) / R and the argmax of the row.  Launch structure of locov_cls_loss (cls_loss.hip): one wave per row,
-//     kSigRowsPerBlock rows per block, grid-stride over the row groups, one double partial per block, a finishing launch that adds the
-//     partials in block order.  No atomics there: the same inputs give the same bits, and a row's element -> lane assignment is the
-//     same with 16-byte loads and with scalar ones, so a column slice of a wider matrix gives the bits of its contiguous copy.
-#include "common.h"
-
-#include <cmath>
+//     mask * (sigmoid - onehot) / R and the argmax of the row.  The launch structure -- the row loop, the partials, the finishing launch,
+//     the host checks -- is the frame of cls_loss_common.h, shared with locov_cls_loss (cls_loss.hip); this file holds the sigmoid
+//     mathematics of one row and the rule for which rows count.
+#include "cls_loss_common.h"
 
 namespace locov {
 
@@ -26,13 +23,6 @@ constexpr int kFedThreads = 1024;
 constexpr int kFedWaves = kFedThreads / kWave;
 constexpr int kFedWords = (LOCOV_FED_LOSS_MAX_CLASSES + 1 + 31) / 32;   // presence bits of the classes 0..K (K: the background label)
 static_assert(kFedWords <= kFedThreads, "one bitmap word per thread");
-
-__device__ __forceinline__ int wave_sum_int(int v)
-{
-#pragma unroll
-    for (int s = kWave / 2; s > 0; s >>= 1) v += __shfl_xor(v, s, kWave);
-    return v;
-}
 
 // the sum of v over the block, in every thread (red: kFedWaves ints; safe to call back to back)
 __device__ __forceinline__ int fed_block_sum(int v, int *red)
@@ -158,84 +148,22 @@ __global__ __launch_bounds__(kFedThreads) void fed_loss_classes_kernel(const int
 
 namespace {
 
-constexpr int kSigRowsPerBlock = 4;
-constexpr int kSigThreads = kSigRowsPerBlock * kWave;
-constexpr int kSigMaxBlocks = 1024;
-constexpr int kSigFinishThreads = 256;
+struct SigmoidLoss {
+    const unsigned char *__restrict__ class_mask;                    // [K] or null: every class
+    double inv_r;                                                    // the gradient's 1 / R
 
-// what a block hands to the finishing launch (32 bytes)
-struct SigPartial {
-    double loss;                                                     // sum of the rows' loss terms
-    int n_fg, n_accurate, n_fg_accurate, n_false_negative, n_invalid, pad;
-};
+    // out of range (counted; upstream's index-put would fail); the sigmoid loss has no ignore index
+    __device__ __forceinline__ bool counts(int64_t y, int C) const { return y >= 0 && y <= C - 1; }
+    __device__ __forceinline__ bool invalid(int64_t) const { return true; }
 
-inline int sig_blocks(int64_t R)
-{
-    const int64_t groups = ceil_div(R, kSigRowsPerBlock);
-    return (int)(groups < kSigMaxBlocks ? groups : kSigMaxBlocks);
-}
-
-// elements [4 * chunk, 4 * chunk + 4) of a row of C logits; past the end: -inf (no weight in the maximum; the loss stops at K < C)
-template <bool VEC>
-__device__ __forceinline__ float4 load_chunk(const float *__restrict__ row, int chunk, int C)
-{
-    if constexpr (VEC) {
-        return reinterpret_cast<const float4 *>(row)[chunk];
-    } else {
-        const int c = chunk * 4;
-        float4 v;
-        v.x = row[c];                                                // (c < C: the caller's loop bound)
-        v.y = c + 1 < C ? row[c + 1] : -INFINITY;
-        v.z = c + 2 < C ? row[c + 2] : -INFINITY;
-        v.w = c + 3 < C ? row[c + 3] : -INFINITY;
-        return v;
-    }
-}
-
-template <bool VEC>
-__device__ __forceinline__ void store_chunk(float *__restrict__ row, int chunk, int C, float4 v)
-{
-    if constexpr (VEC) {
-        reinterpret_cast<float4 *>(row)[chunk] = v;
-    } else {
-        const int c = chunk * 4;
-        row[c] = v.x;
-        if (c + 1 < C) row[c + 1] = v.y;
-        if (c + 2 < C) row[c + 2] = v.z;
-        if (c + 3 < C) row[c + 3] = v.w;
-    }
-}
-
-}  // namespace
-
-template <bool VEC>
-__global__ __launch_bounds__(kSigThreads) void sigmoid_loss_rows_kernel(const float *__restrict__ scores, int64_t ld,
-                                                                        const int64_t *__restrict__ labels,
-                                                                        const unsigned char *__restrict__ class_mask, int64_t R, int C,
-                                                                        float *__restrict__ dscores, SigPartial *__restrict__ partials)
-{
-    __shared__ SigPartial red_p[kSigRowsPerBlock];
-    const int lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
-    const int K = C - 1, chunks = (C + 3) / 4;                       // K: the background column, which never enters the loss
-    const double inv_r = 1.0 / (double)R;
-
-    SigPartial acc = {0.0, 0, 0, 0, 0, 0, 0};                        // this wave's rows, in row order (every lane holds the same)
-    for (int64_t r = (int64_t)blockIdx.x * kSigRowsPerBlock + wave; r < R; r += (int64_t)gridDim.x * kSigRowsPerBlock) {
-        const int64_t y = labels[r];
-        float *drow = dscores ? dscores + r * (int64_t)C : nullptr;
-        if (y < 0 || y > K) {
-            // out of range (counted; upstream's index-put would fail): no loss terms, an exactly zero gradient, and no prediction
-            // can equal such a label, so the row's logits are not read
-            acc.n_invalid += 1;
-            if (drow)
-                for (int k = lane; k < chunks; k += kWave) store_chunk<VEC>(drow, k, C, make_float4(0.f, 0.f, 0.f, 0.f));
-            continue;
-        }
-        const float *row = scores + r * ld;
-        const int label = (int)y;                                    // (K: a background row, every target 0)
-
+    // (label K: a background row, every target 0)
+    template <bool VEC>
+    __device__ __forceinline__ double row_term(const float *__restrict__ row, float *__restrict__ drow, int label, int C, int lane,
+                                               int chunks, int &arg) const
+    {
+        const int K = C - 1;                                         // the background column, which never enters the loss
         float m = -INFINITY;
-        int arg = 0x7fffffff;
+        arg = 0x7fffffff;
         double sum = 0.0;                                            // this lane's terms, fp64 accumulation in a fixed order
         for (int k = lane; k < chunks; k += kWave) {
             const float4 v = load_chunk<VEC>(row, k, C);
@@ -260,84 +188,22 @@ __global__ __launch_bounds__(kSigThreads) void sigmoid_loss_rows_kernel(const fl
             }
             if (drow) store_chunk<VEC>(drow, k, C, make_float4(g[0], g[1], g[2], g[3]));
         }
+        wave_argmax(m, arg);
 #pragma unroll
-        for (int s = kWave / 2; s > 0; s >>= 1) {
-            const float om = __shfl_xor(m, s, kWave);
-            const int oa = __shfl_xor(arg, s, kWave);
-            if (om > m || (om == m && oa < arg)) {
-                m = om;
-                arg = oa;
-            }
-            sum += __shfl_xor(sum, s, kWave);
-        }
-
-        acc.loss += sum;
-        const bool fg = label < K, hit = arg == label;
-        acc.n_fg += fg ? 1 : 0;
-        acc.n_accurate += hit ? 1 : 0;
-        acc.n_fg_accurate += fg && hit ? 1 : 0;
-        acc.n_false_negative += fg && arg == K ? 1 : 0;
+        for (int s = kWave / 2; s > 0; s >>= 1) sum += __shfl_xor(sum, s, kWave);
+        return sum;
     }
+};
 
-    if (lane == 0) red_p[wave] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        SigPartial p = red_p[0];
-#pragma unroll
-        for (int w = 1; w < kSigRowsPerBlock; w++) {
-            p.loss += red_p[w].loss;
-            p.n_fg += red_p[w].n_fg;
-            p.n_accurate += red_p[w].n_accurate;
-            p.n_fg_accurate += red_p[w].n_fg_accurate;
-            p.n_false_negative += red_p[w].n_false_negative;
-            p.n_invalid += red_p[w].n_invalid;
-        }
-        partials[blockIdx.x] = p;
-    }
-}
+}  // namespace
 
-// one block: thread t adds partials t, t + 256, ... in that order, then a fixed tree
-__global__ __launch_bounds__(kSigFinishThreads) void sigmoid_loss_finish_kernel(const SigPartial *__restrict__ partials, int n_partials,
-                                                                                int64_t R, float *__restrict__ loss,
-                                                                                int64_t *__restrict__ stats)
+template <bool VEC>
+__global__ __launch_bounds__(kClsThreads) void sigmoid_loss_rows_kernel(const float *__restrict__ scores, int64_t ld,
+                                                                        const int64_t *__restrict__ labels,
+                                                                        const unsigned char *__restrict__ class_mask, int64_t R, int C,
+                                                                        float *__restrict__ dscores, ClsPartial *__restrict__ partials)
 {
-    __shared__ double red_loss[kSigFinishThreads];
-    __shared__ int64_t red_cnt[kSigFinishThreads][5];
-    const int t = threadIdx.x;
-    double l = 0.0;
-    int64_t c[5] = {0, 0, 0, 0, 0};
-    for (int i = t; i < n_partials; i += kSigFinishThreads) {
-        const SigPartial p = partials[i];
-        l += p.loss;
-        c[0] += p.n_fg;
-        c[1] += p.n_accurate;
-        c[2] += p.n_fg_accurate;
-        c[3] += p.n_false_negative;
-        c[4] += p.n_invalid;
-    }
-    red_loss[t] = l;
-#pragma unroll
-    for (int j = 0; j < 5; j++) red_cnt[t][j] = c[j];
-    __syncthreads();
-    for (int s = kSigFinishThreads / 2; s > 0; s >>= 1) {
-        if (t < s) {
-            red_loss[t] += red_loss[t + s];
-#pragma unroll
-            for (int j = 0; j < 5; j++) red_cnt[t][j] += red_cnt[t + s][j];
-        }
-        __syncthreads();
-    }
-    if (t == 0) {
-        loss[0] = R > 0 ? (float)(red_loss[0] / (double)R) : 0.f;   // the divisor is R, whatever the labels
-        if (stats) {
-            stats[0] = R;                                            // num_instances
-            stats[1] = red_cnt[0][0];                                // num_fg
-            stats[2] = red_cnt[0][1];                                // num_accurate
-            stats[3] = red_cnt[0][2];                                // fg_num_accurate
-            stats[4] = red_cnt[0][3];                                // num_false_negative
-            stats[5] = red_cnt[0][4];                                // num_invalid
-        }
-    }
+    cls_loss_rows<VEC>(SigmoidLoss{class_mask, 1.0 / (double)R}, scores, ld, labels, R, C, dscores, partials);
 }
 
 }  // namespace locov
@@ -357,33 +223,17 @@ extern "C" int locov_fed_loss_classes(const int64_t *gt_classes, int64_t R, cons
     return check_launch("locov_fed_loss_classes");
 }
 
-extern "C" int64_t locov_sigmoid_cls_loss_workspace_bytes(int64_t R)
-{
-    return R > 0 ? (int64_t)sig_blocks(R) * (int64_t)sizeof(SigPartial) : 0;
-}
+extern "C" int64_t locov_sigmoid_cls_loss_workspace_bytes(int64_t R) { return cls_workspace_bytes(R); }
 
 extern "C" int locov_sigmoid_cls_loss(const float *scores, int64_t ld, const int64_t *gt_classes, const unsigned char *class_mask, int64_t R,
                                       int C, void *workspace, int64_t workspace_bytes, float *loss, float *dscores, int64_t *stats,
                                       locov_stream_t stream)
 {
     LOCOV_REQUIRE(R >= 0 && C >= 2, "locov_sigmoid_cls_loss: R >= 0 and K = C - 1 >= 1 required (R %lld, C %d)", (long long)R, C);
-    LOCOV_REQUIRE(ld >= C, "locov_sigmoid_cls_loss: row stride ld %lld is smaller than C %d", (long long)ld, C);
-    LOCOV_REQUIRE(loss && (R == 0 || (scores && gt_classes)), "locov_sigmoid_cls_loss: null pointer");
-    LOCOV_REQUIRE(workspace_bytes >= locov_sigmoid_cls_loss_workspace_bytes(R) && (R == 0 || workspace),
-                  "locov_sigmoid_cls_loss: workspace too small (%lld bytes, %lld needed)", (long long)workspace_bytes,
-                  (long long)locov_sigmoid_cls_loss_workspace_bytes(R));
-    LOCOV_REQUIRE((uintptr_t)workspace % 8 == 0, "locov_sigmoid_cls_loss: workspace must be 8-byte aligned");
-    SigPartial *partials = static_cast<SigPartial *>(workspace);
-    const int blocks = R > 0 ? sig_blocks(R) : 0;
-    if (blocks > 0) {
-        // 16-byte loads and stores when every row of both matrices starts on a 16-byte boundary and holds whole chunks
-        const bool vec = C % 4 == 0 && ld % 4 == 0 && (uintptr_t)scores % 16 == 0 && (uintptr_t)dscores % 16 == 0;
-        hipLaunchKernelGGL(vec ? sigmoid_loss_rows_kernel<true> : sigmoid_loss_rows_kernel<false>, dim3(blocks), dim3(kSigThreads), 0,
-                           as_stream(stream), scores, ld, gt_classes, class_mask, R, C, dscores, partials);
-        const int rc = check_launch("locov_sigmoid_cls_loss (rows)");
-        if (rc != LOCOV_OK) return rc;
-    }
-    hipLaunchKernelGGL(sigmoid_loss_finish_kernel, dim3(1), dim3(kSigFinishThreads), 0, as_stream(stream), partials, blocks, R, loss,
-                       stats);
-    return check_launch("locov_sigmoid_cls_loss (finish)");
+    return cls_loss_launch<false>("locov_sigmoid_cls_loss", scores, ld, gt_classes, R, C, workspace, workspace_bytes, loss, dscores, stats,
+                                  stream, [&](bool vec, int blocks, ClsPartial *partials) {
+                                      hipLaunchKernelGGL(vec ? sigmoid_loss_rows_kernel<true> : sigmoid_loss_rows_kernel<false>,
+                                                         dim3(blocks), dim3(kClsThreads), 0, as_stream(stream), scores, ld, gt_classes,
+                                                         class_mask, R, C, dscores, partials);
+                                  });
 }

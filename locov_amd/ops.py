@@ -1695,8 +1695,11 @@ CLS_STATS = ("num_instances", "num_fg", "num_accurate", "fg_num_accurate", "num_
 
 
 class _ClsLossFn(torch.autograd.Function):
+    """locov_<name> for name in ("cls_loss", "sigmoid_cls_loss"): before_rc and after_rc are the entry's own arguments, which sit between
+    gt_classes and R and between C and the workspace."""
+
     @staticmethod
-    def forward(ctx, scores, gt_classes, ignore_index, want_stats):
+    def forward(ctx, scores, gt_classes, want_stats, name, before_rc, after_rc):
         R, C = scores.shape
         # a column block of a wider matrix is read in place (any row stride, any base alignment)
         if not (scores.stride(1) == 1 and scores.stride(0) >= C):
@@ -1707,10 +1710,11 @@ class _ClsLossFn(torch.autograd.Function):
         stats = torch.empty(len(CLS_STATS), dtype=torch.int64, device=dev) if want_stats else None
         dscores = torch.empty((R, C), dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
         lib = _lib.load()
-        ws = _workspace("cls_loss", scores, lib.locov_cls_loss_workspace_bytes(R))
+        ws = _workspace(name, scores, getattr(lib, f"locov_{name}_workspace_bytes")(R))
         with torch.cuda.device(dev):
-            check(lib.locov_cls_loss(scores.data_ptr(), scores.stride(0), cls.data_ptr(), R, C, ignore_index, ws.data_ptr(), ws.numel(),
-                                     loss.data_ptr(), _ptr(dscores), _ptr(stats), _stream(scores)), "locov_cls_loss")
+            check(getattr(lib, f"locov_{name}")(scores.data_ptr(), scores.stride(0), cls.data_ptr(), *before_rc, R, C, *after_rc,
+                                                ws.data_ptr(), ws.numel(), loss.data_ptr(), _ptr(dscores), _ptr(stats),
+                                                _stream(scores)), f"locov_{name}")
         ctx.dscores = dscores
         ctx.set_materialize_grads(False)                     # (no zeros for the statistics' "gradient")
         if stats is None:
@@ -1720,7 +1724,25 @@ class _ClsLossFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g, *_):
-        return (ctx.dscores * g if ctx.dscores is not None and g is not None else None), None, None, None
+        return (ctx.dscores * g if ctx.dscores is not None and g is not None else None), None, None, None, None, None
+
+
+def _check_cls_loss_args(fn: str, shapes: str, min_classes: int, scores, gt_classes, class_mask=None) -> None:
+    """The argument checks of cls_loss and sigmoid_cls_loss (class_mask [C - 1] uint8: the latter's, where given)."""
+    given = {"scores": scores, "gt_classes": gt_classes}
+    if class_mask is not None:
+        given["class_mask"] = class_mask
+    if not all(isinstance(t, torch.Tensor) for t in given.values()):
+        raise TypeError(f"{fn}: {', '.join(given)} must be torch.Tensors")
+    if not scores.is_cuda or any(t.device != scores.device for t in given.values()):
+        raise LocovError(f"{fn}: " + ", ".join(f"{n} on {t.device}" for n, t in given.items())
+                         + ": the kernel only runs on a ROCm GPU (there is no CPU fallback)")
+    dtypes = dict(zip(given, (torch.float32, torch.int64, torch.uint8)))
+    if any(t.dtype != dtypes[n] for n, t in given.items()):
+        raise TypeError(f"{fn}: " + ", ".join(f"{n} must be {dtypes[n]} (got {t.dtype})" for n, t in given.items()))
+    if scores.dim() != 2 or scores.shape[0] < 1 or scores.shape[1] < min_classes or tuple(gt_classes.shape) != (scores.shape[0],) \
+            or (class_mask is not None and tuple(class_mask.shape) != (scores.shape[1] - 1,)):
+        raise ValueError(f"{fn}: {shapes}, got " + ", ".join(str(tuple(t.shape)) for t in given.values()))
 
 
 def cls_loss(scores: torch.Tensor, gt_classes: torch.Tensor, ignore_index: int = -100,
@@ -1730,19 +1752,10 @@ def cls_loss(scores: torch.Tensor, gt_classes: torch.Tensor, ignore_index: int =
     scores [R, C] fp32 on the device (R > 0; rows may be a column block of a wider matrix), gt_classes [R] int64.  Returns
     (loss, stats): the 0-dim loss, differentiable in scores -- the gradient is made by the same pass, backward only multiplies it by
     the incoming gradient -- and the int64 [6] device tensor of CLS_STATS (None without want_stats).  Nothing is read to the host."""
-    if not isinstance(scores, torch.Tensor) or not isinstance(gt_classes, torch.Tensor):
-        raise TypeError("cls_loss: scores and gt_classes must be torch.Tensors")
-    if not scores.is_cuda or gt_classes.device != scores.device:
-        raise LocovError(f"cls_loss: scores are on {scores.device}, gt_classes on {gt_classes.device}: the kernel only runs on a ROCm GPU "
-                         "(there is no CPU fallback)")
-    if scores.dtype != torch.float32 or gt_classes.dtype != torch.int64:
-        raise TypeError(f"cls_loss: scores must be torch.float32 and gt_classes torch.int64, got {scores.dtype} and {gt_classes.dtype}")
-    if scores.dim() != 2 or scores.shape[0] < 1 or scores.shape[1] < 1 or tuple(gt_classes.shape) != (scores.shape[0],):
-        raise ValueError(f"cls_loss: scores [R, C] with R, C >= 1 and gt_classes [R], got {tuple(scores.shape)} and "
-                         f"{tuple(gt_classes.shape)}")
+    _check_cls_loss_args("cls_loss", "scores [R, C] with R, C >= 1 and gt_classes [R]", 1, scores, gt_classes)
     if not torch.is_grad_enabled():
         scores = scores.detach()                             # (no gradient buffer under no_grad)
-    res = _ClsLossFn.apply(scores, gt_classes, int(ignore_index), bool(want_stats))
+    res = _ClsLossFn.apply(scores, gt_classes, bool(want_stats), "cls_loss", (), (int(ignore_index),))
     return res if want_stats else (res, None)
 
 
@@ -1783,38 +1796,6 @@ def fed_loss_classes(gt_classes: torch.Tensor, weights: torch.Tensor, num_fed: i
     return mask, counts
 
 
-class _SigmoidClsLossFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, scores, gt_classes, class_mask, want_stats):
-        R, C = scores.shape
-        # a column block of a wider matrix is read in place (any row stride, any base alignment)
-        if not (scores.stride(1) == 1 and scores.stride(0) >= C):
-            scores = scores.contiguous()
-        cls = gt_classes if gt_classes.is_contiguous() else gt_classes.contiguous()
-        if class_mask is not None and not class_mask.is_contiguous():
-            class_mask = class_mask.contiguous()
-        dev = scores.device
-        loss = torch.empty((), dtype=torch.float32, device=dev)
-        stats = torch.empty(len(CLS_STATS), dtype=torch.int64, device=dev) if want_stats else None
-        dscores = torch.empty((R, C), dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
-        lib = _lib.load()
-        ws = _workspace("sigmoid_cls_loss", scores, lib.locov_sigmoid_cls_loss_workspace_bytes(R))
-        with torch.cuda.device(dev):
-            check(lib.locov_sigmoid_cls_loss(scores.data_ptr(), scores.stride(0), cls.data_ptr(), _ptr(class_mask), R, C, ws.data_ptr(),
-                                             ws.numel(), loss.data_ptr(), _ptr(dscores), _ptr(stats), _stream(scores)),
-                  "locov_sigmoid_cls_loss")
-        ctx.dscores = dscores
-        ctx.set_materialize_grads(False)                     # (no zeros for the statistics' "gradient")
-        if stats is None:
-            return loss
-        ctx.mark_non_differentiable(stats)
-        return loss, stats
-
-    @staticmethod
-    def backward(ctx, g, *_):
-        return (ctx.dscores * g if ctx.dscores is not None and g is not None else None), None, None, None
-
-
 def sigmoid_cls_loss(scores: torch.Tensor, gt_classes: torch.Tensor, class_mask: Optional[torch.Tensor] = None,
                      want_stats: bool = True) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """[D2-upstream, unverified] FastRCNNOutputLayers.sigmoid_cross_entropy_loss and the counts of _log_classification_stats from one
@@ -1823,23 +1804,12 @@ def sigmoid_cls_loss(scores: torch.Tensor, gt_classes: torch.Tensor, class_mask:
     mask) or None for every class.  Returns (loss, stats): the 0-dim sum of the masked per-class binary cross-entropies over R,
     differentiable in scores -- the gradient is made by the same pass, backward only multiplies it by the incoming gradient -- and the
     int64 [6] device tensor of CLS_STATS (None without want_stats).  Nothing is read to the host."""
-    if not isinstance(scores, torch.Tensor) or not isinstance(gt_classes, torch.Tensor) \
-            or not isinstance(class_mask, (torch.Tensor, type(None))):
-        raise TypeError("sigmoid_cls_loss: scores, gt_classes and class_mask must be torch.Tensors")
-    if not scores.is_cuda or gt_classes.device != scores.device or (class_mask is not None and class_mask.device != scores.device):
-        raise LocovError(f"sigmoid_cls_loss: scores are on {scores.device}, gt_classes on {gt_classes.device}"
-                         + (f", class_mask on {class_mask.device}" if class_mask is not None else "")
-                         + ": the kernel only runs on a ROCm GPU (there is no CPU fallback)")
-    if scores.dtype != torch.float32 or gt_classes.dtype != torch.int64 or (class_mask is not None and class_mask.dtype != torch.uint8):
-        raise TypeError(f"sigmoid_cls_loss: scores must be torch.float32, gt_classes torch.int64 and class_mask torch.uint8, got "
-                        f"{scores.dtype}, {gt_classes.dtype} and {None if class_mask is None else class_mask.dtype}")
-    if scores.dim() != 2 or scores.shape[0] < 1 or scores.shape[1] < 2 or tuple(gt_classes.shape) != (scores.shape[0],) \
-            or (class_mask is not None and tuple(class_mask.shape) != (scores.shape[1] - 1,)):
-        raise ValueError(f"sigmoid_cls_loss: scores [R, K + 1] with R, K >= 1, gt_classes [R] and class_mask [K], got "
-                         f"{tuple(scores.shape)}, {tuple(gt_classes.shape)} and {None if class_mask is None else tuple(class_mask.shape)}")
+    _check_cls_loss_args("sigmoid_cls_loss", "scores [R, K + 1] with R, K >= 1, gt_classes [R] and class_mask [K]", 2, scores, gt_classes,
+                         class_mask)
     if not torch.is_grad_enabled():
         scores = scores.detach()                             # (no gradient buffer under no_grad)
-    res = _SigmoidClsLossFn.apply(scores, gt_classes, class_mask, bool(want_stats))
+    mask = class_mask if class_mask is None or class_mask.is_contiguous() else class_mask.contiguous()
+    res = _ClsLossFn.apply(scores, gt_classes, bool(want_stats), "sigmoid_cls_loss", (_ptr(mask),), ())
     return res if want_stats else (res, None)
 
 

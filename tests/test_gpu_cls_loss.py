@@ -24,7 +24,7 @@ pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 IGNORE = -100
-SHAPES = [(1, 1), (3, 1), (5, 1), (1, 2), (3, 2), (5, 2), (3, 65), (257, 49), (257, 81), (1536, 1204)]
+SHAPES = [(1, 1), (3, 1), (5, 1), (1, 2), (3, 2), (5, 2), (3, 65), (257, 49), (257, 81), (1536, 1204), (4099, 3), (4099, 4)]
 
 
 @pytest.fixture(scope="module")
@@ -164,9 +164,10 @@ def test_hand_built_ties_background_rows_and_an_out_of_range_label(ops):
     assert bp.classification_stats() == {"cls_accuracy": 3 / 6, "fg_cls_accuracy": 1 / 3, "false_negative": 1 / 3}
 
 
-@pytest.mark.parametrize("R,C", [(5, 2), (257, 81), (1536, 1204)])
+@pytest.mark.parametrize("R,C", [(5, 2), (257, 81), (1536, 1204), (4099, 4)])
 def test_column_slice_of_a_wider_matrix_gives_the_bits_of_its_copy(ops, R, C):
-    """ld > C and a base that is 4 bytes past a 16-byte boundary: scalar loads, against the contiguous copy (16-byte loads at C = 1204)."""
+    """ld > C and a base that is 4 bytes past a 16-byte boundary: scalar loads, against the contiguous copy (16-byte loads at C = 1204
+    and C = 4; at R = 4099 there are more row groups than blocks, so a wave takes a second row)."""
     c = _case(R, C)
     wide = torch.randn(R, C + 7, generator=torch.Generator().manual_seed(5)).cuda()
     wide[:, 1:1 + C] = c["scores"].cuda()
@@ -224,7 +225,7 @@ def test_no_gradient_buffer_without_requires_grad_and_null_stats(ops):
     assert none is None and torch.equal(loss, ref) and x.grad is not None
 
 
-@pytest.mark.parametrize("R,C", [(257, 81), (1536, 1204)])
+@pytest.mark.parametrize("R,C", [(257, 81), (1536, 1204), (4099, 4)])
 def test_two_calls_give_the_same_bits(ops, R, C):
     c = _case(R, C)
     outs = []

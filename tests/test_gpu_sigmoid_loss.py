@@ -29,7 +29,7 @@ pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INVALID = -100
-SHAPES = [(1, 2), (3, 2), (5, 66), (257, 49), (257, 81), (1536, 1204)]
+SHAPES = [(1, 2), (3, 2), (5, 66), (257, 49), (257, 81), (1536, 1204), (4099, 3), (4099, 4)]
 
 
 @pytest.fixture(scope="module")
@@ -165,9 +165,10 @@ def test_backward_scales_by_the_incoming_gradient(ops):
     assert torch.equal(s.grad, s2.grad * 0.25)                        # (a power of two: exact)
 
 
-@pytest.mark.parametrize("R,C", [(5, 2), (257, 81), (1536, 1204)])
+@pytest.mark.parametrize("R,C", [(5, 2), (257, 81), (1536, 1204), (4099, 4)])
 def test_column_slice_of_a_wider_matrix_gives_the_bits_of_its_copy(ops, R, C):
-    """ld > C and a base that is 4 bytes past a 16-byte boundary: scalar loads, against the contiguous copy (16-byte loads at C = 1204)."""
+    """ld > C and a base that is 4 bytes past a 16-byte boundary: scalar loads, against the contiguous copy (16-byte loads at C = 1204
+    and C = 4; at R = 4099 there are more row groups than blocks, so a wave takes a second row)."""
     c = _case(R, C, True)
     wide = torch.randn(R, C + 7, generator=torch.Generator().manual_seed(5)).cuda()
     wide[:, 1:1 + C] = c["scores"].cuda()
@@ -181,7 +182,7 @@ def test_column_slice_of_a_wider_matrix_gives_the_bits_of_its_copy(ops, R, C):
     assert view.grad.is_contiguous() and torch.equal(view.grad, s.grad)
 
 
-@pytest.mark.parametrize("R,C", [(257, 81), (1536, 1204)])
+@pytest.mark.parametrize("R,C", [(257, 81), (1536, 1204), (4099, 4)])
 def test_two_calls_give_the_same_bits(ops, R, C):
     c = _case(R, C, True)
     outs = []
