@@ -1062,10 +1062,15 @@ __global__ __launch_bounds__(256, 3) void roi_align_even_bwd_tiles_kernel(const 
                 const float *roi = rois + (int64_t)r * 5;
                 if ((int)roi[0] == img) {
                     const Geo g = geometry(roi);
-                    const float y_lo = g.start_h - 2.f, y_hi = g.start_h + g.bin_h * (float)PH + 2.f;
-                    const float x_lo = g.start_w - 2.f, x_hi = g.start_w + g.bin_w * (float)PW + 2.f;
+                    // a, b: the box's two edges on an axis.  An inverted box under a fixed sampling ratio has a NEGATIVE bin size: its samples
+                    // run from the start BACK to the end, so the footprint is [min, max] of the two, not [a, b].
                     // (NaN coordinates fail every comparison: such a proposal contributes nothing here, as its samples are invalid there)
-                    ok = y_hi >= (float)ty0 && y_lo <= (float)(ty0 + kBT) && x_hi >= (float)tx0 && x_lo <= (float)(tx0 + kBT) && g.gh > 0 && g.gw > 0;
+                    auto reaches = [](float a, float b, int t0) {
+                        const float lo = a <= b ? a : b, hi = a <= b ? b : a;
+                        return hi + 2.f >= (float)t0 && lo - 2.f <= (float)(t0 + kBT);
+                    };
+                    ok = reaches(g.start_h, g.start_h + g.bin_h * (float)PH, ty0) && reaches(g.start_w, g.start_w + g.bin_w * (float)PW, tx0) &&
+                         g.gh > 0 && g.gw > 0;
                 }
             }
             const unsigned long long b = __ballot(ok);
