@@ -29,6 +29,8 @@ CXXFLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-fno-gpu-rd
 FILE_FLAGS = {
     "roi_align.hip": ["-ffp-contract=off"],
     "roi_align_nhwc.hip": ["-ffp-contract=off"],
+    "roi_align_nhwc_bwd.hip": ["-ffp-contract=off"],
+    "roi_align_contract.hip": ["-ffp-contract=off"],
     "roi_align_tiles.hip": ["-ffp-contract=off"],
     "label.hip": ["-ffp-contract=off"],          # (IoU values must be the torch ops', rounded step by step)
     "losses.hip": ["-ffp-contract=off"],         # (box deltas / log-softmax pieces as the torch ops form them)

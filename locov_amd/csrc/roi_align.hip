@@ -11,7 +11,7 @@
 // CT*ph*pw floats, so lanes write consecutive addresses (the kernel is HBM-write-bound:
 // 0.80 MB per proposal at C=1024, P=14).  Coordinates and weights use un-fused fp32
 // (FMA contraction off), which makes the result bit-identical to the oracle.
-#include "common.h"
+#include "roi_align_common.h"
 
 // The oracle defines un-fused fp32 arithmetic; HIP's __f*_rn helpers are plain operators and
 // would be contracted to FMA, so contraction is switched off for this whole file.
@@ -37,11 +37,6 @@ struct LevelTable {
 struct AxisSample {
     int lo, hi;   // element offsets (already multiplied by W on the y axis)
     float wl, wh; // weight of the high tap (l = frac) and of the low tap (h = 1 - frac)
-};
-
-struct RoiGeom {
-    float start_h, start_w, bin_h, bin_w, count;
-    int grid_h, grid_w;
 };
 
 // One axis sample exactly as torchvision's bilinear pre-calc does it (see oracle_precalc).
@@ -70,31 +65,6 @@ __device__ __forceinline__ AxisSample axis_sample(float start, float bin, int p,
     return s;
 }
 
-__device__ __forceinline__ RoiGeom roi_geom(const float *roi, float scale, int ph, int pw, int sampling_ratio,
-                                            int aligned)
-{
-    RoiGeom g;
-    const float off = aligned ? 0.5f : 0.0f;
-    g.start_w = f_sub(f_mul(roi[1], scale), off);
-    g.start_h = f_sub(f_mul(roi[2], scale), off);
-    const float end_w = f_sub(f_mul(roi[3], scale), off);
-    const float end_h = f_sub(f_mul(roi[4], scale), off);
-    float rw = f_sub(end_w, g.start_w), rh = f_sub(end_h, g.start_h);
-    if (!aligned) {
-        rw = fmaxf(rw, 1.f);
-        rh = fmaxf(rh, 1.f);
-    }
-    g.bin_h = f_div(rh, (float)ph);
-    g.bin_w = f_div(rw, (float)pw);
-    int gh = sampling_ratio > 0 ? sampling_ratio : (int)ceilf(g.bin_h);
-    int gw = sampling_ratio > 0 ? sampling_ratio : (int)ceilf(g.bin_w);
-    const int prod = gh * gw;
-    g.count = (float)(prod > 1 ? prod : 1);
-    g.grid_h = gh > 0 ? gh : 0;
-    g.grid_w = gw > 0 ? gw : 0;
-    return g;
-}
-
 constexpr int kRoiThreads = 256;
 constexpr int kMaxAxisEntries = 1024;  // per axis; 2 * 1024 * 16 B = 32 KiB LDS
 
@@ -117,6 +87,8 @@ __global__ __launch_bounds__(kRoiThreads) void roi_align_nchw_kernel(
     const LevelDesc L = levels.lv[(lvl >= 0 && lvl < num_levels) ? lvl : 0];
     const int b = (int)roi[0];
     RoiGeom g = roi_geom(roi, L.scale, PH, PW, sampling_ratio, aligned);
+    g.grid_h = g.grid_h > 0 ? g.grid_h : 0;                 // (a negative bin size: no samples)
+    g.grid_w = g.grid_w > 0 ? g.grid_w : 0;
     if (b < 0 || b >= N || lvl < 0 || lvl >= num_levels) {  // bad batch / level index: no samples -> zeros
         g.grid_h = 0;
         g.grid_w = 0;

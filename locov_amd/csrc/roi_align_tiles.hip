@@ -1,7 +1,7 @@
 // The pooler contract ([R,C,ph,pw] fp32 out of an NCHW map; roi_emb_heads.py:182-187,243-245) with LDS-STAGED PROPOSAL TILES:
 // mode LOCOV_ROIALIGN_FAST of locov_roi_align_from_nhwc_fwd_ex, results within 1e-5 of the exact form (SURVEY.md 8d's gate).
 //
-// The exact form (roi_align_nhwc.hip) issues one 16-byte lane load per bilinear tap and channel quad, in torchvision's sample
+// The exact form (roi_align_contract.hip) issues one 16-byte lane load per bilinear tap and channel quad, in torchvision's sample
 // order; what bounds it is the chain load -> wait -> accumulate, seven times per workgroup for a small box and up to 36 taps
 // deep per bin for a large one, at 4 workgroups per CU -- not HBM (2 TB/s of output for a 6 TB/s write roof).  Here:
 //
@@ -135,19 +135,10 @@ __global__ __launch_bounds__(64) void roi_plan_kernel(const float *__restrict__ 
     const float *roi = rois + r * 5;
     RoiPlan &pl = plans[r];
     const int b = (int)roi[0];
-    const float off = aligned ? 0.5f : 0.0f;
-    const float start_w = __fsub_rn(__fmul_rn(roi[1], scale), off), start_h = __fsub_rn(__fmul_rn(roi[2], scale), off);
-    const float end_w = __fsub_rn(__fmul_rn(roi[3], scale), off), end_h = __fsub_rn(__fmul_rn(roi[4], scale), off);
-    float rw = __fsub_rn(end_w, start_w), rh = __fsub_rn(end_h, start_h);
-    if (!aligned) {
-        rw = fmaxf(rw, 1.f);
-        rh = fmaxf(rh, 1.f);
-    }
-    const float bin_h = __fdiv_rn(rh, (float)PH), bin_w = __fdiv_rn(rw, (float)PW);
-    const int gh = sampling_ratio > 0 ? sampling_ratio : (int)ceilf(bin_h);
-    const int gw = sampling_ratio > 0 ? sampling_ratio : (int)ceilf(bin_w);
-    const int prod = gh * gw;
-    pl.inv_count = 1.f / (float)(prod > 1 ? prod : 1);
+    const RoiGeom g = roi_geom(roi, scale, PH, PW, sampling_ratio, aligned);
+    const float start_h = g.start_h, start_w = g.start_w, bin_h = g.bin_h, bin_w = g.bin_w;
+    const int gh = g.grid_h, gw = g.grid_w;            // RAW: a negative grid makes the plan refuse the proposal (`ok` below)
+    pl.inv_count = 1.f / g.count;
     pl.batch = (b >= 0 && b < N) ? b : -1;
     pl.pad[0] = pl.pad[1] = pl.pad[2] = 0;
     __shared__ PlanScratch ps;
@@ -313,21 +304,9 @@ __global__ __launch_bounds__(kTlThreads) void roi_align_tiles_kernel(const float
         // The exact arithmetic for a ROI the plan does not cover (and zeros for an invalid batch index): torchvision's order,
         // un-fused, samples computed on the fly -- rare by construction, so no tables.
         const float *roi = rois + r * 5;
-        const float off = aligned ? 0.5f : 0.0f;
-        const float start_w = roi[1] * scale - off, start_h = roi[2] * scale - off;
-        const float end_w = roi[3] * scale - off, end_h = roi[4] * scale - off;
-        float rw = end_w - start_w, rh = end_h - start_h;
-        if (!aligned) {
-            rw = fmaxf(rw, 1.f);
-            rh = fmaxf(rh, 1.f);
-        }
-        const float bin_h = rh / (float)PH, bin_w = rw / (float)PW;
-        int gh = sampling_ratio > 0 ? sampling_ratio : (int)ceilf(bin_h);
-        int gw = sampling_ratio > 0 ? sampling_ratio : (int)ceilf(bin_w);
-        const int prod = gh * gw;
-        const float count = (float)(prod > 1 ? prod : 1);
-        gh = (gh > 0 && batch >= 0) ? gh : 0;
-        gw = (gw > 0 && batch >= 0) ? gw : 0;
+        const RoiGeom g = roi_geom(roi, scale, PH, PW, sampling_ratio, aligned);
+        const float start_h = g.start_h, start_w = g.start_w, bin_h = g.bin_h, bin_w = g.bin_w, count = g.count;
+        const int gh = (g.grid_h > 0 && batch >= 0) ? g.grid_h : 0, gw = (g.grid_w > 0 && batch >= 0) ? g.grid_w : 0;
         const unsigned ch_off = (unsigned)(c_ok ? cq : 0) * (unsigned)sizeof(float);
         for (int g0 = 0; g0 < bins; g0 += kTlThreads / kTlQN) {
             const int bin = g0 + wave * (64 / kTlQN) + sub;

@@ -9,7 +9,7 @@ import numpy as np
 
 import roi_align_ref as ref
 
-# thresholds of locov_amd/csrc/roi_align_nhwc.hip
+# thresholds of locov_amd/csrc/roi_align_nhwc_common.h and roi_align_nhwc_bwd.hip
 K_SEP_GRID = 16          # kSepGrid: a larger grid on either axis leaves the separable form
 K_MAX_AXIS = 192         # kMaxAxisN: OH * gh or OW * gw beyond it -> weights computed on the fly
 K_NCHW_AXIS = 1024       # kMaxAxisEntries of roi_align.hip: the NCHW kernel's per-axis tables
@@ -104,7 +104,7 @@ def footprint(case, row):
 
 
 def separable_build(case, row):
-    """The scatter kernel's separable build for roi `row`, mirrored from the reference's taps (roi_align_nhwc.hip, the `sep_try` block):
+    """The scatter kernel's separable build for roi `row`, mirrored from the reference's taps (roi_align_nhwc_common.h, the `sep_try` block of nhwc_roi_frame):
     per axis and bin, base = the lowest low tap among the bin's valid samples, and the build BAILS OUT when some valid sample's high
     tap lies more than `grid` pixels past base (the bin's per-pixel weights then do not fit grid + 1 entries).  Returns
     (bails, rows, columns): the size of the pixel rectangle the kernel derives from the build -- base .. base + highest tap offset

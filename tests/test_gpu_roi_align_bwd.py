@@ -1,7 +1,7 @@
 """The ROIAlign backward kernels outside the one default pooler configuration, against a float64 reference of the operation
 (tests/roi_align_ref.py) on the whole output, all channels.  The inputs live in tests/roi_align_bwd_cases.py:
 
-  channels-last entry (locov_roi_align_nhwc_bwd, locov_amd/csrc/roi_align_nhwc.hip)
+  channels-last entry (locov_roi_align_nhwc_bwd, locov_amd/csrc/roi_align_nhwc_bwd.hip)
     ownership kernel  (P, bin_stride) x aligned x sampling_ratio x scale pairwise, maps inside one tile / exactly one tile / one pixel
                       into the next tile / several tiles, C = 128 and 256, gradient rows that are a column block of a wider matrix,
                       R = 1 / 257 / 2100 (a second pass of the 2048-entry list), boxes with an edge within 2.5 px of a tile boundary,

@@ -1,5 +1,5 @@
 """Developer aid: the even-grid ROIAlign backward by tile ownership against the scatter form as the number of proposals
-grows (the ownership form's workgroups scan ALL proposals for the ones that reach their tile).  usage: python3 tools/ab_pool_bwd_large_r.py"""
+grows (the ownership form's workgroups scan ALL proposals for the ones that reach their tile; both kernels: csrc/roi_align_nhwc_bwd.hip).  usage: python3 tools/ab_pool_bwd_large_r.py"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np

@@ -1,5 +1,6 @@
 """Developer aid (round 5): the even-grid ROIAlign BACKWARD (fp32 atomics into the channels-last map gradient; 800 sampled proposals of ONE size class, 4 images,
-1024 channels = the LSM step's launch) per proposal size class -- where its 0.8 ms goes."""
+1024 channels = the LSM step's launch) per proposal size class -- where its 0.8 ms goes.  The kernels are those of csrc/roi_align_nhwc_bwd.hip
+(LOCOV_POOL_BWD_TILES=0: the scatter kernel; unset: the ownership kernel); LOCOV_HIP_LIB selects another build of them."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch

@@ -1,5 +1,5 @@
 """Developer aid (round 4): the pooler-contract ROIAlign (NCHW in, [R,1024,14,14] out) on the bench's 8 x 1000 proposals -- ms per call
-(incl. the 0.07 ms channels-last copy of the map); LOCOV_HIP_LIB selects a store-policy variant."""
+(incl. the 0.07 ms channels-last copy of the map); LOCOV_HIP_LIB selects a store-policy variant (tools/make_variant.py <tag> roi_align_contract.hip -DLOCOV_T2_...)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
