@@ -477,6 +477,38 @@ int locov_box_reg_loss(const float *proposal_boxes, const float *gt_boxes, const
                        float smooth_l1_beta, float *loss, float *dpred, locov_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * a-11  the IoU forms of that loss -- BBOX_REG_LOSS_TYPE "giou", "diou", "ciou" -- in ONE launch.  Replaces the torch-op chain of
+ * [D2-upstream] FastRCNNOutputLayers.box_reg_loss for a loss type other than "smooth_l1" (the reference imports fvcore's giou_loss and
+ * documents the key as `One of: "smooth_l1", "giou"`: ovr/modeling/roi_heads/box_emb_head.py:5,102,165 and
+ * box_emb_grounding_head.py:5,305,374; [D2-upstream] _dense_box_regression_loss also takes "diou" and "ciou"): for the foreground
+ * rows (0 <= gt_classes < num_classes) Box2BoxTransform.apply_deltas of the row's four predicted deltas (per-class predictions: the
+ * four columns of the row's class) onto its proposal -- d / weight, dw and dh clamped to at most scale_clamp, centre = dx * W + cx,
+ * size = exp(dw) * W -- then, against the matched ground-truth box with eps = 1e-7 ([fvcore, unverified]):
+ *   inter = (min x2 - max x1) * (min y2 - max y1) where both factors are > 0 (strictly), else 0;  union = area_p + area_g - inter;
+ *   iou = inter / (union + eps);  (cw, ch) and area_c: the smallest enclosing box
+ *     LOCOV_BOX_IOU_GIOU  1 - (iou - (area_c - union) / (area_c + eps))
+ *     LOCOV_BOX_IOU_DIOU  1 - iou + dist / (cw^2 + ch^2 + eps), dist = the squared distance of the centres ((x1 + x2) / 2, (y1 + y2) / 2)
+ *     LOCOV_BOX_IOU_CIOU  diou + alpha * v, v = 4 / pi^2 (atan(wg / hg) - atan(w / h))^2, alpha = v / (1 - iou + v + eps) held constant
+ *                         in the gradient (fvcore forms it under no_grad)
+ * summed over the foreground rows in a fixed order and divided by max(R, 1) -- the smooth-L1 form's normalisation -- and
+ * d loss / d pred_deltas from the same launch: a delta above the clamp gets exactly zero (torch.clamp: equality passes the gradient),
+ * equal arguments of a max / min share the gradient half and half (torch.max / torch.min of two tensors), nothing flows through an
+ * intersection that is masked out.  The row's arithmetic is fp64 from the fp32 inputs; the loss and each gradient entry are rounded
+ * to fp32 once.  One workgroup, no atomics: the same inputs give the same bits.  No allocation, no synchronisation.
+ *   Arguments as locov_box_reg_loss: proposal_boxes / gt_boxes [R, 4] XYXY fp32 (16-byte aligned), pred_deltas [R, ld] with ld = 4 or
+ *   4 * num_classes, gt_classes [R] int64; loss [1]; dpred [R, ld] or NULL: written completely when ld == 4 (zeros in background /
+ *   ignored rows), otherwise only the four columns of a foreground row's class (the caller zeroes it).  scale_clamp is a double
+ *   (Box2BoxTransform's log(1000 / 16) is no fp32 number).  Background and ignored rows' predictions are never read: an inf or NaN
+ *   there reaches neither the value nor the gradient.  Foreground proposals must have positive width and height.  R == 0: loss = 0.
+ * ------------------------------------------------------------------------------------- */
+#define LOCOV_BOX_IOU_GIOU 0
+#define LOCOV_BOX_IOU_DIOU 1
+#define LOCOV_BOX_IOU_CIOU 2
+int locov_box_iou_loss(const float *proposal_boxes, const float *gt_boxes, const float *pred_deltas, int64_t ld,
+                       const int64_t *gt_classes, int64_t R, int64_t num_classes, float wx, float wy, float ww, float wh,
+                       double scale_clamp, int kind, float *loss, float *dpred, locov_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * a-11  the classification loss of the training heads and its training statistics from ONE pass over the logits.  Replaces the
  * torch-op chain of [D2-upstream] FastRCNNOutputLayers.losses' `cross_entropy(scores, gt_classes, reduction="mean")`, which the
  * reference's predictors inherit (ovr/modeling/roi_heads/box_emb_head.py:60 and box_emb_grounding_head.py:259: both subclass

@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import c_char_p, c_float, c_int, c_int64, c_uint, c_void_p, POINTER
+from ctypes import c_char_p, c_double, c_float,c_int, c_int64, c_uint, c_void_p, POINTER
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # LOCOV_HIP_LIB: developer override to A/B an experimental build of the same ABI (tools/)
@@ -30,6 +30,7 @@ ABI_VERSION = 8
 DETECT_MAX_CANDIDATES, DETECT_FLAG_NONFINITE, DETECT_FLAG_OVERFLOW = 8192, 1, 2
 FED_LOSS_MAX_CLASSES = 32767
 DISTILL_KD, DISTILL_JS, DISTILL_MSE, DISTILL_MAX_B = 0, 1, 2, 64
+BOX_IOU_GIOU, BOX_IOU_DIOU, BOX_IOU_CIOU = 0, 1, 2
 REGIONS_MAX_B, REGIONS_MAX_CANDIDATES = 64, 4096
 REGIONS_GRID, REGIONS_GRID_ALL, REGIONS_BOXES = 0, 1, 2
 REGIONS_ROWS, REGIONS_NCHW = 0, 1
@@ -93,6 +94,8 @@ SIGNATURES = {
     "locov_sample_proposals": (c_int, [_p, _p, _p, _p, _p, _p, _p, _p, POINTER(c_int), POINTER(c_int), c_int, c_int, c_int, c_int64,
                                        _p, _p, _p, _p, _p, _p, _p, _p]),
     "locov_box_reg_loss": (c_int, [_p, _p, _p, c_int64, _p, c_int64, c_int64, c_float, c_float, c_float, c_float, c_float, _p, _p, _p]),
+    "locov_box_iou_loss": (c_int, [_p, _p, _p, c_int64, _p, c_int64, c_int64, c_float, c_float, c_float, c_float, c_double, c_int, _p, _p,
+                                   _p]),
     "locov_cls_loss_workspace_bytes": (c_int64, [c_int64]),
     "locov_cls_loss": (c_int, [_p, c_int64, _p, c_int64, c_int, c_int64, _p, c_int64, _p, _p, _p, _p]),
     "locov_fed_loss_classes": (c_int, [_p, c_int64, _p, _p, c_int, c_int, _p, _p, _p]),

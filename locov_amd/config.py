@@ -107,7 +107,7 @@ def get_cfg() -> CfgNode:
                 "POOLER_SAMPLING_RATIO": 0,                        # [D2-upstream]
                 "CLS_AGNOSTIC_BBOX_REG": False,                    # coco_lsm.yaml:36 -> True
                 "BBOX_REG_WEIGHTS": (10.0, 10.0, 5.0, 5.0),        # [D2-upstream]
-                "BBOX_REG_LOSS_TYPE": "smooth_l1",                 # [D2-upstream]
+                "BBOX_REG_LOSS_TYPE": "smooth_l1",                 # [D2-upstream] "smooth_l1", "giou", "diou" or "ciou"
                 "BBOX_REG_LOSS_WEIGHT": 1.0,                       # [D2-upstream]
                 "SMOOTH_L1_BETA": 0.0,                             # [D2-upstream]
                 "USE_SIGMOID_CE": False,                           # [D2-upstream] per-class sigmoid cross-entropy instead of the softmax

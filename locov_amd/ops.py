@@ -1691,6 +1691,50 @@ def box_reg_loss(pred_deltas: torch.Tensor, proposal_boxes: torch.Tensor, gt_box
     return _BoxRegLossFn.apply(pred_deltas.float(), proposal_boxes, gt_boxes, gt_classes, num_classes, tuple(weights), smooth_l1_beta)
 
 
+BOX_IOU_KINDS = {"giou": _lib.BOX_IOU_GIOU, "diou": _lib.BOX_IOU_DIOU, "ciou": _lib.BOX_IOU_CIOU}
+
+
+class _BoxIouLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, proposal_boxes, gt_boxes, gt_classes, num_classes, weights, scale_clamp, kind):
+        pred = _dev(pred, "pred_deltas")
+        pb, gb = _dev(proposal_boxes.detach().float(), "proposal_boxes"), _dev(gt_boxes.detach().float(), "gt_boxes")
+        cls = _dev(gt_classes, "gt_classes", torch.int64)
+        R, ld = pred.shape
+        loss = torch.empty(1, dtype=torch.float32, device=pred.device)
+        need = ctx.needs_input_grad[0]
+        dpred = None
+        if need:
+            dpred = torch.empty_like(pred) if ld == 4 else torch.zeros_like(pred)
+        with torch.cuda.device(pred.device):
+            check(_lib.load().locov_box_iou_loss(_ptr(pb), _ptr(gb), _ptr(pred), ld, _ptr(cls), R, int(num_classes),
+                                                 *(float(w) for w in weights), float(scale_clamp), kind, _ptr(loss), _ptr(dpred),
+                                                 _stream(pred)),
+                  "locov_box_iou_loss")
+        ctx.dpred = dpred
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        return (ctx.dpred * g if ctx.dpred is not None else None), None, None, None, None, None, None, None
+
+
+def box_iou_loss(pred_deltas: torch.Tensor, proposal_boxes: torch.Tensor, gt_boxes: torch.Tensor, gt_classes: torch.Tensor,
+                 num_classes: int, weights, scale_clamp: float, kind: str) -> torch.Tensor:
+    """[D2-upstream] FastRCNNOutputLayers.box_reg_loss ("giou" / "diou" / "ciou") in one launch: apply_deltas (weights, scale_clamp) of
+    the foreground rows' (0 <= gt_classes < num_classes) predictions pred_deltas [R, 4] or [R, 4 * num_classes] onto their proposals,
+    [fvcore, unverified] giou_loss / diou_loss / ciou_loss against gt_boxes, sum / max(R, 1).  The foreground boxes must already be
+    known to have positive width and height.  Differentiable in pred_deltas."""
+    if kind not in BOX_IOU_KINDS:
+        raise ValueError(f"box_iou_loss: unknown kind {kind!r} (one of {sorted(BOX_IOU_KINDS)})")
+    R = pred_deltas.shape[0]
+    if pred_deltas.dim() != 2 or pred_deltas.shape[1] not in (4, 4 * num_classes) or tuple(proposal_boxes.shape) != (R, 4) \
+            or tuple(gt_boxes.shape) != (R, 4) or tuple(gt_classes.shape) != (R,) or gt_classes.dtype != torch.int64:
+        raise ValueError("box_iou_loss: pred_deltas [R, 4 | 4K], boxes [R, 4], gt_classes [R] int64")
+    return _BoxIouLossFn.apply(pred_deltas.float(), proposal_boxes, gt_boxes, gt_classes, num_classes, tuple(weights), float(scale_clamp),
+                               BOX_IOU_KINDS[kind])
+
+
 CLS_STATS = ("num_instances", "num_fg", "num_accurate", "fg_num_accurate", "num_false_negative", "num_invalid")
 
 

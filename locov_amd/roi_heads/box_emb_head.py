@@ -288,6 +288,76 @@ def smooth_l1_loss(input: torch.Tensor, target: torch.Tensor, beta: float, reduc
     return loss
 
 
+def _reduce_box_loss(loss: torch.Tensor, reduction: str) -> torch.Tensor:
+    if reduction == "mean":
+        return loss.mean() if loss.numel() > 0 else 0.0 * loss.sum()
+    if reduction == "sum":
+        return loss.sum()
+    return loss
+
+
+def _iou_pieces(boxes1: torch.Tensor, boxes2: torch.Tensor, eps: float, check: bool):
+    """What fvcore's three IoU losses share: the corners, intersection over (union + eps), the union and the smallest enclosing
+    box's corners.  The intersection is selected by its mask (`intsct[mask] = ...` upstream: the same values and the same gradients --
+    nothing flows through a masked-out intersection -- without the index list, whose length is a host read).  check: fvcore's
+    `assert (x2 >= x1).all()`, a host read."""
+    x1, y1, x2, y2 = boxes1.unbind(dim=-1)
+    x1g, y1g, x2g, y2g = boxes2.unbind(dim=-1)
+    if check:
+        assert bool((x2 >= x1).all()), "bad box: x1 larger than x2"
+        assert bool((y2 >= y1).all()), "bad box: y1 larger than y2"
+    xkis1 = torch.max(x1, x1g)
+    ykis1 = torch.max(y1, y1g)
+    xkis2 = torch.min(x2, x2g)
+    ykis2 = torch.min(y2, y2g)
+    mask = (ykis2 > ykis1) & (xkis2 > xkis1)
+    intsct = torch.where(mask, (xkis2 - xkis1) * (ykis2 - ykis1), torch.zeros_like(x1))
+    union = (x2 - x1) * (y2 - y1) + (x2g - x1g) * (y2g - y1g) - intsct
+    iou = intsct / (union + eps)
+    xc1 = torch.min(x1, x1g)
+    yc1 = torch.min(y1, y1g)
+    xc2 = torch.max(x2, x2g)
+    yc2 = torch.max(y2, y2g)
+    return (x1, y1, x2, y2), (x1g, y1g, x2g, y2g), iou, union, (xc1, yc1, xc2, yc2)
+
+
+def giou_loss(boxes1: torch.Tensor, boxes2: torch.Tensor, reduction: str = "none", eps: float = 1e-7, check: bool = True):
+    """[fvcore, unverified] giou_loss of two [N, 4] XYXY box sets: 1 - (IoU - (area_c - union) / (area_c + eps))."""
+    _, _, iou, union, (xc1, yc1, xc2, yc2) = _iou_pieces(boxes1, boxes2, eps, check)
+    area_c = (xc2 - xc1) * (yc2 - yc1)
+    miou = iou - ((area_c - union) / (area_c + eps))
+    return _reduce_box_loss(1 - miou, reduction)
+
+
+def _diou_terms(boxes1, boxes2, eps, check):
+    (x1, y1, x2, y2), (x1g, y1g, x2g, y2g), iou, _, (xc1, yc1, xc2, yc2) = _iou_pieces(boxes1, boxes2, eps, check)
+    diag_len = ((xc2 - xc1) ** 2) + ((yc2 - yc1) ** 2) + eps
+    x_p = (x2 + x1) / 2
+    y_p = (y2 + y1) / 2
+    x_g = (x1g + x2g) / 2
+    y_g = (y1g + y2g) / 2
+    distance = ((x_p - x_g) ** 2) + ((y_p - y_g) ** 2)
+    return iou, 1 - iou + (distance / diag_len), (x2 - x1, y2 - y1, x2g - x1g, y2g - y1g)
+
+
+def diou_loss(boxes1: torch.Tensor, boxes2: torch.Tensor, reduction: str = "none", eps: float = 1e-7, check: bool = True):
+    """[fvcore, unverified] diou_loss: 1 - IoU + (squared distance of the centres) / (squared diagonal of the enclosing box + eps)."""
+    return _reduce_box_loss(_diou_terms(boxes1, boxes2, eps, check)[1], reduction)
+
+
+def ciou_loss(boxes1: torch.Tensor, boxes2: torch.Tensor, reduction: str = "none", eps: float = 1e-7, check: bool = True):
+    """[fvcore, unverified] ciou_loss: diou + alpha * v, v = 4 / pi^2 (atan(wg / hg) - atan(w / h))^2 and alpha = v / (1 - IoU + v + eps)
+    formed under no_grad."""
+    iou, diou, (w_pred, h_pred, w_gt, h_gt) = _diou_terms(boxes1, boxes2, eps, check)
+    v = (4 / (math.pi ** 2)) * torch.pow((torch.atan(w_gt / h_gt) - torch.atan(w_pred / h_pred)), 2)
+    with torch.no_grad():
+        alpha = v / (1 - iou + v + eps)
+    return _reduce_box_loss(diou + alpha * v, reduction)
+
+
+_IOU_BOX_LOSSES = {"giou": giou_loss, "diou": diou_loss, "ciou": ciou_loss}
+
+
 def hip_linear(x: torch.Tensor, layer: nn.Linear) -> torch.Tensor:
     """nn.Linear forward (and backward) on the hand-written f32 MFMA kernel; the weights are read at
     call time (emb_pred.weight/bias are re-assigned by the meta-arch, distill_prop_mmss_gcnn.py:121-125)."""
@@ -517,6 +587,8 @@ class FastRCNNOutputLayers(nn.Module):
         mask instead of `nonzero` indices (a data-dependent size = a host sync): background rows get a unit box as source and
         target (zero deltas, finite everywhere) and weight 0 in the sum -- same value, same gradients."""
         box_dim = proposal_boxes.shape[1]
+        if self.box_reg_loss_type in _IOU_BOX_LOSSES:
+            return self._box_iou_loss(proposal_boxes, gt_boxes, pred_deltas, gt_classes, boxes_validated)
         if self.box_reg_loss_type != "smooth_l1":
             raise ValueError(f"Invalid bbox reg loss type '{self.box_reg_loss_type}'")
         if (_FUSED_BOX_LOSS and boxes_validated and pred_deltas.is_cuda and box_dim == 4 and pred_deltas.dtype == torch.float32
@@ -540,6 +612,36 @@ class FastRCNNOutputLayers(nn.Module):
         pred = torch.where(fg[:, None], pred, gt_pred_deltas)
         per_elem = smooth_l1_loss(pred, gt_pred_deltas, self.smooth_l1_beta, reduction="none")
         loss_box_reg = torch.where(fg[:, None], per_elem, per_elem.new_zeros(())).sum()
+        return loss_box_reg / max(gt_classes.numel(), 1.0)
+
+    def _box_iou_loss(self, proposal_boxes, gt_boxes, pred_deltas, gt_classes, boxes_validated: bool):
+        """[D2-upstream] box_reg_loss_type "giou" / "diou" / "ciou" (_dense_box_regression_loss: apply_deltas of the foreground rows'
+        predictions, the fvcore loss against their ground truth, summed; smooth_l1_beta is not used), normalised by ALL rows.  Selected
+        by a mask as the smooth-L1 form: background rows decode the unit box from the unit box against the unit box (finite
+        everywhere) and are selected out of the sum."""
+        box_dim = proposal_boxes.shape[1]
+        if (_FUSED_BOX_LOSS and boxes_validated and pred_deltas.is_cuda and box_dim == 4 and pred_deltas.dtype == torch.float32
+                and type(self.box2box_transform) is Box2BoxTransform and gt_classes.numel() > 0):
+            # one launch (ops.box_iou_loss = locov_box_iou_loss): the chain below, fused -- same foreground rule, same decoding, same
+            # normalisation; the gradient of the predictions comes out of the same launch
+            return ops.box_iou_loss(pred_deltas, proposal_boxes, gt_boxes, gt_classes, self.num_classes,
+                                    self.box2box_transform.weights, self.box2box_transform.scale_clamp, self.box_reg_loss_type)
+        fg = (gt_classes >= 0) & (gt_classes < self.num_classes)
+        if pred_deltas.shape[1] == box_dim:
+            pred = pred_deltas
+        else:
+            rows = torch.arange(gt_classes.shape[0], device=gt_classes.device)
+            pred = pred_deltas.view(-1, self.num_classes, box_dim)[rows, gt_classes.clamp(0, self.num_classes - 1)]
+        unit = torch.cat([proposal_boxes.new_zeros(box_dim // 2), proposal_boxes.new_ones(box_dim - box_dim // 2)])   # [0, 0, 1, 1], built on the device
+        src_boxes = torch.where(fg[:, None], proposal_boxes, unit)
+        target_boxes = torch.where(fg[:, None], gt_boxes, unit)
+        # background / ignored rows are REPLACED (zero deltas: the unit box again), not multiplied by zero: a non-finite prediction in
+        # such a row (which the indexed upstream form never touches) must not reach the value or the gradient
+        pred = torch.where(fg[:, None], pred, pred.new_zeros(()))
+        pred_boxes = self.box2box_transform.apply_deltas(pred, src_boxes)
+        # (fvcore's box assert is a host read: only where get_deltas' check runs in the smooth-L1 form)
+        per_row = _IOU_BOX_LOSSES[self.box_reg_loss_type](pred_boxes, target_boxes, reduction="none", check=not boxes_validated)
+        loss_box_reg = torch.where(fg, per_row, per_row.new_zeros(())).sum()
         return loss_box_reg / max(gt_classes.numel(), 1.0)
 
     def inference(self, predictions, proposals):
