@@ -184,7 +184,8 @@ int locov_roi_align_nhwc_ld_fwd(const void *feat, int feat_dtype, int N, int H, 
  *   feat_ld : elements between consecutive pixels of feat (>= C; the C channels pooled by this call may be
  *             a column block of a wider per-pixel vector, e.g. [conv1 | shortcut] outputs)
  *   ch_scale, ch_shift [C] (either may be null), relu: per-channel affine (FrozenBN) + ReLU applied to the
- *             pooled value, i.e. AFTER the pooling, exactly where the reference applies them. */
+ *             pooled value, i.e. AFTER the pooling, exactly where the reference applies them.  A proposal whose image
+ *             index is outside [0, N) pools to zero and then gets the affine and the ReLU like any other row. */
 int locov_roi_align_nhwc_affine_fwd(const void *feat, int feat_dtype, int N, int H, int W, int C,
                                     int64_t feat_ld, const float *rois, int64_t R, int pooled_h,
                                     int pooled_w, float spatial_scale, int sampling_ratio,

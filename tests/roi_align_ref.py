@@ -63,37 +63,46 @@ def axis_weights(start, end, pooled, bins, sampling_ratio, aligned, scale, exten
     return out
 
 
+def _pooled(P):
+    """(PH, PW) of a pooled size given as one int (square) or as a pair."""
+    return (int(P), int(P)) if np.isscalar(P) else (int(P[0]), int(P[1]))
+
+
 def grid_sizes(rois, P, scale, sr, aligned):
-    """(gh, gw): int64 [R] each, the contract's RAW sampling grid per roi (<= 0: the roi has no samples), float32 geometry."""
+    """(gh, gw): int64 [R] each, the contract's RAW sampling grid per roi (<= 0: the roi has no samples), float32 geometry.
+    P: the pooled size, an int or (PH, PW)."""
+    PH, PW = _pooled(P)
     rois = np.asarray(rois, np.float32).reshape(-1, 5)
-    gh = np.array([_axis_geometry(r[2], r[4], P, sr, aligned, scale)[2] for r in rois], np.int64)
-    gw = np.array([_axis_geometry(r[1], r[3], P, sr, aligned, scale)[2] for r in rois], np.int64)
+    gh = np.array([_axis_geometry(r[2], r[4], PH, sr, aligned, scale)[2] for r in rois], np.int64)
+    gw = np.array([_axis_geometry(r[1], r[3], PW, sr, aligned, scale)[2] for r in rois], np.int64)
     return gh, gw
 
 
 def _roi_matrices(roi, H, W, P, scale, sr, aligned, bin_stride):
-    bins = np.arange(0, P, bin_stride)
-    wy = axis_weights(roi[2], roi[4], P, bins, sr, aligned, scale, H)
-    wx = axis_weights(roi[1], roi[3], P, bins, sr, aligned, scale, W)
-    gh = _axis_geometry(roi[2], roi[4], P, sr, aligned, scale)[2]
-    gw = _axis_geometry(roi[1], roi[3], P, sr, aligned, scale)[2]
+    PH, PW = _pooled(P)
+    wy = axis_weights(roi[2], roi[4], PH, np.arange(0, PH, bin_stride), sr, aligned, scale, H)
+    wx = axis_weights(roi[1], roi[3], PW, np.arange(0, PW, bin_stride), sr, aligned, scale, W)
+    gh = _axis_geometry(roi[2], roi[4], PH, sr, aligned, scale)[2]
+    gw = _axis_geometry(roi[1], roi[3], PW, sr, aligned, scale)[2]
     return wy, wx, float(max(gh * gw, 1))
 
 
 def roi_align_fwd_f64(feat_nhwc, rois, P, scale, sr, aligned, bin_stride=1):
-    """feat [N,H,W,C], rois [R,5] (image, x1, y1, x2, y2) -> float64 [R, OH, OW, C], OH = OW = ceil(P / bin_stride): the bins
-    0, bin_stride, 2 bin_stride, ... of a P x P pooler.  A roi whose image index is outside [0, N) gives zeros."""
+    """feat [N,H,W,C], rois [R,5] (image, x1, y1, x2, y2) -> float64 [R, OH, OW, C], OH = ceil(PH / bin_stride), OW = ceil(PW /
+    bin_stride): the bins 0, bin_stride, 2 bin_stride, ... of a PH x PW pooler (P: an int, or the pair).  A roi whose image index
+    is outside [0, N) gives zeros."""
     feat = np.asarray(feat_nhwc, np.float64)
     rois = np.asarray(rois, np.float32).reshape(-1, 5)
     N, H, W, C = feat.shape
-    O = len(range(0, P, bin_stride))
-    out = np.zeros((len(rois), O, O, C), np.float64)
+    PH, PW = _pooled(P)
+    OH, OW = len(range(0, PH, bin_stride)), len(range(0, PW, bin_stride))
+    out = np.zeros((len(rois), OH, OW, C), np.float64)
     for r, roi in enumerate(rois):
         b = int(roi[0])
         if not 0 <= b < N:
             continue
         wy, wx, count = _roi_matrices(roi, H, W, P, scale, sr, aligned, bin_stride)
-        t = (wy @ feat[b].reshape(H, W * C)).reshape(O, W, C)
+        t = (wy @ feat[b].reshape(H, W * C)).reshape(OH, W, C)
         out[r] = np.matmul(wx, t) / count
     return out
 

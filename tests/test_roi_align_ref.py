@@ -7,11 +7,17 @@ Oracle distance, max abs error / max(|reference|.max(), 1), worst case per group
   list edges 2.0e-6 (R = 2100: ~2100 fp32 additions per pixel), footprint margin 3.4e-7, scatter cases 6.4e-7,
   accumulation 5.6e-7, strided rows 1.9e-7, NCHW 8.7e-7 (huge grids 2.8e-7).
 Every case is inside 1e-5 by a factor of 4.7 or more, so no case of the GPU file has a gate of its own.
+
+The same for the forward cases of tests/test_gpu_roi_align_fwd.py (tests/roi_align_fwd_cases.py; those without a bf16 map or an
+affine, which the oracle does not have): worst oracle distance per group
+  pooler settings 1.6e-7, table form 1.3e-7, on the fly 1.0e-7, channel slices 1.3e-7, option maps 9.7e-8, pooler contract 1.5e-7.
+A forward case whose oracle distance is within a factor 3 of the gate has the wrong inputs for that gate and fails here.
 """
 import numpy as np
 import pytest
 
 import roi_align_bwd_cases as cases
+import roi_align_fwd_cases as fwd_cases
 import roi_align_ref as ref
 
 
@@ -105,3 +111,36 @@ def test_oracle_distance_per_gpu_case(oracle, case):
     ratio = cases.error_ratio(got, want[..., :got.shape[-1]])
     print(f"oracle distance {case['name']}: {ratio:.2e}")
     assert ratio <= 1e-5
+
+
+_FWD = fwd_cases.plain_cases()
+
+
+@pytest.mark.parametrize("case", _FWD, ids=[c["name"] for c in _FWD])
+def test_oracle_distance_per_forward_gpu_case(oracle, case):
+    """Per plain case of the forward GPU file: check_conditions (every marked proposal has the grid, taps or plan that select its
+    branch; plan() runs on every proposal of a contract case), and the fp32 oracle's distance from reference(case) on the first 16
+    channels, out-of-range rows dropped -- printed, and asserted a factor 3 inside the GPU file's gate."""
+    want = fwd_cases.check_conditions(case)
+    if case["entry"] == "contract":
+        plans = [fwd_cases.plan(case, r) for r in range(len(case["rois"]))]
+        assert all(p["fast"] == (p["why"] is None) for p in plans)
+        if max(fwd_cases.pooled(case)) <= fwd_cases.K_TL_BINS:
+            assert any(p["fast"] for p in plans), "no proposal of this case takes the staged form"
+    got, keep = fwd_cases.oracle_forward(oracle, case)
+    ratio = fwd_cases.error_ratio(got, want[keep][..., :got.shape[-1]])
+    print(f"oracle distance {case['name']}: {ratio:.2e}")
+    assert ratio <= fwd_cases.GATE / 3
+
+
+def test_forward_case_helpers():
+    """The restated slice rule, the bf16 rounding, and that every variant of the GPU file passes its conditions."""
+    assert [fwd_cases.fwd_slices(C) for C in (8, 36, 508, 512, 516, 1024, 1028, 2048, 4096)] == \
+        [(1, 2), (1, 9), (1, 127), (2, 64), (2, 65), (4, 64), (4, 65), (8, 64), (8, 128)]
+    x = np.array([1.0, 1.00390625, 1.01171875, -3.1415927, 1e-30, 65504.0], np.float32)
+    import torch
+    assert np.array_equal(fwd_cases.bf16_round(x), torch.from_numpy(x).to(torch.bfloat16).float().numpy())
+    names = [c["name"] for c in fwd_cases.all_cases()]
+    assert len(set(names)) == len(names)
+    for case in fwd_cases.affine_cases() + fwd_cases.sliced_affine_cases() + fwd_cases.misc_cases() + [c for c, _ in fwd_cases.dtype_cases()]:
+        fwd_cases.check_conditions(case)
