@@ -34,7 +34,8 @@ extern "C" {
 
 /* 8: locov_detect_postprocess; later, additively: locov_grounding_ce_dist_fwd / _bwd, locov_distill_loss_fwd / _bwd,
  *    locov_detect_postprocess_wide (+ _workspace_bytes), locov_regions_select / _gather_fwd / _gather_bwd,
- *    locov_detect_postprocess_cs / _wide_cs (+ _workspace_bytes) */
+ *    locov_detect_postprocess_cs / _wide_cs (+ _workspace_bytes), locov_grounding_align_fwd / _bwd,
+ *    locov_grounding_triplet_fwd / _bwd */
 #define LOCOV_ABI_VERSION 8
 
 #define LOCOV_OK 0
@@ -688,7 +689,8 @@ int locov_detect_postprocess_wide_cs(const float *probs, int64_t ld_probs, int n
  * a-12  LSM grounding: word<->region alignment -> [caption, image] cost matrices.
  * Replaces the B^2-replicated chain of GroundingHead.forward
  * (ovr/modeling/mmss_heads/grounding_head.py:116-243) for LOCAL_METRIC "dot", ALIGNMENT
- * "softmax", GLOBAL_METRIC "aligned_local" (configs/coco_lsm.yaml).
+ * "softmax", GLOBAL_METRIC "aligned_local" (configs/coco_lsm.yaml); ALIGNMENT "hardmax" and a
+ * single direction: locov_grounding_align_fwd / _bwd below.
  *   S [B*T, B*NR] = caption token embeddings [B*T, L] . region embeddings [B*NR, L]^T
  *     (one locov_gemm_nt_f32 call; the region embeddings are v2l_projection(region_features),
  *     grounding_head.py:111, itself a locov_gemm_nt_f32 call)
@@ -704,6 +706,26 @@ int locov_grounding_fwd(const float *S, int B, int T, int NR, const float *capti
 int locov_grounding_bwd(const float *S, int B, int T, int NR, const float *caption_mask,
                         const float *region_mask, float temperature, const float *grad_w2r,
                         const float *grad_r2w, float *grad_S, locov_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
+ * a-12  the same launch with the alignment rule chosen and either direction optional (grounding_head.py:161-174 and
+ * ALIGN_WORDS_TO_REGIONS / ALIGN_REGIONS_TO_WORDS).  Added under ABI version 8.  Same kernel, same LDS tile, same limits; with
+ * LOCOV_GROUNDING_ALIGN_SOFTMAX and both directions given the results are bit-identical to locov_grounding_fwd / _bwd.
+ *   alignment HARDMAX: every word aligns to its valid region of largest S[t, r] (the lowest index on ties, torch's argmax rule;
+ *     region 0 with its unmasked distance when the image has no valid region -- every entry then equals the reference's fill), and
+ *     cost_w2r[c, i] = sum_t cm[t] * (-S[t, r*(t)] / temperature) / max(num_words, 1); regions to words symmetrically over the valid
+ *     words of each valid region (word 0 when the caption has none).  The one-hot is a constant: the backward adds
+ *     -g_w2r[c, i] * cm[t] / (temperature * max(num_words, 1)) to dS[t, r*(t)], the region direction likewise, summed where both meet.
+ *   cost_w2r / cost_r2w (forward), grad_w2r / grad_r2w (backward): NULL turns that direction off -- it is neither computed nor
+ *     read; both NULL is LOCOV_ERR_INVALID_ARG.  grad_S is always written in full (zeros where nothing flows).
+ * ------------------------------------------------------------------------------------- */
+#define LOCOV_GROUNDING_ALIGN_SOFTMAX 0
+#define LOCOV_GROUNDING_ALIGN_HARDMAX 1
+int locov_grounding_align_fwd(const float *S, int B, int T, int NR, const float *caption_mask, const float *region_mask,
+                              float temperature, int alignment, float *cost_w2r, float *cost_r2w, locov_stream_t stream);
+int locov_grounding_align_bwd(const float *S, int B, int T, int NR, const float *caption_mask, const float *region_mask,
+                              float temperature, int alignment, const float *grad_w2r, const float *grad_r2w, float *grad_S,
+                              locov_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * a-12  the cross-entropy tail of GroundingHead.forward on the [B, B] caption x image costs of locov_grounding_fwd, in ONE launch
@@ -736,6 +758,34 @@ int locov_grounding_ce_dist_bwd(const float *cost_w2r, const float *cost_r2w, co
                                 int T, int NR, const float *g_w2r_caption, const float *g_w2r_image, const float *g_r2w_caption,
                                 const float *g_r2w_image, const float *g_pw_w2r, const float *g_pw_r2w, float *dcost_w2r, float *dcost_r2w,
                                 locov_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
+ * a-12  the triplet tail of GroundingHead.forward (LOSS "triplet", grounding_head.py:279-343) on the same [B, B] costs, ONE launch
+ * each way.  Added under ABI version 8.  B <= LOCOV_GROUNDING_CE_MAX_B; cost_w2r / cost_r2w: either may be NULL.
+ *   Pairs with neither words nor regions get max(cost) + 100 first (:239-251, a detached constant, bit-identical to
+ *   torch.where(ok, cost, cost.max() + 100)).  positive = the diagonal.  The negative of column j ("choose caption") is, over the
+ *   rows i != j, the minimum (LOCOV_TRIPLET_HARDEST) or maximum (LOCOV_TRIPLET_EASIEST) of cost[i, j], or (LOCOV_TRIPLET_GIVEN) the
+ *   entry at reduced index k = neg_idx[...][j]: row k if k < j, else row k + 1 -- what gather on the matrix without its diagonal
+ *   picks (NEGATIVE_MINING "random", the draw made by the caller).  Rows ("choose image") likewise.
+ *   loss = mean(relu(positive - negative + margin)) in that fp32 order; B < 2: negative = positive + margin, zero gradient.
+ *   neg_idx: int64 [2 directions (w2r, r2w)][2 choices (caption, image)][B], required for GIVEN (values in [0, B - 1); the caller
+ *     vouches for them, the device clamps rather than follow one out of the matrix), ignored otherwise.
+ *   out8: the layout of locov_grounding_ce_fwd with the two losses in the CE slots; the accuracies are the same argmin means.
+ *   pw_w2r / pw_r2w: the filled costs, NULL where not wanted.
+ *   _bwd: g_* = device scalars d L / d (each of the four losses) or NULL (= 0), g_pw_* [B, B] the upstream gradients of the returned
+ *     distributions (NULL = 0).  The gradient reaches the diagonal entry and the selected negative of each active hinge; the filled
+ *     pairs are constants.
+ * ------------------------------------------------------------------------------------- */
+#define LOCOV_TRIPLET_HARDEST 0
+#define LOCOV_TRIPLET_EASIEST 1
+#define LOCOV_TRIPLET_GIVEN 2
+int locov_grounding_triplet_fwd(const float *cost_w2r, const float *cost_r2w, const float *caption_mask, const float *region_mask, int B,
+                                int T, int NR, int mining, float margin, const int64_t *neg_idx, float *out8, float *pw_w2r,
+                                float *pw_r2w, locov_stream_t stream);
+int locov_grounding_triplet_bwd(const float *cost_w2r, const float *cost_r2w, const float *caption_mask, const float *region_mask, int B,
+                                int T, int NR, int mining, float margin, const int64_t *neg_idx, const float *g_w2r_caption,
+                                const float *g_w2r_image, const float *g_r2w_caption, const float *g_r2w_image, const float *g_pw_w2r,
+                                const float *g_pw_r2w, float *dcost_w2r, float *dcost_r2w, locov_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * The distillation losses of the LSM meta-architecture over the [B, B] caption x image costs, ONE launch each way (SURVEY 8f-3;

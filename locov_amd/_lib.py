@@ -30,6 +30,8 @@ ABI_VERSION = 8
 DETECT_MAX_CANDIDATES, DETECT_FLAG_NONFINITE, DETECT_FLAG_OVERFLOW = 8192, 1, 2
 FED_LOSS_MAX_CLASSES = 32767
 DISTILL_KD, DISTILL_JS, DISTILL_MSE, DISTILL_MAX_B = 0, 1, 2, 64
+GROUNDING_ALIGN_SOFTMAX, GROUNDING_ALIGN_HARDMAX = 0, 1
+TRIPLET_HARDEST, TRIPLET_EASIEST, TRIPLET_GIVEN = 0, 1, 2
 BOX_IOU_GIOU, BOX_IOU_DIOU, BOX_IOU_CIOU = 0, 1, 2
 REGIONS_MAX_B, REGIONS_MAX_CANDIDATES = 64, 4096
 REGIONS_GRID, REGIONS_GRID_ALL, REGIONS_BOXES = 0, 1, 2
@@ -105,6 +107,9 @@ SIGNATURES = {
     "locov_grounding_ce_bwd": (c_int, [_p, _p, _p, _p, c_int, c_int, c_int, _p, _p, _p, _p, _p, _p, _p]),
     "locov_grounding_ce_dist_fwd": (c_int, [_p, _p, _p, _p, c_int, c_int, c_int, _p, _p, _p, _p]),
     "locov_grounding_ce_dist_bwd": (c_int, [_p, _p, _p, _p, c_int, c_int, c_int, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "locov_grounding_triplet_fwd": (c_int, [_p, _p, _p, _p, c_int, c_int, c_int, c_int, c_float, _p, _p, _p, _p, _p]),
+    "locov_grounding_triplet_bwd": (c_int, [_p, _p, _p, _p, c_int, c_int, c_int, c_int, c_float, _p, _p, _p, _p, _p, _p, _p, _p, _p,
+                                            _p]),
     "locov_distill_loss_fwd": (c_int, [_p, _p, _p, c_int, c_int, c_int, c_float, c_float, _p, _p]),
     "locov_distill_loss_bwd": (c_int, [_p, _p, _p, c_int, c_int, c_int, c_float, c_float, _p, _p, _p, _p, _p]),
     "locov_nms_workspace_bytes": (c_int64, [c_int64]),
@@ -124,6 +129,8 @@ SIGNATURES = {
                                                  _p, _p, _p]),
     "locov_grounding_fwd": (c_int, [_p, c_int, c_int, c_int, _p, _p, c_float, _p, _p, _p]),
     "locov_grounding_bwd": (c_int, [_p, c_int, c_int, c_int, _p, _p, c_float, _p, _p, _p, _p]),
+    "locov_grounding_align_fwd": (c_int, [_p, c_int, c_int, c_int, _p, _p, c_float, c_int, _p, _p, _p]),
+    "locov_grounding_align_bwd": (c_int, [_p, c_int, c_int, c_int, _p, _p, c_float, c_int, _p, _p, _p, _p]),
     "locov_token_attention_fwd": (c_int, [_p, c_int64, c_int, _p, _p, c_int, c_int, c_float, c_int, c_int, _p, _p, _p, _p]),
     "locov_token_attention_bwd": (c_int, [_p, c_int64, c_int, _p, _p, c_int, c_int, c_float, c_int, c_int, _p, _p, _p, _p, _p]),
     "locov_rownorm_fwd": (c_int, [_p, c_int64, c_int, c_int, c_float, _p, _p]),

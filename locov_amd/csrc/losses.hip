@@ -9,6 +9,8 @@
 //     239-251 the "(max + 100)" replacement of pairs with neither words nor regions, :273-290 log_softmax over captions and over
 //     images + the diagonal means, :357-377 the batch accuracies) on the [B, B] caption x image cost matrices of locov_grounding_fwd;
 //     locov_grounding_ce_dist_fwd / _bwd the same launch when the head also returns the filled costs (DISTILLATION_LOSS).
+//   * locov_grounding_triplet_fwd / _bwd -- the triplet tail of the same forward (:279-343: hardest / easiest / given negatives of
+//     every caption and image, the hinge means) with the same fill, accuracies and optional distributions, one launch each way.
 //   * locov_distill_loss_fwd / _bwd -- MultiDistillLoss / MultiDistillLossJS / MultiDistillLossL2 (ovr/modeling/meta_arch/
 //     distill_mmss_gcnn.py:211-433) on the transformer's and the grounding head's [B, B] costs, one workgroup, all three staged in LDS.
 //
@@ -231,6 +233,127 @@ __global__ __launch_bounds__(kLossThreads) void grounding_ce_dist_kernel(const f
     grounding_ce_body<GRAD, true>(cost0, cost1, cmask, rmask, B, T, NR, out, up0, up1, up2, up3, d0, d1, pw0, pw1, gpw0, gpw1);
 }
 
+
+// The triplet tail (grounding_head.py:279-343) on the same [B, B] costs, one workgroup: positive = the diagonal; the negative of
+// column j ("choose caption") / row i ("choose image") is the off-diagonal minimum (hardest), maximum (easiest) or the entry a given
+// index names in the matrix without its diagonal (reduced index k -> k below the diagonal position, k + 1 from it on: what gather on
+// remove_diag picks; an index outside [0, B - 1) is clamped into it, never followed out of the matrix).  out as grounding_ce_body's,
+// the two CE values replaced by mean(relu(positive - negative + margin)).  B < 2: negative = positive + margin, no gradient.
+// GRAD: the hinge's gradient on the diagonal entry and on the selected negative, plus gpw on the pairs that are not filled.
+template <bool GRAD>
+__global__ __launch_bounds__(kLossThreads) void grounding_triplet_kernel(
+    const float *__restrict__ cost0, const float *__restrict__ cost1, const float *__restrict__ cmask, const float *__restrict__ rmask,
+    int B, int T, int NR, int mining, float margin, const int64_t *__restrict__ neg_idx, float *__restrict__ out,
+    float *__restrict__ pw0, float *__restrict__ pw1, const float *up0, const float *up1, const float *up2, const float *up3,
+    const float *__restrict__ gpw0, const float *__restrict__ gpw1, float *__restrict__ d0, float *__restrict__ d1)
+{
+    __shared__ float red[kLossThreads];
+    __shared__ float cf[LOCOV_GROUNDING_CE_MAX_B * LOCOV_GROUNDING_CE_MAX_B];      // the filled cost of the current tag
+    __shared__ float dacc[GRAD ? LOCOV_GROUNDING_CE_MAX_B * LOCOV_GROUNDING_CE_MAX_B : 1];
+    __shared__ float nw[LOCOV_GROUNDING_CE_MAX_B], nr[LOCOV_GROUNDING_CE_MAX_B];
+    const int t = threadIdx.x, BB = B * B;
+    for (int i = t; i < B; i += kLossThreads) {
+        float a = 0.f, b = 0.f;
+        for (int k = 0; k < T; k++) a = a + cmask[i * T + k];
+        for (int k = 0; k < NR; k++) b = b + rmask[i * NR + k];
+        nw[i] = a;
+        nr[i] = b;
+    }
+    __syncthreads();
+    for (int tag = 0; tag < 2; tag++) {
+        const float *cost = tag ? cost1 : cost0;
+        if (!cost) {                                          // (workgroup-uniform)
+            if (!GRAD && t < 4) out[tag * 4 + t] = 0.f;
+            continue;
+        }
+        float m = -INFINITY;
+        for (int e = t; e < BB; e += kLossThreads) m = fmaxf(m, cost[e]);
+        const float fill = block_max(m, red) + 100.0f;       // pairs with neither words nor regions: max + 100 (:239-251)
+        for (int e = t; e < BB; e += kLossThreads) {
+            const int i = e / B, j = e - i * B;
+            const float c = (nw[i] > 0.f || nr[j] > 0.f) ? cost[e] : fill;
+            cf[e] = c;
+            if (GRAD) dacc[e] = 0.f;
+            float *pw = tag ? pw1 : pw0;
+            if (!GRAD && pw) pw[e] = c;
+        }
+        __syncthreads();
+        // thread k: column k (choose caption) and row k (choose image)
+        const int k = t;
+        int nc = -1, ni = -1;                                 // the selected negatives: cf[nc * B + k], cf[k * B + ni]
+        float hc = 0.f, hi = 0.f, ac = 0.f, ai = 0.f;
+        if (k < B) {
+            const float pos = cf[k * B + k];
+            float negc, negi;
+            if (B < 2) {
+                negc = negi = pos + margin;
+            } else if (mining == LOCOV_TRIPLET_GIVEN) {
+                const int64_t *idx = neg_idx + (int64_t)tag * 2 * B;
+                int64_t a = idx[k], b = idx[B + k];
+                a = a < 0 ? 0 : (a > B - 2 ? B - 2 : a);
+                b = b < 0 ? 0 : (b > B - 2 ? B - 2 : b);
+                nc = (int)(a < k ? a : a + 1);
+                ni = (int)(b < k ? b : b + 1);
+                negc = cf[nc * B + k];
+                negi = cf[k * B + ni];
+            } else {
+                const bool easiest = mining == LOCOV_TRIPLET_EASIEST;
+                for (int v = 0; v < B; v++) {
+                    if (v == k) continue;
+                    const float xc = cf[v * B + k], xi = cf[k * B + v];
+                    if (nc < 0 || (easiest ? xc > cf[nc * B + k] : xc < cf[nc * B + k])) nc = v;
+                    if (ni < 0 || (easiest ? xi > cf[k * B + ni] : xi < cf[k * B + ni])) ni = v;
+                }
+                negc = cf[nc * B + k];
+                negi = cf[k * B + ni];
+            }
+            hc = fmaxf((pos - negc) + margin, 0.f);
+            hi = fmaxf((pos - negi) + margin, 0.f);
+            if (B < 2) nc = ni = -1;
+            if (!GRAD) {
+                int bc = 0, bi = 0;                           // argmin, first index on ties
+                for (int v = 1; v < B; v++) {
+                    if (cf[v * B + k] < cf[bc * B + k]) bc = v;
+                    if (cf[k * B + v] < cf[k * B + bi]) bi = v;
+                }
+                ac = bc == k ? 1.f : 0.f;
+                ai = bi == k ? 1.f : 0.f;
+            }
+        }
+        if (!GRAD) {
+            const float shc = block_sum(hc, red), shi = block_sum(hi, red), sac = block_sum(ac, red), sai = block_sum(ai, red);
+            if (t == 0) {
+                out[tag * 4 + 0] = shc / (float)B;
+                out[tag * 4 + 1] = shi / (float)B;
+                out[tag * 4 + 2] = sac / (float)B;
+                out[tag * 4 + 3] = sai / (float)B;
+            }
+        } else {
+            const float *pc = tag ? up2 : up0, *pi = tag ? up3 : up1;
+            const float gc = (pc ? pc[0] : 0.f) / (float)B, gi = (pi ? pi[0] : 0.f) / (float)B;
+            // column k's two entries belong to thread k alone, row k's likewise; the two passes meet, so a barrier parts them
+            if (k < B && nc >= 0 && hc > 0.f) {
+                dacc[k * B + k] += gc;
+                dacc[nc * B + k] -= gc;
+            }
+            __syncthreads();
+            if (k < B && ni >= 0 && hi > 0.f) {
+                dacc[k * B + k] += gi;
+                dacc[k * B + ni] -= gi;
+            }
+            __syncthreads();
+            float *d = tag ? d1 : d0;
+            const float *gp = tag ? gpw1 : gpw0;
+            for (int e = t; e < BB; e += kLossThreads) {
+                const int i = e / B, j = e - i * B;
+                float dc = dacc[e];
+                if (gp) dc = dc + gp[e];
+                d[e] = (nw[i] > 0.f || nr[j] > 0.f) ? dc : 0.f;   // the replaced pairs are constants
+            }
+        }
+        __syncthreads();
+    }
+}
 
 // ---- the distillation losses (locov_distill_loss_fwd / _bwd; include/locov_hip.h states the arithmetic) ----
 constexpr int kDistMaxB = LOCOV_DISTILL_MAX_B;
@@ -492,6 +615,48 @@ extern "C" int locov_grounding_ce_dist_bwd(const float *cost_w2r, const float *c
                        region_mask, B, T, NR, nullptr, g_w2r_caption, g_w2r_image, g_r2w_caption, g_r2w_image, dcost_w2r, dcost_r2w,
                        nullptr, nullptr, cost_w2r ? g_pw_w2r : nullptr, cost_r2w ? g_pw_r2w : nullptr);
     return check_launch("locov_grounding_ce_dist_bwd");
+}
+
+static int grounding_triplet_args(const float *c0, const float *c1, const float *cm, const float *rm, int B, int T, int NR, int mining,
+                                  const int64_t *neg_idx)
+{
+    using namespace locov;
+    LOCOV_REQUIRE(B >= 1 && B <= LOCOV_GROUNDING_CE_MAX_B && T >= 0 && NR >= 0, "locov_grounding_triplet: 1 <= B <= %d",
+                  LOCOV_GROUNDING_CE_MAX_B);
+    LOCOV_REQUIRE(mining == LOCOV_TRIPLET_HARDEST || mining == LOCOV_TRIPLET_EASIEST || mining == LOCOV_TRIPLET_GIVEN,
+                  "locov_grounding_triplet: unknown mining %d", mining);
+    LOCOV_REQUIRE(mining != LOCOV_TRIPLET_GIVEN || neg_idx, "locov_grounding_triplet: given negatives need their indices");
+    LOCOV_REQUIRE((c0 || c1) && cm && rm, "locov_grounding_triplet: null pointer");
+    return LOCOV_OK;
+}
+
+extern "C" int locov_grounding_triplet_fwd(const float *cost_w2r, const float *cost_r2w, const float *caption_mask, const float *region_mask,
+                                           int B, int T, int NR, int mining, float margin, const int64_t *neg_idx, float *out8,
+                                           float *pw_w2r, float *pw_r2w, locov_stream_t stream)
+{
+    using namespace locov;
+    if (int rc = grounding_triplet_args(cost_w2r, cost_r2w, caption_mask, region_mask, B, T, NR, mining, neg_idx)) return rc;
+    LOCOV_REQUIRE(out8, "locov_grounding_triplet_fwd: null output");
+    hipLaunchKernelGGL(grounding_triplet_kernel<false>, dim3(1), dim3(kLossThreads), 0, as_stream(stream), cost_w2r, cost_r2w,
+                       caption_mask, region_mask, B, T, NR, mining, margin, neg_idx, out8, cost_w2r ? pw_w2r : nullptr,
+                       cost_r2w ? pw_r2w : nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+    return check_launch("locov_grounding_triplet_fwd");
+}
+
+extern "C" int locov_grounding_triplet_bwd(const float *cost_w2r, const float *cost_r2w, const float *caption_mask, const float *region_mask,
+                                           int B, int T, int NR, int mining, float margin, const int64_t *neg_idx,
+                                           const float *g_w2r_caption, const float *g_w2r_image, const float *g_r2w_caption,
+                                           const float *g_r2w_image, const float *g_pw_w2r, const float *g_pw_r2w, float *dcost_w2r,
+                                           float *dcost_r2w, locov_stream_t stream)
+{
+    using namespace locov;
+    if (int rc = grounding_triplet_args(cost_w2r, cost_r2w, caption_mask, region_mask, B, T, NR, mining, neg_idx)) return rc;
+    LOCOV_REQUIRE((!cost_w2r || dcost_w2r) && (!cost_r2w || dcost_r2w), "locov_grounding_triplet_bwd: null gradient output");
+    hipLaunchKernelGGL(grounding_triplet_kernel<true>, dim3(1), dim3(kLossThreads), 0, as_stream(stream), cost_w2r, cost_r2w,
+                       caption_mask, region_mask, B, T, NR, mining, margin, neg_idx, nullptr, nullptr, nullptr, g_w2r_caption,
+                       g_w2r_image, g_r2w_caption, g_r2w_image, cost_w2r ? g_pw_w2r : nullptr, cost_r2w ? g_pw_r2w : nullptr,
+                       dcost_w2r, dcost_r2w);
+    return check_launch("locov_grounding_triplet_bwd");
 }
 
 static int distill_args(const float *trans, const float *w2r, const float *r2w, int B, int kind, float temperature)

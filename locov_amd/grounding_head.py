@@ -11,14 +11,23 @@ caption tokens meet in ONE [B*T, B*NR] GEMM and one fused kernel reduces each T 
 two cost entries (csrc/grounding.hip).  The B x B cross-entropy tail is one more launch each way
 (csrc/losses.hip), with or without the distributions DISTILLATION_LOSS asks for.
 
-The other variants the reference defines -- ALIGNMENT hardmax / random_categorical / random_top3
-(:169-208), GLOBAL_METRIC reconstruction_mse (:215-224), LOSS triplet with hardest / easiest / random
-negatives (:279-343), one alignment direction only -- share the same single similarity GEMM and then
-follow the reference's statements on the [B^2, T, NR] view with device tensor ops (`_general`); they
-are configuration options off the shipped path, kept for drop-in completeness and pinned to the
-reference's own outputs (tests/golden G8).  What the reference itself rejects is rejected the same
-way: LOCAL_METRIC other than "dot" (NotImplementedError, :149), LOSS "matching" with the dot metric
-(Exception, :258-262), unknown names (NotImplementedError).
+ALIGNMENT "hardmax" (:169-174), LOSS "triplet" with hardest / easiest / random negatives (:279-343) and
+a single alignment direction run on the same kernels: the alignment kernel takes the rule and the
+directions (ops.grounding_costs(alignment=, words=, regions=)), hardmax costs feed the same
+cross-entropy tail, and the triplet tail is one launch each way (ops.grounding_triplet) with no host
+read.  NEGATIVE_MINING "random" draws its indices here, with the torch.randint calls `_general` makes in
+the same order, so a seeded run keeps its RNG stream, and hands them to the kernel.
+
+Out of scope for the kernels, still on `_general` (the reference's statements on the [B^2, T, NR] view
+with device tensor ops after the same single similarity GEMM; configuration options off the shipped
+path, kept for drop-in completeness and pinned to the reference's own outputs, tests/golden G8):
+GLOBAL_METRIC reconstruction_mse (:215-224) -- it needs the embeddings inside the tile, and its region
+direction only broadcasts for B^2 == NR in the reference; ALIGNMENT random_categorical / random_top3
+(:175-208) -- torch.multinomial's draw cannot be reproduced inside a kernel.  `_general` also answers
+every configuration it answers with an exception (e.g. DISTILLATION_LOSS with one direction off:
+KeyError), B above GROUNDING_CE_MAX_B and LOCOV_FUSED_LOSSES=0.  What the reference itself rejects is
+rejected the same way: LOCAL_METRIC other than "dot" (NotImplementedError, :149), LOSS "matching" with
+the dot metric (Exception, :258-262), unknown names (NotImplementedError).
 """
 from __future__ import annotations
 
@@ -60,6 +69,11 @@ class GroundingHead(nn.Module):
         self.log_info: Dict[str, object] = {}          # LoggedModule.log_info (filled lazily, no host syncs)
         self._fused = (self.local_metric, self.global_metric, self.alignment, self.loss_type) == \
             ("dot", "aligned_local", "softmax", "cross_entropy")
+        # the variants the kernels also take (hardmax, triplet); what `_general` answers with an exception stays there
+        self._fused_variant = not self._fused and (self.local_metric, self.global_metric) == ("dot", "aligned_local") and \
+            self.alignment in ("softmax", "hardmax") and self.loss_type in ("cross_entropy", "triplet") and \
+            (self.loss_type != "triplet" or self.negative_mining in ("hardest", "easiest", "random")) and \
+            not (self.return_dist and not (self.align_words and self.align_regions))
 
     def forward(self, input_image, input_caption):
         caption_emb = input_caption[self.grounding_text_input]                       # [B, T, L]
@@ -78,6 +92,9 @@ class GroundingHead(nn.Module):
             raise NotImplementedError                                                 # :146-149
         # :147 all B^2 caption x image token-region similarities as one NT GEMM
         S = ops.linear_autograd(cap, image_emb, None)                                 # [B*T, B*NR]
+        if self._fused_variant and S.is_cuda and S.dtype == torch.float32 and B <= ops.GROUNDING_CE_MAX_B and \
+                os.environ.get("LOCOV_FUSED_LOSSES", "1") != "0":
+            return self._variant(S, caption_mask, region_mask, B)
         if not self._fused:
             return self._general(S, cap.view(B, T, -1), image_emb.view(B, NR, -1), caption_mask, region_mask, caption_mask.sum(dim=1),
                                  region_mask.sum(dim=1))
@@ -125,6 +142,46 @@ class GroundingHead(nn.Module):
             return other_info, losses, {"w2r": pw.get("Words"), "r2w": pw.get("Regions")}
         return other_info, losses
 
+    # ------------------------------------------------------------------ hardmax / triplet / one direction on the kernels
+    def _variant(self, S, caption_mask, region_mask, B):
+        """:150-343 for ALIGNMENT softmax | hardmax and LOSS cross_entropy | triplet: one alignment launch, one tail launch."""
+        c0, c1 = ops.grounding_costs(S, caption_mask, region_mask, self.temperature, alignment=self.alignment,
+                                     words=self.align_words, regions=self.align_regions)
+        pw0 = pw1 = None
+        if self.loss_type == "cross_entropy":
+            name = "CE_loss"
+            if self.return_dist:
+                vals, pw0, pw1 = ops.grounding_ce_dist(c0, c1, caption_mask, region_mask)
+            else:
+                vals = ops.grounding_ce(c0, c1, caption_mask, region_mask)
+        else:
+            name = "Triplet Loss"
+            mining, neg_idx = self.negative_mining, None
+            if B < 2:
+                mining = "hardest"                            # (:296 negative = positive + margin whatever the mining; nothing is drawn)
+            elif mining == "random":
+                # the draws of `_general`, same calls in the same order: per direction that is on, (1, B) then (B, 1)
+                draws = [None] * 4
+                for k, on in enumerate((self.align_words, self.align_regions)):
+                    if on:
+                        draws[2 * k] = torch.randint(B - 1, (1, B), device=S.device).view(B)
+                        draws[2 * k + 1] = torch.randint(B - 1, (B, 1), device=S.device).view(B)
+                spare = next(d for d in draws if d is not None)                  # (a direction that is off is not read)
+                mining, neg_idx = "given", torch.stack([d if d is not None else spare for d in draws]).view(2, 2, B)
+            res = ops.grounding_triplet(c0, c1, caption_mask, region_mask, mining, self.margin, neg_idx, with_dist=self.return_dist)
+            vals, pw0, pw1 = res if self.return_dist else (res, None, None)
+        losses, other_info = {}, {}
+        for k, (on, tag) in enumerate(((self.align_words, "Words"), (self.align_regions, "Regions"))):
+            if not on:
+                continue
+            losses[f"{name} (Align {tag}, Choose Caption)"] = vals[4 * k]
+            losses[f"{name} (Align {tag}, Choose Image)"] = vals[4 * k + 1]
+            other_info[f"Batch Accuracy (Align {tag}, Choose Caption)"] = vals[4 * k + 2]
+            other_info[f"Batch Accuracy (Align {tag}, Choose Image)"] = vals[4 * k + 3]
+        self.log_info = {**losses, **other_info}
+        if self.return_dist:
+            return other_info, losses, {"w2r": pw0, "r2w": pw1}
+        return other_info, losses
 
     # ------------------------------------------------------------------ the reference's other variants (:146-343)
     def _general(self, S, cap, img, caption_mask, region_mask, num_words, num_regions):

@@ -1488,16 +1488,68 @@ class _GroundingFn(torch.autograd.Function):
         return dS, None, None, None, None, None, None
 
 
-def grounding_costs(S: torch.Tensor, caption_mask: torch.Tensor, region_mask: torch.Tensor,
-                    temperature: float) -> Tuple[torch.Tensor, torch.Tensor]:
+GROUNDING_ALIGNMENTS = {"softmax": _lib.GROUNDING_ALIGN_SOFTMAX, "hardmax": _lib.GROUNDING_ALIGN_HARDMAX}
+
+
+class _GroundingAlignFn(torch.autograd.Function):
+    """_GroundingFn with the alignment rule chosen and either direction optional (locov_grounding_align_fwd / _bwd): returns the
+    costs of the directions that are on."""
+
+    @staticmethod
+    def forward(ctx, S, cmask, rmask, B, T, NR, temperature, alignment, words, regions):
+        ctx.set_materialize_grads(False)
+        S = _dev(S, "S")
+        cmask, rmask = _dev(cmask, "caption_mask"), _dev(rmask, "region_mask")
+        w2r = torch.empty((B, B), dtype=torch.float32, device=S.device) if words else None
+        r2w = torch.empty((B, B), dtype=torch.float32, device=S.device) if regions else None
+        with torch.cuda.device(S.device):
+            check(_lib.load().locov_grounding_align_fwd(_ptr(S), B, T, NR, _ptr(cmask), _ptr(rmask), float(temperature), alignment,
+                                                        _ptr(w2r), _ptr(r2w), _stream(S)), "locov_grounding_align_fwd")
+        ctx.save_for_backward(S, cmask, rmask)
+        ctx.dims = (B, T, NR, temperature, alignment, words, regions)
+        return tuple(c for c in (w2r, r2w) if c is not None)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *g):
+        S, cmask, rmask = ctx.saved_tensors
+        B, T, NR, temperature, alignment, words, regions = ctx.dims
+        g = list(g)
+        g_w2r = g.pop(0) if words else None
+        g_r2w = g.pop(0) if regions else None
+        if g_w2r is None and g_r2w is None:                       # no cost was used: nothing flows
+            return (torch.zeros_like(S),) + (None,) * 9
+        g_w2r = _dev(g_w2r, "grad_w2r") if g_w2r is not None else None
+        g_r2w = _dev(g_r2w, "grad_r2w") if g_r2w is not None else None
+        dS = torch.empty_like(S)
+        with torch.cuda.device(S.device):
+            check(_lib.load().locov_grounding_align_bwd(_ptr(S), B, T, NR, _ptr(cmask), _ptr(rmask), float(temperature), alignment,
+                                                        _ptr(g_w2r), _ptr(g_r2w), _ptr(dS), _stream(S)),
+                  "locov_grounding_align_bwd")
+        return (dS,) + (None,) * 9
+
+
+def grounding_costs(S: torch.Tensor, caption_mask: torch.Tensor, region_mask: torch.Tensor, temperature: float,
+                    alignment: str = "softmax", words: bool = True,
+                    regions: bool = True) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
     """S [B*T, B*NR] (caption tokens x region embeddings), masks [B,T] / [B,NR] fp32 ->
-    (cost_w2r, cost_r2w) [B,B] with rows = captions, columns = images.  Differentiable in S."""
+    (cost_w2r, cost_r2w) [B,B] with rows = captions, columns = images.  Differentiable in S.
+    alignment "softmax" | "hardmax" (grounding_head.py:161-174); words / regions False turns that direction off (its cost is
+    None and nothing of it is computed)."""
     B, T = caption_mask.shape
     NR = region_mask.shape[1]
     if tuple(S.shape) != (B * T, B * NR):
         raise ValueError(f"S must be [{B * T},{B * NR}], got {tuple(S.shape)}")
-    return _GroundingFn.apply(S, caption_mask.to(torch.float32), region_mask.to(torch.float32), B, T, NR,
-                              float(temperature))
+    if alignment not in GROUNDING_ALIGNMENTS:
+        raise ValueError(f"grounding_costs: unknown alignment {alignment!r} (softmax | hardmax)")
+    if not (words or regions):
+        raise ValueError("grounding_costs: both alignment directions are off")
+    if alignment == "softmax" and words and regions:
+        return _GroundingFn.apply(S, caption_mask.to(torch.float32), region_mask.to(torch.float32), B, T, NR,
+                                  float(temperature))
+    res = list(_GroundingAlignFn.apply(S, caption_mask.to(torch.float32), region_mask.to(torch.float32), B, T, NR, float(temperature),
+                                       GROUNDING_ALIGNMENTS[alignment], bool(words), bool(regions)))
+    return (res.pop(0) if words else None), (res.pop(0) if regions else None)
 
 
 GROUNDING_CE_MAX_B = 64        # LOCOV_GROUNDING_CE_MAX_B
@@ -1605,6 +1657,88 @@ def grounding_ce_dist(cost_w2r: Optional[torch.Tensor], cost_r2w: Optional[torch
     if ref is None or ref.dim() != 2 or ref.shape[0] != ref.shape[1] or ref.shape[0] > GROUNDING_CE_MAX_B:
         raise ValueError(f"grounding_ce_dist: costs must be [B, B] with B <= {GROUNDING_CE_MAX_B}")
     res = _GroundingCEDistFn.apply(cost_w2r, cost_r2w, caption_mask.to(torch.float32), region_mask.to(torch.float32))
+    pw = list(res[8:])
+    pw0 = pw.pop(0) if cost_w2r is not None else None
+    pw1 = pw.pop(0) if cost_r2w is not None else None
+    return tuple(res[:8]), pw0, pw1
+
+
+TRIPLET_MINING = {"hardest": _lib.TRIPLET_HARDEST, "easiest": _lib.TRIPLET_EASIEST, "given": _lib.TRIPLET_GIVEN}
+
+
+class _GroundingTripletFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, cost_w2r, cost_r2w, cmask, rmask, mining, margin, neg_idx, with_dist):
+        ctx.set_materialize_grads(False)                  # unused outputs send NULL, not zero-filled upstream gradients
+        ref = cost_w2r if cost_w2r is not None else cost_r2w
+        c0 = _dev(cost_w2r, "cost_w2r") if cost_w2r is not None else None
+        c1 = _dev(cost_r2w, "cost_r2w") if cost_r2w is not None else None
+        cmask, rmask = _dev(cmask, "caption_mask"), _dev(rmask, "region_mask")
+        B, T, NR = ref.shape[0], cmask.shape[1], rmask.shape[1]
+        out = torch.empty(8, dtype=torch.float32, device=ref.device)          # (the kernel zeroes an absent alignment's four)
+        pw0 = torch.empty_like(c0) if with_dist and c0 is not None else None
+        pw1 = torch.empty_like(c1) if with_dist and c1 is not None else None
+        with torch.cuda.device(ref.device):
+            check(_lib.load().locov_grounding_triplet_fwd(_ptr(c0), _ptr(c1), _ptr(cmask), _ptr(rmask), B, T, NR, mining, margin,
+                                                          _ptr(neg_idx), _ptr(out), _ptr(pw0), _ptr(pw1), _stream(ref)),
+                  "locov_grounding_triplet_fwd")
+        ctx.save_for_backward(*(t for t in (c0, c1, neg_idx) if t is not None), cmask, rmask)
+        ctx.have = (c0 is not None, c1 is not None, neg_idx is not None)
+        ctx.args = (mining, margin, with_dist)
+        vals = out.unbind(0)
+        ctx.mark_non_differentiable(vals[2], vals[3], vals[6], vals[7])
+        return vals + tuple(p for p in (pw0, pw1) if p is not None)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *g):
+        saved = list(ctx.saved_tensors)
+        c0 = saved.pop(0) if ctx.have[0] else None
+        c1 = saved.pop(0) if ctx.have[1] else None
+        neg_idx = saved.pop(0) if ctx.have[2] else None
+        cmask, rmask = saved
+        mining, margin, with_dist = ctx.args
+        ref = c0 if c0 is not None else c1
+        B, T, NR = ref.shape[0], cmask.shape[1], rmask.shape[1]
+        ups = [(_dev(g[i].reshape(1), "grad") if g[i] is not None else None) for i in (0, 1, 4, 5)]
+        gpw = list(g[8:])
+        g0 = gpw.pop(0) if with_dist and ctx.have[0] else None
+        g1 = gpw.pop(0) if with_dist and ctx.have[1] else None
+        g0 = _dev(g0, "grad_pw_w2r") if g0 is not None else None
+        g1 = _dev(g1, "grad_pw_r2w") if g1 is not None else None
+        d0 = torch.empty_like(c0) if c0 is not None else None
+        d1 = torch.empty_like(c1) if c1 is not None else None
+        with torch.cuda.device(ref.device):
+            check(_lib.load().locov_grounding_triplet_bwd(_ptr(c0), _ptr(c1), _ptr(cmask), _ptr(rmask), B, T, NR, mining, margin,
+                                                          _ptr(neg_idx), *(_ptr(u) for u in ups), _ptr(g0), _ptr(g1), _ptr(d0),
+                                                          _ptr(d1), _stream(ref)), "locov_grounding_triplet_bwd")
+        return d0, d1, None, None, None, None, None, None
+
+
+def grounding_triplet(cost_w2r: Optional[torch.Tensor], cost_r2w: Optional[torch.Tensor], caption_mask: torch.Tensor,
+                      region_mask: torch.Tensor, mining: str, margin: float, neg_idx: Optional[torch.Tensor] = None,
+                      with_dist: bool = False):
+    """The triplet tail of GroundingHead.forward (grounding_head.py:239-251,279-343,357-377) on the [B, B] costs of grounding_costs,
+    one launch each way (locov_grounding_triplet_fwd / _bwd).  mining "hardest" | "easiest" | "given"; "given" takes neg_idx, int64
+    [2 (w2r, r2w), 2 (choose caption, choose image), B] with values in [0, B - 1): indices into the matrix without its diagonal, as
+    NEGATIVE_MINING "random" draws them (the values stay on the device and are not inspected here).  Returns the 8 scalars in
+    grounding_ce's layout (the hinge means in the CE slots); with_dist: (the 8 scalars, pw_w2r, pw_r2w) as grounding_ce_dist."""
+    ref = cost_w2r if cost_w2r is not None else cost_r2w
+    if ref is None or ref.dim() != 2 or ref.shape[0] != ref.shape[1] or ref.shape[0] > GROUNDING_CE_MAX_B:
+        raise ValueError(f"grounding_triplet: costs must be [B, B] with B <= {GROUNDING_CE_MAX_B}")
+    if mining not in TRIPLET_MINING:
+        raise ValueError(f"grounding_triplet: unknown mining {mining!r} (hardest | easiest | given)")
+    B = ref.shape[0]
+    if mining == "given":
+        if neg_idx is None or neg_idx.dtype != torch.int64 or tuple(neg_idx.shape) != (2, 2, B) or neg_idx.device != ref.device:
+            raise ValueError(f"grounding_triplet: given negatives need neg_idx int64 [2, 2, {B}] on the costs' device")
+        neg_idx = neg_idx.contiguous()
+    else:
+        neg_idx = None
+    res = _GroundingTripletFn.apply(cost_w2r, cost_r2w, caption_mask.to(torch.float32), region_mask.to(torch.float32),
+                                    TRIPLET_MINING[mining], float(margin), neg_idx, bool(with_dist))
+    if not with_dist:
+        return tuple(res[:8])
     pw = list(res[8:])
     pw0 = pw.pop(0) if cost_w2r is not None else None
     pw1 = pw.pop(0) if cost_r2w is not None else None
