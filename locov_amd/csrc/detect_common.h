@@ -85,6 +85,7 @@ __global__ __launch_bounds__(256) void det_decode_clip_cs_kernel(const float *__
     boxes[t] = det_clip(o, g.w[img], g.h[img]);
 }
 
+// must round exactly as nms.hip's iou_gt does (all three files are compiled with -ffp-contract=off): change them together
 __device__ __forceinline__ bool det_iou_gt(const float4 a, const float4 b, float thr)        // (= nms.hip's iou_gt)
 {
     const float left = fmaxf(a.x, b.x), right = fminf(a.z, b.z);

@@ -15,6 +15,7 @@
 
 namespace locov {
 
+// must round exactly as detect_common.h's det_iou_gt does (both files are compiled with -ffp-contract=off): change them together
 __device__ __forceinline__ bool iou_gt(const float4 a, const float4 b, float thr)
 {
     const float left = fmaxf(a.x, b.x), right = fminf(a.z, b.z);
