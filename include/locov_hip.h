@@ -35,7 +35,7 @@ extern "C" {
 /* 8: locov_detect_postprocess; later, additively: locov_grounding_ce_dist_fwd / _bwd, locov_distill_loss_fwd / _bwd,
  *    locov_detect_postprocess_wide (+ _workspace_bytes), locov_regions_select / _gather_fwd / _gather_bwd,
  *    locov_detect_postprocess_cs / _wide_cs (+ _workspace_bytes), locov_grounding_align_fwd / _bwd,
- *    locov_grounding_triplet_fwd / _bwd */
+ *    locov_grounding_triplet_fwd / _bwd, locov_mha_fwd / _bwd */
 #define LOCOV_ABI_VERSION 8
 
 #define LOCOV_OK 0
@@ -1114,6 +1114,38 @@ int locov_regions_gather_fwd(const float *src, int layout, int64_t ld, int B, in
                              float *out, locov_stream_t stream);
 int locov_regions_gather_bwd(const float *grad_out, int layout, int64_t ld, int64_t rows, int C, int64_t hw, const int *inv,
                              float *grad_src, locov_stream_t stream);
+
+/* ---- fused multi-head self-attention core (csrc/mha.hip): TransformerHead's BERT layers ------------------------------------
+ * (ovr/modeling/mmss_heads/transformer_head.py:170-176 -> BertSelfAttention).  Added under ABI version 8.
+ *
+ *   ctx = dropout(softmax(Q K^T * scale + bias[n, key])) V      for every (sequence n < Nseq, head h < H)
+ *
+ *   q, k, v, ctx : fp32 [Nseq * S, H * d], row pitches ldq / ldk / ldv / ldo in floats (the operands may be column blocks of one
+ *                  [Nseq * S, 3 H d] matrix, or separate tensors); head h is columns [h * d, (h + 1) * d).
+ *   bias         : fp32 [Nseq, S], finite; added per key, broadcast over heads and queries (the reference passes its 0 / 1
+ *                  attention mask here, so padded keys are down-weighted, not excluded).
+ *   keep, p_drop : optional dropout: uint8 [Nseq, H, S, S] keep mask ([n][h][query][key]) drawn by the caller; kept
+ *                  probabilities are multiplied by 1 / (1 - p_drop).  keep == NULL: no dropout (p_drop is not read).
+ *   lse          : out, fp32 [Nseq, H, S]: log-sum-exp of the biased, scaled scores of each query (what the backward reads).
+ *   Products on v_mfma_f32_32x32x2_f32, softmax in fp32 with the running maximum subtracted; no S x S tensor is written.
+ *
+ * locov_mha_bwd: dq, dk, dv (pitches lddq / lddk / lddv) from dctx (pitch ldo) -- the probabilities are recomputed from q, k,
+ *   bias and lse with the same keep mask; ctx is not needed.  delta: fp32 [Nseq, H, S] scratch (sum_k P dP of each query row,
+ *   written by the first of the two launches, read by the second).  No atomics: each output row is summed by one wave in a fixed
+ *   order, so the result is bitwise reproducible.  No gradient for bias.
+ *
+ * Supported: 1 <= S <= LOCOV_MHA_MAX_S, d in {32, 64, 96, 128}, Nseq, H <= LOCOV_MHA_MAX_GRID; anything else is
+ *   LOCOV_ERR_UNSUPPORTED.  Pointers 16-byte aligned, pitches multiples of 4 floats and >= H * d, else LOCOV_ERR_INVALID_ARG.
+ *   Every check happens before the first launch; no host wait. */
+#define LOCOV_MHA_MAX_S 4096
+#define LOCOV_MHA_MAX_GRID 65535
+int locov_mha_fwd(const float *q, int64_t ldq, const float *k, int64_t ldk, const float *v, int64_t ldv, const float *bias,
+                  const uint8_t *keep, float p_drop, float scale, int nseq, int S, int H, int d, float *ctx, int64_t ldo,
+                  float *lse, locov_stream_t stream);
+int locov_mha_bwd(const float *q, int64_t ldq, const float *k, int64_t ldk, const float *v, int64_t ldv, const float *bias,
+                  const uint8_t *keep, float p_drop, float scale, int nseq, int S, int H, int d, const float *dctx,
+                  int64_t ldo, const float *lse, float *delta, float *dq, int64_t lddq, float *dk, int64_t lddk, float *dv,
+                  int64_t lddv, locov_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -36,6 +36,7 @@ BOX_IOU_GIOU, BOX_IOU_DIOU, BOX_IOU_CIOU = 0, 1, 2
 REGIONS_MAX_B, REGIONS_MAX_CANDIDATES = 64, 4096
 REGIONS_GRID, REGIONS_GRID_ALL, REGIONS_BOXES = 0, 1, 2
 REGIONS_ROWS, REGIONS_NCHW = 0, 1
+MHA_MAX_S, MHA_MAX_GRID, MHA_HEAD_DIMS = 4096, 65535, (32, 64, 96, 128)
 
 _p = c_void_p  # device pointer
 
@@ -198,6 +199,10 @@ SIGNATURES = {
                                      c_int, c_int, _p, _p, _p, _p, _p, _p, _p]),
     "locov_regions_gather_fwd": (c_int, [_p, c_int, c_int64, c_int, c_int, c_int, c_int64, _p, _p, _p]),
     "locov_regions_gather_bwd": (c_int, [_p, c_int, c_int64, c_int64, c_int, c_int64, _p, _p, _p]),
+    "locov_mha_fwd": (c_int, [_p, c_int64, _p, c_int64, _p, c_int64, _p, _p, c_float, c_float, c_int, c_int, c_int, c_int, _p, c_int64,
+                              _p, _p]),
+    "locov_mha_bwd": (c_int, [_p, c_int64, _p, c_int64, _p, c_int64, _p, _p, c_float, c_float, c_int, c_int, c_int, c_int, _p,
+                              c_int64, _p, _p, _p, c_int64, _p, c_int64, _p, c_int64, _p]),
 }
 
 _lib = None

@@ -99,6 +99,19 @@ def get_cfg() -> CfgNode:
                     "LOCAL_METRIC": "dot", "GLOBAL_METRIC": "aligned_local", "ALIGNMENT": "softmax",
                     "ALIGNMENT_TEMPERATURE": 10.0,
                 },
+                "DISTILLATION_LOSS": False,                        # config.py:43; coco_lsm.yaml -> True
+                "TRANSFORMER": {                                   # config.py:66-102 (keys TransformerHead reads)
+                    "MVM_LOSS": "",                                # "", "reconstruction_error" or "contrastive_cross_entropy"
+                    "MVM_LOSS_NUM_NEGATIVE": 128,
+                    "MMM_LOSS": "",                                # "" or "cross_entropy"; coco_lsm.yaml -> "cross_entropy"
+                    "BERT_CONFIG": {
+                        "vocab_size": 30522, "hidden_size": 768, "num_hidden_layers": 12, "num_attention_heads": 12,
+                        "intermediate_size": 3072, "hidden_act": "gelu", "hidden_dropout_prob": 0.1,
+                        "attention_probs_dropout_prob": 0.1, "max_position_embeddings": 512, "type_vocab_size": 2,
+                        "initializer_range": 0.02, "layer_norm_eps": 1e-12, "pad_token_id": 0, "gradient_checkpointing": False,
+                    },
+                    "pretrained_weights": False,
+                },
             },
             "ROI_BOX_HEAD": {
                 "NAME": "EmbeddingFastRCNNOutputLayers",

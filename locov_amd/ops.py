@@ -2396,3 +2396,118 @@ def regions_gather(src: torch.Tensor, selection: RegionSelection) -> torch.Tenso
     if rows != selection.inv.numel():
         raise ValueError(f"regions_gather: the selection is over {selection.inv.numel()} candidates, the features hold {rows}")
     return _RegionsGatherFn.apply(src, selection.src_row, selection.inv)
+
+
+# --------------------------------------------------------------------------------------
+# fused multi-head self-attention core (csrc/mha.hip)
+MHA_MAX_S = _lib.MHA_MAX_S            # LOCOV_MHA_MAX_S
+MHA_HEAD_DIMS = _lib.MHA_HEAD_DIMS    # the head dims locov_mha_fwd / _bwd are built for
+
+
+def _check_mha_args(fn: str, given: dict, key_bias, num_heads: int, keep, p_drop: float) -> None:
+    """The argument checks of mha and mha_packed.  given: the row operands ({"q": .., "k": .., "v": ..} | {"qkv": ..})."""
+    every = {**given, "key_bias": key_bias, **({"keep": keep} if keep is not None else {})}
+    if not all(isinstance(t, torch.Tensor) for t in every.values()):
+        raise TypeError(f"{fn}: {', '.join(every)} must be torch.Tensors")
+    first = next(iter(given.values()))
+    if not first.is_cuda or any(t.device != first.device for t in every.values()):
+        raise LocovError(f"{fn}: " + ", ".join(f"{n} on {t.device}" for n, t in every.items())
+                         + ": the kernel only runs on a ROCm GPU (there is no CPU fallback)")
+    want = {n: (torch.uint8 if n == "keep" else torch.float32) for n in every}
+    if any(t.dtype != want[n] for n, t in every.items()):
+        raise TypeError(f"{fn}: " + ", ".join(f"{n} must be {want[n]} (got {t.dtype})" for n, t in every.items()))
+    shapes = ", ".join(f"{n} {tuple(t.shape)}" for n, t in every.items())
+    parts = 3 if "qkv" in given else 1
+    H = int(num_heads)
+    if any(t.dim() != 2 for t in given.values()) or len({tuple(t.shape) for t in given.values()}) != 1 or key_bias.dim() != 2 or H < 1:
+        raise ValueError(f"{fn}: row operands [Nseq * S, {parts if parts > 1 else ''}{' * ' if parts > 1 else ''}H * d] and key_bias "
+                         f"[Nseq, S] with num_heads >= 1, got {shapes}, num_heads {num_heads}")
+    R, E = first.shape
+    nseq, S = key_bias.shape
+    if R != nseq * S or E % (parts * H) != 0:
+        raise ValueError(f"{fn}: {R} rows of {E} columns do not match key_bias [Nseq, S] = {tuple(key_bias.shape)} and num_heads {H}: "
+                         f"got {shapes}")
+    d = E // (parts * H)
+    if d not in MHA_HEAD_DIMS:
+        raise ValueError(f"{fn}: head dim must be one of {MHA_HEAD_DIMS}, got {d} ({shapes}, num_heads {H})")
+    if not 1 <= S <= MHA_MAX_S:
+        raise ValueError(f"{fn}: sequence length S must be in [1, {MHA_MAX_S}], got {S}")
+    if keep is not None and tuple(keep.shape) != (nseq, H, S, S):
+        raise ValueError(f"{fn}: keep must be uint8 [Nseq, H, S, S] = {(nseq, H, S, S)}, got {tuple(keep.shape)}")
+    if keep is not None and not 0.0 <= float(p_drop) < 1.0:
+        raise ValueError(f"{fn}: p_drop must be in [0, 1), got {p_drop}")
+
+
+class _MhaFn(torch.autograd.Function):
+    """locov_mha_fwd / locov_mha_bwd.  packed: `a` is one [R, 3 H d] matrix whose column blocks are Q, K, V (b, c are None) and the
+    backward returns ONE [R, 3 H d] gradient, written in place by the kernels."""
+
+    @staticmethod
+    def forward(ctx, a, b, c, key_bias, keep, H, scale, p_drop, packed):
+        a = _rows(a, "qkv" if packed else "q")
+        if packed:
+            E = a.shape[1] // 3
+            q, k, v = a[:, :E], a[:, E:2 * E], a[:, 2 * E:]
+        else:
+            q, k, v = a, _rows(b, "k"), _rows(c, "v")
+            E = q.shape[1]
+        bias = _dev(key_bias, "key_bias")
+        keep = _dev(keep, "keep", torch.uint8) if keep is not None else None
+        nseq, S = bias.shape
+        d = E // H
+        out = torch.empty((nseq * S, E), dtype=torch.float32, device=q.device)
+        lse = torch.empty((nseq, H, S), dtype=torch.float32, device=q.device)
+        with torch.cuda.device(q.device):
+            check(_lib.load().locov_mha_fwd(_ptr(q), q.stride(0), _ptr(k), k.stride(0), _ptr(v), v.stride(0), _ptr(bias), _ptr(keep),
+                                            float(p_drop), float(scale), nseq, S, H, d, _ptr(out), out.stride(0), _ptr(lse),
+                                            _stream(q)), "locov_mha_fwd")
+        ctx.save_for_backward(a if packed else q, k if not packed else None, v if not packed else None, bias, keep, lse)
+        ctx.args = (H, float(scale), float(p_drop), packed, nseq, S, d, E)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        a, k, v, bias, keep, lse = ctx.saved_tensors
+        H, scale, p_drop, packed, nseq, S, d, E = ctx.args
+        g = g if g.is_contiguous() else g.contiguous()
+        if packed:
+            q, k, v = a[:, :E], a[:, E:2 * E], a[:, 2 * E:]
+            grad = torch.empty_like(a, memory_format=torch.contiguous_format)
+            dq, dk, dv = grad[:, :E], grad[:, E:2 * E], grad[:, 2 * E:]
+        else:
+            q = a
+            dq, dk, dv = (torch.empty((nseq * S, E), dtype=torch.float32, device=q.device) for _ in range(3))
+        delta = torch.empty_like(lse)
+        with torch.cuda.device(q.device):
+            check(_lib.load().locov_mha_bwd(_ptr(q), q.stride(0), _ptr(k), k.stride(0), _ptr(v), v.stride(0), _ptr(bias), _ptr(keep),
+                                            p_drop, scale, nseq, S, H, d, _ptr(g), g.stride(0), _ptr(lse), _ptr(delta),
+                                            _ptr(dq), dq.stride(0), _ptr(dk), dk.stride(0), _ptr(dv), dv.stride(0), _stream(q)),
+                  "locov_mha_bwd")
+        if packed:
+            return grad, None, None, None, None, None, None, None, None
+        return dq, dk, dv, None, None, None, None, None, None
+
+
+def mha(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, key_bias: torch.Tensor, num_heads: int, *, scale: Optional[float] = None,
+        keep: Optional[torch.Tensor] = None, p_drop: float = 0.0) -> torch.Tensor:
+    """ctx = dropout(softmax(Q K^T * scale + key_bias[n, key])) V per (sequence, head), in one launch (locov_mha_fwd); differentiable
+    in q, k, v (locov_mha_bwd: two launches, no atomics, bitwise reproducible).  q, k, v [Nseq * S, H * d] fp32 on the device --
+    column blocks of a wider matrix are read in place (unit column stride, row pitch a multiple of 4, 16-byte aligned) -- key_bias
+    [Nseq, S] fp32 (finite, no gradient), d in MHA_HEAD_DIMS, S <= MHA_MAX_S, scale defaults to 1 / sqrt(d).  keep: optional uint8
+    [Nseq, H, S, S] dropout keep mask drawn by the caller; kept probabilities are multiplied by 1 / (1 - p_drop).  No S x S tensor is
+    allocated and nothing is read to the host."""
+    _check_mha_args("mha", {"q": q, "k": k, "v": v}, key_bias, num_heads, keep, p_drop)
+    H = int(num_heads)
+    scale = 1.0 / math.sqrt(q.shape[1] // H) if scale is None else float(scale)
+    return _MhaFn.apply(q, k, v, key_bias, keep, H, scale, float(p_drop), False)
+
+
+def mha_packed(qkv: torch.Tensor, key_bias: torch.Tensor, num_heads: int, *, scale: Optional[float] = None,
+               keep: Optional[torch.Tensor] = None, p_drop: float = 0.0) -> torch.Tensor:
+    """mha for Q, K, V that are the three column blocks of ONE [Nseq * S, 3 H d] matrix (one GEMM against the concatenated weight):
+    the blocks are read in place and the backward writes one [Nseq * S, 3 H d] gradient in place, with no slicing or summing."""
+    _check_mha_args("mha_packed", {"qkv": qkv}, key_bias, num_heads, keep, p_drop)
+    H = int(num_heads)
+    scale = 1.0 / math.sqrt(qkv.shape[1] // (3 * H)) if scale is None else float(scale)
+    return _MhaFn.apply(qkv, None, None, key_bias, keep, H, scale, float(p_drop), True)
