@@ -35,7 +35,7 @@ extern "C" {
 /* 8: locov_detect_postprocess; later, additively: locov_grounding_ce_dist_fwd / _bwd, locov_distill_loss_fwd / _bwd,
  *    locov_detect_postprocess_wide (+ _workspace_bytes), locov_regions_select / _gather_fwd / _gather_bwd,
  *    locov_detect_postprocess_cs / _wide_cs (+ _workspace_bytes), locov_grounding_align_fwd / _bwd,
- *    locov_grounding_triplet_fwd / _bwd, locov_mha_fwd / _bwd */
+ *    locov_grounding_triplet_fwd / _bwd, locov_mha_fwd / _bwd, locov_rpn_proposals (+ _workspace_bytes) */
 #define LOCOV_ABI_VERSION 8
 
 #define LOCOV_OK 0
@@ -684,6 +684,44 @@ int locov_detect_postprocess_wide_cs(const float *probs, int64_t ld_probs, int n
                                      float wx, float wy, float ww, float wh, float scale_clamp, float score_thresh, float nms_thresh, int topk,
                                      int per_class_above, void *workspace, int64_t workspace_bytes, float *out_boxes, float *out_scores,
                                      int64_t *out_classes, int64_t *out_rows, int *counts_and_flags, locov_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
+ * a-10d the RPN's proposal generation of one feature level, on the device, without a host read.  Replaces the torch-op chain of
+ * [D2-upstream] RPN.predict_proposals -> find_top_rpn_proposals (top-k, gather, Box2BoxTransform.apply_deltas, the finite test,
+ * Boxes.clip, nonempty, torchvision's batched_nms, slice) as the reference reaches it: the evaluation call OvrRCNN.inference
+ * (ovr/modeling/meta_arch/ovr_rcnn.py:76-124, backbone -> proposal_generator -> roi_heads) and the STT fine-tune's proposals
+ * (ovr/modeling/meta_arch/distill_prop_mmss_gcnn.py:243-246,508-509).  The reference tree has no RPN source of its own; the
+ * operation is restated from public sources.  Per image n:
+ *   candidates: all hwa anchors, flat index i = (y W + x) A + a (the order of an NHWC head output);
+ *   selection: descending logit, then ascending i (-0.0 and +0.0 compare equal; outputs carry the original bits); the first
+ *     P = min(hwa, pre_nms_topk) -- the stable descending sort, where torch.topk leaves the order of ties open;
+ *   box = apply_deltas(deltas[n, i], anchors[i]) with weights (wx, wy, ww, wh) and scale_clamp; a selected logit or a component of a
+ *     selected decoded box that is inf / NaN (before clipping) raises LOCOV_RPN_FLAG_NONFINITE -- it is raised for ANY non-finite
+ *     logit of the image, selected or not; the outputs are then not to be used (the caller runs the torch chain);
+ *   clip to the image's (h, w); boxes whose width or height is not > min_box_size are dropped (they suppress nothing);
+ *   greedy NMS in selection order: a box is dropped when IoU(kept, box) > nms_thresh for an earlier kept box;
+ *   the first post_nms_topk survivors, in order.
+ *   logits [n_images, hwa], deltas [n_images, hwa, 4] (16-byte aligned), anchors [hwa, 4] (16-byte aligned) fp32; image_hw:
+ *   n_images HOST (height, width) pairs.
+ *   out_boxes [n_images, post_nms_topk, 4] (16-byte aligned), out_logits [n_images, post_nms_topk] fp32, out_index
+ *   [n_images, post_nms_topk] int64 (the flat i); rows at or beyond an image's count are zero (boxes 0, logits 0, index -1);
+ *   counts_and_flags [n_images + 1] int32: survivors written per image, then the flag word.
+ *   Limits, checked before any HIP call: 1 <= post_nms_topk <= pre_nms_topk <= 16 384, hwa < 2^22, at most LOCOV_LABEL_MAX_IMAGES
+ *   images; n_images == 0 or hwa == 0 is a no-op success.
+ *   workspace: locov_rpn_proposals_workspace_bytes(n_images, hwa, pre_nms_topk) bytes, from host data only.  With
+ *   W = ceil(min(hwa, pre_nms_topk) / 64):
+ *       n_images (512 W^2 + 1 544 W)
+ *   (per image 64 W selection slots of a box, a logit and an index, W words of size-filter bits, and the 64 W x W words of the
+ *   overlap bit matrix: 18 MB at 12 000 boxes).  0 for empty input; < 0 on an argument error.
+ * ------------------------------------------------------------------------------------- */
+#define LOCOV_RPN_FLAG_NONFINITE 1
+#define LOCOV_RPN_MAX_PRE_NMS_TOPK 16384
+int64_t locov_rpn_proposals_workspace_bytes(int n_images, int64_t hwa, int pre_nms_topk);
+
+int locov_rpn_proposals(const float *logits, const float *deltas, const float *anchors, int64_t hwa, const float *image_hw, int n_images,
+                        float wx, float wy, float ww, float wh, float scale_clamp, int pre_nms_topk, int post_nms_topk, float min_box_size,
+                        float nms_thresh, void *workspace, int64_t workspace_bytes, float *out_boxes, float *out_logits, int64_t *out_index,
+                        int *counts_and_flags, locov_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * a-12  LSM grounding: word<->region alignment -> [caption, image] cost matrices.

@@ -28,6 +28,7 @@ ZERO_LIST_MAX = 24
 LABEL_MAX_IMAGES, LABEL_MAX_THRESHOLDS, SAMPLE_MAX_PROPOSALS = 64, 6, 4096
 ABI_VERSION = 8
 DETECT_MAX_CANDIDATES, DETECT_FLAG_NONFINITE, DETECT_FLAG_OVERFLOW = 8192, 1, 2
+RPN_FLAG_NONFINITE, RPN_MAX_PRE_NMS_TOPK, RPN_MAX_ANCHORS = 1, 16384, (1 << 22) - 1
 FED_LOSS_MAX_CLASSES = 32767
 DISTILL_KD, DISTILL_JS, DISTILL_MSE, DISTILL_MAX_B = 0, 1, 2, 64
 GROUNDING_ALIGN_SOFTMAX, GROUNDING_ALIGN_HARDMAX = 0, 1
@@ -128,6 +129,9 @@ SIGNATURES = {
     "locov_detect_postprocess_wide_cs": (c_int, [_p, c_int64, c_int, _p, c_int64, c_int, _p, POINTER(c_int), POINTER(c_float), c_int, c_float,
                                                  c_float, c_float, c_float, c_float, c_float, c_float, c_int, c_int, _p, c_int64, _p, _p, _p,
                                                  _p, _p, _p]),
+    "locov_rpn_proposals_workspace_bytes": (c_int64, [c_int, c_int64, c_int]),
+    "locov_rpn_proposals": (c_int, [_p, _p, _p, c_int64, POINTER(c_float), c_int, c_float, c_float, c_float, c_float, c_float, c_int, c_int,
+                                    c_float, c_float, _p, c_int64, _p, _p, _p, _p, _p]),
     "locov_grounding_fwd": (c_int, [_p, c_int, c_int, c_int, _p, _p, c_float, _p, _p, _p]),
     "locov_grounding_bwd": (c_int, [_p, c_int, c_int, c_int, _p, _p, c_float, _p, _p, _p, _p]),
     "locov_grounding_align_fwd": (c_int, [_p, c_int, c_int, c_int, _p, _p, c_float, c_int, _p, _p, _p]),

@@ -37,6 +37,7 @@ FILE_FLAGS = {
     "box_iou_loss.hip": ["-ffp-contract=off"],   # (fp64 row arithmetic, each step rounded on its own)
     "detect.hip":["-ffp-contract=off"],         # (box decoding / shifted IoU as the torch ops round them)
     "detect_wide.hip": ["-ffp-contract=off"],    # (the same, at any candidate count)
+    "rpn.hip": ["-ffp-contract=off"],            # (the same decoding and IoU, through detect_common.h)
     "mha.hip": ["-ffp-contract=off"],            # (dP - delta must cancel exactly where one key holds a row: no fused dP * keep - delta)
     "nms.hip": ["-ffp-contract=off"],            # (iou_gt must round as detect_common.h's det_iou_gt: the bit-identity tests)
 }

@@ -78,6 +78,20 @@ def get_cfg() -> CfgNode:
             "MASK_ON": False,
             "KEYPOINT_ON": False,
             "LOAD_EMB_PRED_FROM_MMSS_HEAD": False,                # config.py:13
+            "PROPOSAL_GENERATOR": {"NAME": "RPN", "MIN_SIZE": 0},     # [D2-upstream]
+            "ANCHOR_GENERATOR": {                                  # [D2-upstream]
+                "NAME": "DefaultAnchorGenerator",
+                "SIZES": [[32, 64, 128, 256, 512]], "ASPECT_RATIOS": [[0.5, 1.0, 2.0]], "OFFSET": 0.0,
+            },
+            "RPN": {                                               # [D2-upstream]; coco_lsm.yaml -> PRE_NMS_TOPK_TEST 6000
+                "HEAD_NAME": "StandardRPNHead",
+                "IN_FEATURES": ["res4"],
+                "BBOX_REG_WEIGHTS": (1.0, 1.0, 1.0, 1.0),
+                "PRE_NMS_TOPK_TRAIN": 12000, "PRE_NMS_TOPK_TEST": 6000,
+                "POST_NMS_TOPK_TRAIN": 2000, "POST_NMS_TOPK_TEST": 1000,
+                "NMS_THRESH": 0.7,
+                "CONV_DIMS": [-1],
+            },
             "ROI_HEADS": {
                 "NAME": "EmbeddingRes5ROIHeads",
                 "IN_FEATURES": ["res4"],                           # [D2-upstream]

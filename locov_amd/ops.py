@@ -872,17 +872,23 @@ def _detect_postprocess_flags(probs, deltas, proposal_boxes, sizes, image_shapes
                                                     per_class_above, _ptr(ws), ws.numel(), _ptr(out_boxes), _ptr(out_scores),
                                                     _ptr(out_classes), _ptr(out_rows), _ptr(counts), _stream(probs)),
                   "locov_detect_postprocess_wide")
-    # the ONE host read: B + 1 ints to pinned memory behind an event (the stream's later work stays queued)
+    vals = _read_counts_and_flags(counts)
+    return (out_boxes, out_scores, out_classes, out_rows, vals[:B]), vals[B]
+
+
+def _read_counts_and_flags(counts: torch.Tensor) -> list:
+    """The ONE host read of a post-processing call: its B + 1 ints to pinned memory behind an event (the stream's later work
+    stays queued)."""
+    dev, n = counts.device, counts.numel()
     key = (dev, torch.cuda.current_stream(dev).cuda_stream)
     host = _DETECT_PINNED.get(key)
-    if host is None or host.numel() < B + 1:
-        host = _DETECT_PINNED[key] = torch.empty(max(B + 1, DETECT_MAX_IMAGES + 1), dtype=torch.int32).pin_memory()
-    host[:B + 1].copy_(counts, non_blocking=True)
+    if host is None or host.numel() < n:
+        host = _DETECT_PINNED[key] = torch.empty(max(n, DETECT_MAX_IMAGES + 1), dtype=torch.int32).pin_memory()
+    host[:n].copy_(counts, non_blocking=True)
     ev = torch.cuda.Event()
     ev.record(torch.cuda.current_stream(dev))
     ev.synchronize()
-    vals = host[:B + 1].tolist()
-    return (out_boxes, out_scores, out_classes, out_rows, vals[:B]), vals[B]
+    return host[:n].tolist()
 
 
 def detect_postprocess_wide(probs: torch.Tensor, deltas: torch.Tensor, proposal_boxes: torch.Tensor, sizes, image_shapes, weights,
@@ -894,6 +900,57 @@ def detect_postprocess_wide(probs: torch.Tensor, deltas: torch.Tensor, proposal_
     out, flags = _detect_postprocess_flags(probs, deltas, proposal_boxes, sizes, image_shapes, weights, scale_clamp, score_thresh,
                                            nms_thresh, topk, per_class_above=per_class_above)
     return None if flags else out
+
+
+RPN_MAX_IMAGES, RPN_MAX_PRE_NMS_TOPK, RPN_MAX_ANCHORS = _lib.LABEL_MAX_IMAGES, _lib.RPN_MAX_PRE_NMS_TOPK, _lib.RPN_MAX_ANCHORS
+
+
+def rpn_proposals(logits: torch.Tensor, deltas: torch.Tensor, anchors: torch.Tensor, image_shapes, weights, scale_clamp: float,
+                  pre_nms_topk: int, post_nms_topk: int, min_box_size: float, nms_thresh: float):
+    """The RPN's proposal generation of one feature level on the device (csrc/rpn.hip): the pre_nms_topk best anchors per image
+    (descending logit, ties by anchor index), box decoding, the finite test, clipping, the size filter, greedy NMS and the first
+    post_nms_topk survivors -- three launches and ONE host read (the proposals per image + the flag word).
+    logits [N, HWA], deltas [N, HWA, 4], anchors [HWA, 4] in the (y, x, a) order of an NHWC head output; image_shapes: (height,
+    width) per image; weights: Box2BoxTransform's.
+    Returns (boxes [N, post, 4], logits [N, post], index [N, post] int64, counts: list of N ints); rows at or beyond an image's
+    count are zero (index -1).  None when the kernels flagged non-finite values: the caller then runs the torch chain."""
+    out, flags = _rpn_proposals_flags(logits, deltas, anchors, image_shapes, weights, scale_clamp, pre_nms_topk, post_nms_topk,
+                                      min_box_size, nms_thresh)
+    return None if flags else out
+
+
+def _rpn_proposals_flags(logits, deltas, anchors, image_shapes, weights, scale_clamp, pre_nms_topk, post_nms_topk, min_box_size,
+                         nms_thresh):
+    """rpn_proposals's work, with the flag word (RPN_FLAG_NONFINITE) returned next to the outputs instead of folded into None."""
+    logits, deltas, anchors = _dev(logits, "logits"), _dev(deltas, "deltas"), _dev(anchors, "anchors")
+    if logits.dim() != 2 or tuple(deltas.shape) != (*logits.shape, 4) or tuple(anchors.shape) != (logits.shape[1], 4) \
+            or len(image_shapes) != logits.shape[0]:
+        raise ValueError("rpn_proposals: inconsistent shapes (logits [N, HWA], deltas [N, HWA, 4], anchors [HWA, 4], N image shapes)")
+    N, HWA = logits.shape
+    pre, post = int(pre_nms_topk), int(post_nms_topk)
+    if not (N <= RPN_MAX_IMAGES and HWA <= RPN_MAX_ANCHORS and 1 <= post <= pre <= RPN_MAX_PRE_NMS_TOPK):
+        raise ValueError("rpn_proposals: outside the kernels' limits (images, anchors per image, 1 <= post <= pre <= 16 384)")
+    dev = logits.device
+    if N == 0 or HWA == 0:                  # (the C call is a no-op then: the empty rows are written here)
+        return (torch.zeros((N, post, 4), dtype=torch.float32, device=dev), torch.zeros((N, post), dtype=torch.float32, device=dev),
+                torch.full((N, post), -1, dtype=torch.int64, device=dev), [0] * N), 0
+    out_boxes = torch.empty((N, post, 4), dtype=torch.float32, device=dev)
+    out_logits = torch.empty((N, post), dtype=torch.float32, device=dev)
+    out_index = torch.empty((N, post), dtype=torch.int64, device=dev)
+    lib = _lib.load()
+    hw = (ctypes.c_float * (2 * N))(*[float(v) for shape in image_shapes for v in shape[:2]])
+    nbytes = int(lib.locov_rpn_proposals_workspace_bytes(N, HWA, pre))
+    if nbytes < 0:
+        check(nbytes, "locov_rpn_proposals_workspace_bytes")
+    ws = _workspace("rpn", logits, nbytes)
+    counts = torch.empty((N + 1,), dtype=torch.int32, device=dev)
+    wx, wy, ww, wh = (float(w) for w in weights)
+    with torch.cuda.device(dev):
+        check(lib.locov_rpn_proposals(_ptr(logits), _ptr(deltas), _ptr(anchors), HWA, hw, N, wx, wy, ww, wh, float(scale_clamp), pre, post,
+                                      float(min_box_size), float(nms_thresh), _ptr(ws), ws.numel(), _ptr(out_boxes), _ptr(out_logits),
+                                      _ptr(out_index), _ptr(counts), _stream(logits)), "locov_rpn_proposals")
+    vals = _read_counts_and_flags(counts)
+    return (out_boxes, out_logits, out_index, vals[:N]), vals[N]
 
 
 # --------------------------------------------------------------------------------------
