@@ -35,7 +35,8 @@ extern "C" {
 /* 8: locov_detect_postprocess; later, additively: locov_grounding_ce_dist_fwd / _bwd, locov_distill_loss_fwd / _bwd,
  *    locov_detect_postprocess_wide (+ _workspace_bytes), locov_regions_select / _gather_fwd / _gather_bwd,
  *    locov_detect_postprocess_cs / _wide_cs (+ _workspace_bytes), locov_grounding_align_fwd / _bwd,
- *    locov_grounding_triplet_fwd / _bwd, locov_mha_fwd / _bwd, locov_rpn_proposals (+ _workspace_bytes) */
+ *    locov_grounding_triplet_fwd / _bwd, locov_mha_fwd / _bwd, locov_rpn_proposals (+ _workspace_bytes),
+ *    locov_rpn_label_anchors (+ _workspace_bytes), locov_rpn_sample_anchors, locov_rpn_loss (+ _workspace_bytes) */
 #define LOCOV_ABI_VERSION 8
 
 #define LOCOV_OK 0
@@ -722,6 +723,64 @@ int locov_rpn_proposals(const float *logits, const float *deltas, const float *a
                         float wx, float wy, float ww, float wh, float scale_clamp, int pre_nms_topk, int post_nms_topk, float min_box_size,
                         float nms_thresh, void *workspace, int64_t workspace_bytes, float *out_boxes, float *out_logits, int64_t *out_index,
                         int *counts_and_flags, locov_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
+ * a-10e the RPN's training half of one feature level on the device, without a host read: anchor labelling, the sample draw and the
+ * two losses with their gradients.  Replaces the torch-op chains of [D2-upstream] RPN.label_and_sample_anchors (pairwise_iou, Matcher
+ * with allow_low_quality_matches, Boxes.inside_box, subsample_labels) and RPN.losses (binary_cross_entropy_with_logits over the
+ * sampled anchors, Box2BoxTransform.get_deltas + smooth_l1_loss over the sampled positives), which the reference runs in every
+ * detection step (ovr/modeling/meta_arch/ovr_rcnn.py:54-73, distill_prop_mmss_gcnn.py:243-267,595-616).  The reference tree has no
+ * RPN source of its own; the operation is restated from public sources.  The anchors [hwa, 4] (flat index i = (y W + x) A + a) are
+ * shared by the images of the batch.  Limits of all three, checked before any HIP call: at most LOCOV_LABEL_MAX_IMAGES images,
+ * hwa < 2^22; n_images == 0 or hwa == 0 is a no-op success.
+ *
+ * locov_rpn_label_anchors -- per image n and anchor i:
+ *   iou = pairwise_iou(gt box, anchor) in torch's operation order, every step rounded on its own; the matched box is the FIRST
+ *   maximum over the image's boxes; the label is the Matcher's: 1, overwritten by lab[k] of every interval lo[k] <= max < hi[k]
+ *   that holds; with allow_low_quality every anchor whose iou with some box of the image EQUALS that box's maximum over all anchors
+ *   becomes 1 (it keeps its first-maximum box; a box that overlaps no anchor has the maximum 0 and promotes every anchor that does
+ *   not touch it, as upstream); an image without ground truth: every label 0, matched boxes 0; boundary_thresh >= 0: anchors not
+ *   inside [-t, w + t) x [-t, h + t) get -1 (Boxes.inside_box; after the promotion).
+ *   anchors [hwa, 4], gt_boxes [sum M, 4] fp32 (16-byte aligned); gt_offsets_host: n_images + 1 HOST row offsets starting at 0;
+ *   image_hw_host: n_images HOST (height, width) pairs; thr_*_host: the Matcher's n_thresholds <= LOCOV_LABEL_MAX_THRESHOLDS intervals.
+ *   labels [n_images, hwa] int8 in {-1, 0, 1} (before the draw); matched_boxes [n_images, hwa, 4] fp32 (16-byte aligned);
+ *   counts [n_images, 4] int32: (anchors labelled 1, anchors labelled 0, -, -) -- the entry point zeroes all four.
+ *   workspace: locov_rpn_label_anchors_workspace_bytes(n_images, hwa, n_gt) = 16 ceil(n_gt / 4) bytes (one maximum per ground-truth
+ *   box; zeroed by the entry point), n_gt = sum M; 0 for empty input; < 0 on an argument error.
+ *
+ * locov_rpn_sample_anchors -- subsample_labels with background label 0, the randomness passed in: rnd [2, n_images, hwa] float64
+ *   uniforms in [0, 1).  num_pos = min(#label 1, max_pos) anchors of label 1 with the smallest rnd[0] stay 1, then
+ *   num_neg = min(#label 0, budget - num_pos) anchors of label 0 with the smallest rnd[1] stay 0; equal keys are taken in ascending
+ *   anchor index; every other anchor becomes -1.  labels / counts: locov_rpn_label_anchors' outputs; out_labels [n_images, hwa] int8
+ *   (must not alias labels); counts[n, 2] = num_pos, counts[n, 3] = num_neg are written.  Requires 0 <= max_pos <= budget.
+ *
+ * locov_rpn_loss -- one pass over logits [n_images, hwa], deltas [n_images, hwa, 4], labels (after the draw), anchors and
+ *   matched_boxes:
+ *     loss[0] = cls_scale * sum over labels >= 0 of max(x, 0) - x y + log1p(exp(-|x|)),  y = [label == 1]
+ *     loss[1] = loc_scale * sum over labels == 1 of smooth_l1(deltas - get_deltas(anchor, matched box); beta)  (beta < 1e-5: L1)
+ *     dlogits = cls_scale (sigmoid(x) - y) where label >= 0, else 0;  ddeltas = loc_scale d smooth_l1 where label == 1, else 0
+ *   (the caller folds the normaliser and the loss weights into the two scales).  Both gradients are written completely.  The sums
+ *   are fp64 per-block partials added in block order: the same inputs give the same bits.  flags[0] (zeroed by the entry point)
+ *   receives LOCOV_RPN_LOSS_FLAG_DEGENERATE when an anchor of label 1 has no positive width and height (Box2BoxTransform's assert).
+ *   deltas, anchors, matched_boxes, ddeltas 16-byte aligned.
+ *   workspace: locov_rpn_loss_workspace_bytes(n_images, hwa) = 16 n_images ceil(hwa / 256) bytes; < 0 on an argument error.
+ * ------------------------------------------------------------------------------------- */
+#define LOCOV_RPN_LOSS_FLAG_DEGENERATE 1
+int64_t locov_rpn_label_anchors_workspace_bytes(int n_images, int64_t hwa, int64_t n_gt);
+
+int locov_rpn_label_anchors(const float *anchors, int64_t hwa, const float *gt_boxes, const int *gt_offsets_host, const float *image_hw_host,
+                            int n_images, const float *thr_lo_host, const float *thr_hi_host, const int *thr_label_host, int n_thresholds,
+                            int allow_low_quality, float boundary_thresh, void *workspace, int64_t workspace_bytes, int8_t *labels,
+                            float *matched_boxes, int *counts, locov_stream_t stream);
+
+int locov_rpn_sample_anchors(const int8_t *labels, const double *rnd, int64_t hwa, int n_images, int budget, int max_pos, int *counts,
+                             int8_t *out_labels, locov_stream_t stream);
+
+int64_t locov_rpn_loss_workspace_bytes(int n_images, int64_t hwa);
+
+int locov_rpn_loss(const float *logits, const float *deltas, const int8_t *labels, const float *anchors, const float *matched_boxes,
+                   int64_t hwa, int n_images, float wx, float wy, float ww, float wh, float smooth_l1_beta, float cls_scale, float loc_scale,
+                   void *workspace, int64_t workspace_bytes, float *loss, float *dlogits, float *ddeltas, int *flags, locov_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * a-12  LSM grounding: word<->region alignment -> [caption, image] cost matrices.

@@ -29,6 +29,7 @@ LABEL_MAX_IMAGES, LABEL_MAX_THRESHOLDS, SAMPLE_MAX_PROPOSALS = 64, 6, 4096
 ABI_VERSION = 8
 DETECT_MAX_CANDIDATES, DETECT_FLAG_NONFINITE, DETECT_FLAG_OVERFLOW = 8192, 1, 2
 RPN_FLAG_NONFINITE, RPN_MAX_PRE_NMS_TOPK, RPN_MAX_ANCHORS = 1, 16384, (1 << 22) - 1
+RPN_LOSS_FLAG_DEGENERATE = 1
 FED_LOSS_MAX_CLASSES = 32767
 DISTILL_KD, DISTILL_JS, DISTILL_MSE, DISTILL_MAX_B = 0, 1, 2, 64
 GROUNDING_ALIGN_SOFTMAX, GROUNDING_ALIGN_HARDMAX = 0, 1
@@ -132,6 +133,13 @@ SIGNATURES = {
     "locov_rpn_proposals_workspace_bytes": (c_int64, [c_int, c_int64, c_int]),
     "locov_rpn_proposals": (c_int, [_p, _p, _p, c_int64, POINTER(c_float), c_int, c_float, c_float, c_float, c_float, c_float, c_int, c_int,
                                     c_float, c_float, _p, c_int64, _p, _p, _p, _p, _p]),
+    "locov_rpn_label_anchors_workspace_bytes": (c_int64, [c_int, c_int64, c_int64]),
+    "locov_rpn_label_anchors": (c_int, [_p, c_int64, _p, POINTER(c_int), POINTER(c_float), c_int, POINTER(c_float), POINTER(c_float),
+                                        POINTER(c_int), c_int, c_int, c_float, _p, c_int64, _p, _p, _p, _p]),
+    "locov_rpn_sample_anchors": (c_int, [_p, _p, c_int64, c_int, c_int, c_int, _p, _p, _p]),
+    "locov_rpn_loss_workspace_bytes": (c_int64, [c_int, c_int64]),
+    "locov_rpn_loss": (c_int, [_p, _p, _p, _p, _p, c_int64, c_int, c_float, c_float, c_float, c_float, c_float, c_float, c_float, _p,
+                               c_int64, _p, _p, _p, _p, _p]),
     "locov_grounding_fwd": (c_int, [_p, c_int, c_int, c_int, _p, _p, c_float, _p, _p, _p]),
     "locov_grounding_bwd": (c_int, [_p, c_int, c_int, c_int, _p, _p, c_float, _p, _p, _p, _p]),
     "locov_grounding_align_fwd": (c_int, [_p, c_int, c_int, c_int, _p, _p, c_float, c_int, _p, _p, _p]),

@@ -91,6 +91,12 @@ def get_cfg() -> CfgNode:
                 "POST_NMS_TOPK_TRAIN": 2000, "POST_NMS_TOPK_TEST": 1000,
                 "NMS_THRESH": 0.7,
                 "CONV_DIMS": [-1],
+                # the training half: anchor labelling, the sample draw and the two losses
+                "IOU_THRESHOLDS": [0.3, 0.7], "IOU_LABELS": [0, -1, 1],
+                "BATCH_SIZE_PER_IMAGE": 256, "POSITIVE_FRACTION": 0.5,
+                "BOUNDARY_THRESH": -1,
+                "LOSS_WEIGHT": 1.0, "BBOX_REG_LOSS_WEIGHT": 1.0,
+                "BBOX_REG_LOSS_TYPE": "smooth_l1", "SMOOTH_L1_BETA": 0.0,
             },
             "ROI_HEADS": {
                 "NAME": "EmbeddingRes5ROIHeads",

@@ -16,7 +16,7 @@
 //
 // Built with -ffp-contract=off: each step is the torch op it replaces, rounded on its own; the sums run in a fixed order (one
 // workgroup, a fixed tree), so a step's losses are reproducible run to run.
-#include "common.h"
+#include "box_delta_common.h"
 
 namespace locov {
 
@@ -71,28 +71,14 @@ __global__ __launch_bounds__(kLossThreads) void box_reg_loss_kernel(const float4
         const int64_t col = agnostic ? 0 : (c < 0 ? 0 : (c >= num_classes ? num_classes - 1 : c)) * 4;
         float g[4] = {0.f, 0.f, 0.f, 0.f};
         if (fg) {
-            const float4 s = src[r], t = tgt[r];
-            // Box2BoxTransform.get_deltas, op by op
-            const float sw = s.z - s.x, sh = s.w - s.y;
-            const float scx = s.x + 0.5f * sw, scy = s.y + 0.5f * sh;
-            const float tw = t.z - t.x, th = t.w - t.y;
-            const float tcx = t.x + 0.5f * tw, tcy = t.y + 0.5f * th;
-            const float d[4] = {wx * (tcx - scx) / sw, wy * (tcy - scy) / sh, ww * logf(tw / sw), wh * logf(th / sh)};
+            // Box2BoxTransform.get_deltas and fvcore's smooth_l1_loss, op by op (box_delta_common.h)
+            float d[4];
+            box_get_deltas(src[r], tgt[r], wx, wy, ww, wh, d);
             const float *p = pred + r * ld + col;
 #pragma unroll
             for (int j = 0; j < 4; j++) {
-                const float e = p[j] - d[j], a = fabsf(e);
-                float l, de;                                  // fvcore smooth_l1_loss (beta < 1e-5: plain L1) and its derivative in e
-                if (beta < 1e-5f) {
-                    l = a;
-                    de = e > 0.f ? 1.f : (e < 0.f ? -1.f : 0.f);
-                } else if (a < beta) {
-                    l = 0.5f * (a * a) / beta;
-                    de = e / beta;
-                } else {
-                    l = a - 0.5f * beta;
-                    de = e > 0.f ? 1.f : (e < 0.f ? -1.f : 0.f);
-                }
+                float l, de;
+                smooth_l1_term(p[j] - d[j], beta, l, de);
                 part = part + l;
                 g[j] = de / n;
             }

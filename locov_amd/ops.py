@@ -1408,6 +1408,121 @@ def sample_proposals(key_pos: torch.Tensor, key_neg: torch.Tensor, labels: torch
     return picked, out_boxes, classes, out_gt, fg, rois, field_out
 
 
+RPN_LOSS_FLAG_DEGENERATE = _lib.RPN_LOSS_FLAG_DEGENERATE
+
+
+def _check_rpn_train_limits(fn: str, N: int, HWA: int) -> None:
+    if N > RPN_MAX_IMAGES or HWA > RPN_MAX_ANCHORS:
+        raise ValueError(f"{fn}: outside the kernels' limits (at most {RPN_MAX_IMAGES} images, fewer than 2^22 anchors per image)")
+
+
+def rpn_label_anchors(anchors: torch.Tensor, gt_boxes: Optional[torch.Tensor], n_gt, image_shapes, thresholds, labels_of,
+                      allow_low_quality: bool = True, boundary_thresh: float = -1.0):
+    """The RPN's anchor labelling of a batch on the device (locov_rpn_label_anchors, csrc/rpn_train.hip): pairwise_iou, the Matcher
+    with its low-quality rule, the boundary test -- two launches, no [num_gt, HWA] matrix, no host read.
+    anchors [HWA, 4] fp32 (shared by the images); gt_boxes [sum M, 4] fp32 concatenated over the images (None when there are none);
+    n_gt: per-image counts (host ints); image_shapes: (height, width) per image; thresholds: the Matcher's [-inf, t1, ..., inf];
+    labels_of: its interval labels.
+    Returns (labels [N, HWA] int8 before the draw, matched boxes [N, HWA, 4], counts [N, 4] int32 = (#1, #0, 0, 0))."""
+    anchors = _dev(anchors, "anchors")
+    N, HWA, total = len(n_gt), anchors.shape[0], int(sum(n_gt))
+    if anchors.dim() != 2 or anchors.shape[1] != 4 or len(image_shapes) != N:
+        raise ValueError("rpn_label_anchors: anchors [HWA, 4], one (height, width) per image")
+    _check_rpn_train_limits("rpn_label_anchors", N, HWA)
+    if len(labels_of) > LABEL_MAX_THRESHOLDS or len(thresholds) != len(labels_of) + 1:
+        raise ValueError("rpn_label_anchors: too many matcher intervals, or thresholds / labels that do not pair up")
+    gt_boxes = _dev(gt_boxes, "gt_boxes") if total else None
+    if total and tuple(gt_boxes.shape) != (total, 4):
+        raise ValueError("rpn_label_anchors: gt_boxes must be [sum(n_gt), 4]")
+    dev = anchors.device
+    labels = torch.empty((N, HWA), dtype=torch.int8, device=dev)
+    matched = torch.empty((N, HWA, 4), dtype=torch.float32, device=dev)
+    counts = torch.zeros((N, 4), dtype=torch.int32, device=dev)
+    if N == 0 or HWA == 0:
+        return labels, matched, counts
+    lib = _lib.load()
+    goff = (ctypes.c_int * (N + 1))(*([0] + list(itertools.accumulate(int(n) for n in n_gt))))
+    hw = (ctypes.c_float * (2 * N))(*[float(v) for shape in image_shapes for v in shape[:2]])
+    nt = len(labels_of)
+    lo = (ctypes.c_float * max(nt, 1))(*[float(v) for v in thresholds[:-1]])
+    hi = (ctypes.c_float * max(nt, 1))(*[float(v) for v in thresholds[1:]])
+    lab = (ctypes.c_int * max(nt, 1))(*[int(v) for v in labels_of])
+    nbytes = int(lib.locov_rpn_label_anchors_workspace_bytes(N, HWA, total))
+    if nbytes < 0:
+        check(nbytes, "locov_rpn_label_anchors_workspace_bytes")
+    ws = _workspace("rpn_label", anchors, nbytes)
+    with torch.cuda.device(dev):
+        check(lib.locov_rpn_label_anchors(_ptr(anchors), HWA, _ptr(gt_boxes), goff, hw, N, lo, hi, lab, nt, int(bool(allow_low_quality)),
+                                          float(boundary_thresh), _ptr(ws), ws.numel(), _ptr(labels), _ptr(matched), _ptr(counts),
+                                          _stream(anchors)), "locov_rpn_label_anchors")
+    return labels, matched, counts
+
+
+def rpn_sample_anchors(labels: torch.Tensor, counts: torch.Tensor, rnd: torch.Tensor, budget: int, max_pos: int) -> torch.Tensor:
+    """subsample_labels behind rpn_label_anchors, on the device (locov_rpn_sample_anchors): per image the min(#1, max_pos) positives
+    of smallest rnd[0] stay 1, the min(#0, budget - num_pos) negatives of smallest rnd[1] stay 0 (equal keys in anchor order),
+    everything else becomes -1 -- one launch, no host read.  labels [N, HWA] int8 and counts [N, 4] int32 from rpn_label_anchors;
+    rnd [2, N, HWA] float64 uniforms in [0, 1).  Returns the final labels [N, HWA] int8; counts[:, 2:] receive (num_pos, num_neg)."""
+    labels, counts, rnd = _dev(labels, "labels", torch.int8), _dev(counts, "counts", torch.int32), _dev(rnd, "rnd", torch.float64)
+    if labels.dim() != 2 or tuple(counts.shape) != (labels.shape[0], 4) or tuple(rnd.shape) != (2, *labels.shape):
+        raise ValueError("rpn_sample_anchors: labels [N, HWA] int8, counts [N, 4] int32, rnd [2, N, HWA] float64")
+    N, HWA = labels.shape
+    _check_rpn_train_limits("rpn_sample_anchors", N, HWA)
+    if not 0 <= int(max_pos) <= int(budget):
+        raise ValueError("rpn_sample_anchors: 0 <= max_pos <= budget")
+    out = torch.empty_like(labels)
+    with torch.cuda.device(labels.device):
+        check(_lib.load().locov_rpn_sample_anchors(_ptr(labels), _ptr(rnd), HWA, N, int(budget), int(max_pos), _ptr(counts), _ptr(out),
+                                                   _stream(labels)), "locov_rpn_sample_anchors")
+    return out
+
+
+class _RpnLossFn(torch.autograd.Function):
+    """locov_rpn_loss: both losses and both gradients from ONE pass; backward scales the saved gradients by the incoming [2]."""
+
+    @staticmethod
+    def forward(ctx, logits, deltas, labels, anchors, matched, weights, beta, cls_scale, loc_scale):
+        logits, deltas = _dev(logits, "logits"), _dev(deltas, "deltas")
+        labels, anchors, matched = _dev(labels, "labels", torch.int8), _dev(anchors, "anchors"), _dev(matched, "matched_boxes")
+        N, HWA = logits.shape
+        dev = logits.device
+        loss = torch.zeros(2, dtype=torch.float32, device=dev)
+        flags = torch.zeros(1, dtype=torch.int32, device=dev)
+        dlogits, ddeltas = torch.empty_like(logits), torch.empty_like(deltas)
+        lib = _lib.load()
+        nbytes = int(lib.locov_rpn_loss_workspace_bytes(N, HWA))
+        if nbytes < 0:
+            check(nbytes, "locov_rpn_loss_workspace_bytes")
+        ws = _workspace("rpn_loss", logits, nbytes)
+        with torch.cuda.device(dev):
+            check(lib.locov_rpn_loss(_ptr(logits), _ptr(deltas), _ptr(labels), _ptr(anchors), _ptr(matched), HWA, N,
+                                     *(float(w) for w in weights), float(beta), float(cls_scale), float(loc_scale), _ptr(ws), ws.numel(),
+                                     _ptr(loss), _ptr(dlogits), _ptr(ddeltas), _ptr(flags), _stream(logits)), "locov_rpn_loss")
+        ctx.grads = (dlogits, ddeltas)
+        ctx.mark_non_differentiable(flags)
+        return loss, flags
+
+    @staticmethod
+    def backward(ctx, g, _):
+        dlogits, ddeltas = ctx.grads
+        return (dlogits * g[0] if ctx.needs_input_grad[0] else None, ddeltas * g[1] if ctx.needs_input_grad[1] else None,
+                None, None, None, None, None, None, None)
+
+
+def rpn_loss(logits: torch.Tensor, deltas: torch.Tensor, labels: torch.Tensor, anchors: torch.Tensor, matched_boxes: torch.Tensor,
+             weights, smooth_l1_beta: float, cls_scale: float, loc_scale: float):
+    """[D2-upstream] RPN.losses in one pass (locov_rpn_loss): loss[0] = cls_scale * sum over labels >= 0 of the objectness
+    cross-entropy, loss[1] = loc_scale * sum over labels == 1 of smooth-L1(deltas - get_deltas(anchor, matched box)) -- the caller
+    folds the normaliser and the loss weights into the two scales.  logits [N, HWA], deltas [N, HWA, 4], labels [N, HWA] int8 (after
+    the draw), anchors [HWA, 4], matched_boxes [N, HWA, 4].  Differentiable in logits and deltas; reproducible bit for bit.
+    Returns (loss [2], flags [1] int32: RPN_LOSS_FLAG_DEGENERATE when a positive anchor has no positive width and height)."""
+    if logits.dim() != 2 or tuple(deltas.shape) != (*logits.shape, 4) or tuple(labels.shape) != tuple(logits.shape) \
+            or tuple(anchors.shape) != (logits.shape[1], 4) or tuple(matched_boxes.shape) != tuple(deltas.shape):
+        raise ValueError("rpn_loss: logits [N, HWA], deltas [N, HWA, 4], labels [N, HWA], anchors [HWA, 4], matched_boxes [N, HWA, 4]")
+    _check_rpn_train_limits("rpn_loss", *logits.shape)
+    return _RpnLossFn.apply(logits.float(), deltas.float(), labels, anchors, matched_boxes, tuple(weights), smooth_l1_beta, cls_scale, loc_scale)
+
+
 def zero_if_raised(tensors, word: torch.Tensor) -> None:
     """Zero-fill every tensor of `tensors` (contiguous fp32 device tensors, None entries skipped) ON THE DEVICE when the
     range-guard word `word` is set; a no-op launch otherwise.  No host read (locov_zero_if_raised)."""

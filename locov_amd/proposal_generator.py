@@ -10,7 +10,15 @@ proposal_generator.rpn_head.{conv,objectness_logits,anchor_deltas}.{weight,bias}
 Proposal generation of a single feature level (what the reference uses: RPN.IN_FEATURES ["res4"]) is ONE device operation,
 ops.rpn_proposals (csrc/rpn.hip).  In predict_proposals several levels, CPU tensors, LOCOV_FUSED_RPN=0 and non-finite predictions
 take the torch chain of this file, which computes the same proposals.  The head itself (and so RPN.forward) needs device tensors:
-it has no torch fallback.  The RPN's training losses are not part of this module yet.
+it has no torch fallback.
+
+Training ([D2-upstream] RPN.label_and_sample_anchors, RPN.losses): RPN.forward with targets labels the anchors (Matcher with
+low-quality matches, the boundary test), draws the 256-anchor sample and forms loss_rpn_cls / loss_rpn_loc.  One feature level on
+device tensors is three device operations (ops.rpn_label_anchors, ops.rpn_sample_anchors, ops.rpn_loss: csrc/rpn_train.hip) that
+read nothing back; several levels, CPU tensors, LOCOV_FUSED_RPN=0 and sizes beyond the kernels' limits take the torch chain of this
+file, which returns the same labels and matched boxes for the same `rnd` (the uniforms of the draw, [2, N, HWA] float64: the
+num_pos positives of smallest rnd[0], then the negatives of smallest rnd[1], equal keys in anchor order).  With grad enabled the
+head builds a graph over the same kernels (the 3x3 layer: _Conv3x3ReluFn; the 1x1 pair: ops.linear_autograd).
 """
 from __future__ import annotations
 
@@ -23,8 +31,10 @@ from torch import nn
 
 from . import ops
 from .registry import Registry, configurable
+from .res5_train import _wino_ok
 from .roi_heads.box_emb_head import Box2BoxTransform, batched_nms
-from .structures import Boxes, Instances, ShapeSpec
+from .roi_heads.labelling import Matcher, get_event_storage
+from .structures import Boxes, Instances, ShapeSpec, pairwise_iou
 
 __all__ = ["DefaultAnchorGenerator", "StandardRPNHead", "RPN", "build_proposal_generator", "build_anchor_generator", "build_rpn_head",
            "find_top_rpn_proposals", "PROPOSAL_GENERATOR_REGISTRY", "ANCHOR_GENERATOR_REGISTRY", "RPN_HEAD_REGISTRY"]
@@ -114,6 +124,39 @@ class DefaultAnchorGenerator(nn.Module):
         return [Boxes(self._grid_anchors(i, f.shape[-2:])) for i, f in enumerate(features)]
 
 
+class _Conv3x3ReluFn(torch.autograd.Function):
+    """relu(conv3x3(rows) + bias) over N channels-last H x W maps, differentiable in rows, weight and bias.  Forward: the implicit-GEMM
+    kernel on the packed weight (what the no_grad path runs: the same bits).  Backward, from kernels the Res5 stage already uses:
+    the ReLU mask on the incoming gradient; the data gradient as the same convolution with the flipped filter; the weight gradient in
+    the Winograd domain on 7 x 7 maps, else g^T . im2col(rows) on the TN GEMM; the bias gradient a column sum."""
+
+    @staticmethod
+    def forward(ctx, rows, weight, bias, w_packed, shift, H, W):
+        y = ops.conv3x3_nhwc_ex(rows, w_packed, H, W, shift=shift, relu=True)
+        ctx.save_for_backward(rows, weight, y)
+        ctx.hw = (H, W)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        rows, weight, y = ctx.saved_tensors
+        H, W = ctx.hw
+        cout, cin = weight.shape[:2]
+        g = ops.relu_mask(g.contiguous(), y)
+        gx = gw = gb = None
+        if ctx.needs_input_grad[0]:
+            flipped = ops.conv3x3_weight_flip(weight.detach().float().contiguous())
+            gx = ops.conv3x3_nhwc_ex(g, ops.pack_conv3x3_weight(flipped), H, W)
+        if ctx.needs_input_grad[1]:
+            if _wino_ok(H, W, cin, cout):
+                gw = ops.winograd_wgrad(rows, g, roi_major=True)
+            else:
+                gw = ops.conv3x3_wgrad_unpack(ops.gemm_tn(g, ops.im2col3x3(rows, H, W)))
+        if ctx.needs_input_grad[2]:
+            gb = g.sum(dim=0)
+        return gx, gw, gb, None, None, None, None
+
+
 @RPN_HEAD_REGISTRY.register()
 class StandardRPNHead(nn.Module):
     """[D2-upstream] 3x3 conv + ReLU, then two 1x1 layers: an objectness logit and box_dim deltas per anchor.  The 3x3 runs on the
@@ -160,6 +203,13 @@ class StandardRPNHead(nn.Module):
         A + a box_dim ...  The head runs on the kernels only: a CPU map is an error (ops raises LocovError), not a torch fallback."""
         N, C, H, W = x.shape
         w3, b3, w1, b1 = self._operands()
+        if torch.is_grad_enabled() and (x.requires_grad or (self.training and any(p.requires_grad for p in self.parameters()))):
+            # training (or an input that carries a graph; evaluation and no_grad keep the detached path below): the same two kernels with a graph behind them; torch.cat hands the 1x1 pair's weight gradient back in slices
+            rows = x.float().permute(0, 2, 3, 1).reshape(N * H * W, C).contiguous()
+            t = _Conv3x3ReluFn.apply(rows, self.conv.weight, self.conv.bias, w3, b3, H, W)
+            lw, dw = self.objectness_logits.weight, self.anchor_deltas.weight
+            return ops.linear_autograd(t, torch.cat([lw.flatten(1), dw.flatten(1)]).float(),
+                                       torch.cat([self.objectness_logits.bias, self.anchor_deltas.bias]).float())
         rows = x.detach().float().permute(0, 2, 3, 1).reshape(N * H * W, C).contiguous()
         return ops.linear(ops.conv3x3_nhwc_ex(rows, w3, H, W, shift=b3, relu=True), w1, b1)
 
@@ -229,7 +279,9 @@ class RPN(nn.Module):
 
     @configurable
     def __init__(self, *, in_features: List[str], head: nn.Module, anchor_generator: nn.Module, box2box_transform: Box2BoxTransform,
-                 pre_nms_topk: Tuple[int, int], post_nms_topk: Tuple[int, int], nms_thresh: float = 0.7, min_box_size: float = 0.0):
+                 pre_nms_topk: Tuple[int, int], post_nms_topk: Tuple[int, int], nms_thresh: float = 0.7, min_box_size: float = 0.0,
+                 anchor_matcher: Optional[Matcher] = None, batch_size_per_image: int = 256, positive_fraction: float = 0.5,
+                 anchor_boundary_thresh: float = -1.0, loss_weight=1.0, box_reg_loss_type: str = "smooth_l1", smooth_l1_beta: float = 0.0):
         super().__init__()
         self.in_features = list(in_features)
         self.rpn_head = head
@@ -239,6 +291,18 @@ class RPN(nn.Module):
         self.post_nms_topk = {True: int(post_nms_topk[0]), False: int(post_nms_topk[1])}
         self.nms_thresh = float(nms_thresh)
         self.min_box_size = float(min_box_size)
+        self.anchor_matcher = anchor_matcher if anchor_matcher is not None else Matcher([0.3, 0.7], [0, -1, 1], allow_low_quality_matches=True)
+        self.batch_size_per_image = int(batch_size_per_image)
+        self.positive_fraction = float(positive_fraction)
+        self.anchor_boundary_thresh = anchor_boundary_thresh
+        if isinstance(loss_weight, (int, float)):
+            loss_weight = {"loss_rpn_cls": float(loss_weight), "loss_rpn_loc": float(loss_weight)}
+        self.loss_weight = dict(loss_weight)
+        self.box_reg_loss_type = box_reg_loss_type
+        self.smooth_l1_beta = float(smooth_l1_beta)
+        self._fused_batch = None            # the batch tensors behind the lists label_and_sample_anchors last returned
+        self._pending_log = None            # (pinned counters, event, images) of a fused losses call not yet logged
+        self._defer_log = False
 
     @classmethod
     def from_config(cls, cfg, input_shape: Dict[str, ShapeSpec]):
@@ -248,17 +312,170 @@ class RPN(nn.Module):
                 "box2box_transform": Box2BoxTransform(weights=cfg.MODEL.RPN.BBOX_REG_WEIGHTS),
                 "pre_nms_topk": (cfg.MODEL.RPN.PRE_NMS_TOPK_TRAIN, cfg.MODEL.RPN.PRE_NMS_TOPK_TEST),
                 "post_nms_topk": (cfg.MODEL.RPN.POST_NMS_TOPK_TRAIN, cfg.MODEL.RPN.POST_NMS_TOPK_TEST),
-                "anchor_generator": build_anchor_generator(cfg, shapes), "head": build_rpn_head(cfg, shapes)}
+                "anchor_generator": build_anchor_generator(cfg, shapes), "head": build_rpn_head(cfg, shapes),
+                "anchor_matcher": Matcher(cfg.MODEL.RPN.IOU_THRESHOLDS, cfg.MODEL.RPN.IOU_LABELS, allow_low_quality_matches=True),
+                "batch_size_per_image": cfg.MODEL.RPN.BATCH_SIZE_PER_IMAGE, "positive_fraction": cfg.MODEL.RPN.POSITIVE_FRACTION,
+                "anchor_boundary_thresh": cfg.MODEL.RPN.BOUNDARY_THRESH,
+                "loss_weight": {"loss_rpn_cls": cfg.MODEL.RPN.LOSS_WEIGHT,
+                                "loss_rpn_loc": cfg.MODEL.RPN.BBOX_REG_LOSS_WEIGHT * cfg.MODEL.RPN.LOSS_WEIGHT},
+                "box_reg_loss_type": cfg.MODEL.RPN.BBOX_REG_LOSS_TYPE, "smooth_l1_beta": cfg.MODEL.RPN.SMOOTH_L1_BETA}
 
     def forward(self, images, features: Dict[str, torch.Tensor], gt_instances: Optional[List[Instances]] = None):
-        """images: an ImageList (its image_sizes are read); features: name -> NCHW map.  Returns (proposals, losses)."""
-        if self.training and gt_instances is not None:
-            raise NotImplementedError("RPN: the training losses (anchor labelling with low-quality matches, the 256-sample draw, the "
-                                      "objectness and localisation losses) are a follow-up; proposals come from forward without targets")
+        """images: an ImageList (its image_sizes are read); features: name -> NCHW map.  Returns (proposals, losses): in training
+        with gt_instances the losses are {"loss_rpn_cls", "loss_rpn_loc"}, otherwise {}."""
         feats = [features[f] for f in self.in_features]
+        if not (self.training and gt_instances is not None):
+            anchors = self.anchor_generator(feats)
+            logits, deltas = self.rpn_head.flat_predictions(feats)
+            return self.predict_proposals(anchors, logits, deltas, images.image_sizes), {}
+        if not all(f.is_cuda for f in feats):
+            raise NotImplementedError("RPN: the training losses need device tensors (feature maps on a ROCm GPU): the RPN head runs on "
+                                      "the kernels only and has no torch path")
         anchors = self.anchor_generator(feats)
         logits, deltas = self.rpn_head.flat_predictions(feats)
-        return self.predict_proposals(anchors, logits, deltas, images.image_sizes), {}
+        gt_labels, gt_boxes = self.label_and_sample_anchors(anchors, gt_instances)
+        self._defer_log = True              # the counters are handed to the event storage behind predict_proposals' own read
+        try:
+            losses = self.losses(anchors, logits, gt_labels, deltas, gt_boxes)
+        finally:
+            self._defer_log = False
+        proposals = self.predict_proposals(anchors, [l.detach() for l in logits], [d.detach() for d in deltas], images.image_sizes)
+        self._flush_log()
+        return proposals, losses
+
+    # ------------------------------------------------------------------------------------------------ training: labels and sample
+
+    def _fused_train_ok(self, tensors, n_levels: int, n_images: int, hwa: int) -> bool:
+        m = self.anchor_matcher
+        return (_fused_rpn() and n_levels == 1 and type(m) is Matcher and len(m.labels) <= ops.LABEL_MAX_THRESHOLDS
+                and 0 < n_images <= ops.RPN_MAX_IMAGES and 0 < hwa <= ops.RPN_MAX_ANCHORS
+                and all(t.is_cuda and t.device == tensors[0].device for t in tensors))
+
+    @torch.no_grad()
+    def label_and_sample_anchors(self, anchors: List[Boxes], gt_instances: List[Instances], rnd: Optional[torch.Tensor] = None):
+        """[D2-upstream] per image: pairwise_iou(gt, anchors) -> the matcher (low-quality matches promoted) -> the boundary test ->
+        subsample_labels with background label 0, everything not drawn -1.  rnd: the draw's [2, N, HWA] float64 uniforms (drawn here
+        when None): the min(#positive, int(B f)) positives of smallest rnd[0], then the min(#negative, B - num_pos) negatives of
+        smallest rnd[1], equal keys in anchor order -- a uniformly random subset, as upstream's randperm[:k].
+        Returns (gt_labels: per image [HWA] int8 in {-1, 0, 1}, matched_gt_boxes: per image [HWA, 4]; zeros without ground truth)."""
+        n_levels = len(anchors)
+        anchors_t = Boxes.cat(list(anchors)).tensor
+        N, HWA = len(gt_instances), anchors_t.shape[0]
+        gt = [x.gt_boxes.tensor.float() if x.has("gt_boxes") else anchors_t.new_zeros((0, 4)) for x in gt_instances]
+        sizes = [x.image_size for x in gt_instances]
+        if rnd is None:
+            rnd = torch.rand((2, N, HWA), dtype=torch.float64, device=anchors_t.device)
+        if tuple(rnd.shape) != (2, N, HWA) or rnd.dtype != torch.float64:
+            raise ValueError(f"label_and_sample_anchors: rnd must be float64 [2, {N}, {HWA}]")
+        B, max_pos = self.batch_size_per_image, int(self.batch_size_per_image * self.positive_fraction)
+        m = self.anchor_matcher
+        if self._fused_train_ok([anchors_t, rnd] + gt, n_levels, N, HWA):
+            n_gt = [g.shape[0] for g in gt]
+            gtb = torch.cat([g for g in gt if g.shape[0]]) if sum(n_gt) else None
+            pre, matched, counts = ops.rpn_label_anchors(anchors_t, gtb, n_gt, sizes, m.thresholds, m.labels, m.allow_low_quality_matches,
+                                                         float(self.anchor_boundary_thresh))
+            labels = ops.rpn_sample_anchors(pre, counts, rnd, B, max_pos)
+            gt_labels, gt_boxes = list(labels.unbind(0)), list(matched.unbind(0))
+            self._fused_batch = (gt_labels, gt_boxes, labels, matched, counts)
+            return gt_labels, gt_boxes
+        self._fused_batch = None
+        gt_labels, gt_boxes = [], []
+        for n in range(N):
+            if gt[n].shape[0]:
+                was, m.check_quality = getattr(m, "check_quality", True), False
+                try:
+                    matched_idxs, lab = m(pairwise_iou(Boxes(gt[n]), Boxes(anchors_t)))
+                finally:
+                    m.check_quality = was
+                lab = lab.to(torch.int8)
+                boxes = gt[n][matched_idxs]
+            else:
+                lab = torch.zeros(HWA, dtype=torch.int8, device=anchors_t.device)
+                boxes = torch.zeros_like(anchors_t)
+            if self.anchor_boundary_thresh >= 0:
+                lab[~Boxes(anchors_t).inside_box(sizes[n], self.anchor_boundary_thresh)] = -1
+            pos, neg = lab == 1, lab == 0
+            num_pos = min(int(pos.sum()), max_pos)
+            num_neg = min(int(neg.sum()), B - num_pos)
+            pos_idx = torch.argsort(rnd[0, n] + (~pos).to(rnd.dtype) * 2.0, stable=True)[:num_pos]
+            neg_idx = torch.argsort(rnd[1, n] + (~neg).to(rnd.dtype) * 2.0, stable=True)[:num_neg]
+            out = torch.full_like(lab, -1)
+            out[pos_idx] = 1
+            out[neg_idx] = 0
+            gt_labels.append(out)
+            gt_boxes.append(boxes)
+        return gt_labels, gt_boxes
+
+    # ------------------------------------------------------------------------------------------------ training: losses
+
+    def losses(self, anchors: List[Boxes], pred_objectness_logits: List[torch.Tensor], gt_labels: List[torch.Tensor],
+               pred_anchor_deltas: List[torch.Tensor], gt_boxes: List[torch.Tensor]) -> Dict[str, torch.Tensor]:
+        """[D2-upstream] RPN.losses: loss_rpn_cls = the sum of binary_cross_entropy_with_logits over the anchors of label >= 0,
+        loss_rpn_loc = the sum over label == 1 of smooth-L1 between the predicted deltas and get_deltas(anchor, matched box) (beta
+        < 1e-5: L1), both divided by batch_size_per_image x N and multiplied by their loss weights.  Logs rpn/num_pos_anchors and
+        rpn/num_neg_anchors.  pred_objectness_logits [N, Hi Wi A] and pred_anchor_deltas [N, Hi Wi A, 4] per level."""
+        if self.box_reg_loss_type != "smooth_l1":
+            raise NotImplementedError(f"RPN: MODEL.RPN.BBOX_REG_LOSS_TYPE {self.box_reg_loss_type!r} (box_reg_loss_type) is not implemented; "
+                                      "only \"smooth_l1\"")
+        N = len(gt_labels)
+        normalizer = self.batch_size_per_image * N
+        w_cls, w_loc = self.loss_weight.get("loss_rpn_cls", 1.0), self.loss_weight.get("loss_rpn_loc", 1.0)
+        anchors_t = Boxes.cat(list(anchors)).tensor
+        logits0 = pred_objectness_logits[0]
+        if self._fused_train_ok([anchors_t, logits0, pred_anchor_deltas[0]] + list(gt_labels) + list(gt_boxes), len(pred_objectness_logits),
+                                N, anchors_t.shape[0]):
+            fb = self._fused_batch
+            if fb is not None and fb[0] is gt_labels and fb[1] is gt_boxes:
+                labels, matched, counts = fb[2], fb[3], fb[4]
+            else:
+                labels, matched = torch.stack(list(gt_labels)).to(torch.int8), torch.stack(list(gt_boxes)).float()
+                n_pos, n_neg = (labels == 1).sum(dim=1), (labels == 0).sum(dim=1)
+                counts = torch.stack([n_pos, n_neg, n_pos, n_neg], dim=1).to(torch.int32)      # (the kernels' [N, 4] layout)
+            loss, flags = ops.rpn_loss(logits0, pred_anchor_deltas[0], labels, anchors_t, matched, self.box2box_transform.weights,
+                                       self.smooth_l1_beta, w_cls / normalizer, w_loc / normalizer)
+            # the two logged counters and the degenerate-anchor bit: to pinned memory, read behind an event (no wait here)
+            host = self.__dict__.get("_log_pinned")
+            if host is None or host.numel() < 4 * N + 1:
+                host = self.__dict__["_log_pinned"] = torch.empty(4 * max(N, ops.RPN_MAX_IMAGES) + 1, dtype=torch.int32).pin_memory()
+            host[:4 * N].copy_(counts.view(-1), non_blocking=True)
+            host[4 * N:4 * N + 1].copy_(flags, non_blocking=True)
+            event = torch.cuda.Event()
+            event.record(torch.cuda.current_stream(logits0.device))
+            self._pending_log = (host, event, N)
+            if not self._defer_log:
+                self._flush_log()
+            return {"loss_rpn_cls": loss[0], "loss_rpn_loc": loss[1]}
+        labels = torch.stack(list(gt_labels))
+        pos_mask, valid_mask = labels == 1, labels >= 0
+        storage = get_event_storage()
+        storage.put_scalar("rpn/num_pos_anchors", int(pos_mask.sum()) / N)
+        storage.put_scalar("rpn/num_neg_anchors", int((labels == 0).sum()) / N)
+        degenerate = ~(((anchors_t[:, 2] - anchors_t[:, 0]) > 0) & ((anchors_t[:, 3] - anchors_t[:, 1]) > 0))
+        assert not bool((degenerate[None, :] & pos_mask).any()), "Input boxes to Box2BoxTransform are not valid!"
+        target = torch.stack([self.box2box_transform.get_deltas(anchors_t, b, check=False) for b in gt_boxes])
+        diff = (torch.cat(list(pred_anchor_deltas), dim=1)[pos_mask] - target[pos_mask]).abs()
+        if self.smooth_l1_beta < 1e-5:
+            loss_loc = diff.sum()
+        else:
+            beta = self.smooth_l1_beta
+            loss_loc = torch.where(diff < beta, 0.5 * diff ** 2 / beta, diff - 0.5 * beta).sum()
+        loss_cls = torch.nn.functional.binary_cross_entropy_with_logits(torch.cat(list(pred_objectness_logits), dim=1)[valid_mask],
+                                                                        labels[valid_mask].to(torch.float32), reduction="sum")
+        return {"loss_rpn_cls": loss_cls / normalizer * w_cls, "loss_rpn_loc": loss_loc / normalizer * w_loc}
+
+    def _flush_log(self) -> None:
+        """Hand the counters of the last fused losses call to the event storage (one event wait; none when a later read of the same
+        stream -- predict_proposals' -- has already returned)."""
+        pending, self._pending_log = self._pending_log, None
+        if pending is None:
+            return
+        host, event, N = pending
+        event.synchronize()
+        vals = host[:4 * N + 1].tolist()
+        assert not vals[4 * N] & ops.RPN_LOSS_FLAG_DEGENERATE, "Input boxes to Box2BoxTransform are not valid!"
+        storage = get_event_storage()
+        storage.put_scalar("rpn/num_pos_anchors", sum(vals[2:4 * N:4]) / N)
+        storage.put_scalar("rpn/num_neg_anchors", sum(vals[3:4 * N:4]) / N)
 
     @torch.no_grad()
     def predict_proposals(self, anchors: List[Boxes], logits: List[torch.Tensor], deltas: List[torch.Tensor], image_sizes) -> List[Instances]:
