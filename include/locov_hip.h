@@ -36,7 +36,8 @@ extern "C" {
  *    locov_detect_postprocess_wide (+ _workspace_bytes), locov_regions_select / _gather_fwd / _gather_bwd,
  *    locov_detect_postprocess_cs / _wide_cs (+ _workspace_bytes), locov_grounding_align_fwd / _bwd,
  *    locov_grounding_triplet_fwd / _bwd, locov_mha_fwd / _bwd, locov_rpn_proposals (+ _workspace_bytes),
- *    locov_rpn_label_anchors (+ _workspace_bytes), locov_rpn_sample_anchors, locov_rpn_loss (+ _workspace_bytes) */
+ *    locov_rpn_label_anchors (+ _workspace_bytes), locov_rpn_sample_anchors, locov_rpn_loss (+ _workspace_bytes),
+ *    locov_resnet_stem_fwd */
 #define LOCOV_ABI_VERSION 8
 
 #define LOCOV_OK 0
@@ -1243,6 +1244,26 @@ int locov_mha_bwd(const float *q, int64_t ldq, const float *k, int64_t ldk, cons
                   const uint8_t *keep, float p_drop, float scale, int nseq, int S, int H, int d, const float *dctx,
                   int64_t ldo, const float *lse, float *delta, float *dq, int64_t lddq, float *dk, int64_t lddk, float *dv,
                   int64_t lddv, locov_stream_t stream);
+
+/* ---- the ResNet stem in one launch (csrc/resnet_stem.hip): the front of the C4 backbone -----------------------------------
+ * ([D2-upstream] detectron2.modeling.backbone.resnet.BasicStem; the reference tree has no source for it).  Added under ABI
+ * version 8.
+ *
+ *   CH = (H + 1) / 2, CW = (W + 1) / 2, PH = (CH + 1) / 2, PW = (CW + 1) / 2
+ *   c[n, k, i, j] = sum_{c, u, v} x[n, c, 2 i - 3 + u, 2 j - 3 + v] w[k, c, u, v]        (zero outside the image)
+ *   a             = relu(c * scale[k] + shift[k])                                        (the FrozenBN fold)
+ *   y[n, p, q, k] = max a[n, k, i, j] over i in {2p - 1, 2p, 2p + 1} within [0, CH), j likewise within [0, CW)
+ *
+ *   x     : fp32 [N, 3, H, W], NCHW, contiguous.
+ *   w     : fp32 [Cout, 3, 7, 7] as conv1.weight stores it (16-byte aligned); scale, shift: fp32 [Cout].
+ *   y     : out, fp32 [N, PH, PW, Cout] channels-last (16-byte aligned): the pixel rows the GEMM kernels take.
+ *   A conv row CH or column CW (an odd CH / CW puts one next to the last window) does not exist: it is left out of the maximum,
+ *   not computed from zero padding.  Exact fp32 products, fp32 accumulation; the conv intermediate stays on chip.  No atomics;
+ *   an image's result does not depend on N or on the other images of the launch.
+ * Supported: Cout == 64.  Cout != 64, N < 0, H or W <= 0, a null or misaligned pointer, sizes whose element offsets leave int64 or
+ *   whose tiles leave the launch grid: LOCOV_ERR_INVALID_ARG before any launch.  N == 0: LOCOV_OK, nothing is read or written. */
+int locov_resnet_stem_fwd(const float *x, int N, int H, int W, const float *w, const float *scale, const float *shift, int Cout,
+                          float *y, locov_stream_t stream);
 
 #ifdef __cplusplus
 }

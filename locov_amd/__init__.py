@@ -6,9 +6,10 @@ reference's Detectron2 plugin surface (poolers, res5, roi_heads).
 """
 __version__ = "0.1.0"
 
-from . import config, mmss_regions, ops, poolers, proposal_generator, res5, structures, transformer_head  # noqa: F401
+from . import backbone, config, mmss_regions, ops, poolers, proposal_generator, res5, structures, transformer_head  # noqa: F401
 from .mmss_regions import box_regions, grid_regions  # noqa: F401
 from .transformer_head import TransformerHead, build_transformer_head  # noqa: F401
 from .roi_heads import (EmbeddingFastRCNNOutputLayers, EmbeddingProposalsRes5ROIHeads,  # noqa: F401
                         EmbeddingRes5ROIHeads, build_box_predictor, build_roi_heads)
 from .proposal_generator import RPN, DefaultAnchorGenerator, StandardRPNHead, build_proposal_generator  # noqa: F401
+from .backbone import BasicStem, ResNet, build_backbone, build_resnet_backbone  # noqa: F401

@@ -215,6 +215,7 @@ SIGNATURES = {
                               _p, _p]),
     "locov_mha_bwd": (c_int, [_p, c_int64, _p, c_int64, _p, c_int64, _p, _p, c_float, c_float, c_int, c_int, c_int, c_int, _p,
                               c_int64, _p, _p, _p, c_int64, _p, c_int64, _p, c_int64, _p]),
+    "locov_resnet_stem_fwd": (c_int, [_p, c_int, c_int, c_int, _p, _p, _p, c_int, _p, _p]),
 }
 
 _lib = None

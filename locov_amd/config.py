@@ -78,6 +78,7 @@ def get_cfg() -> CfgNode:
             "MASK_ON": False,
             "KEYPOINT_ON": False,
             "LOAD_EMB_PRED_FROM_MMSS_HEAD": False,                # config.py:13
+            "BACKBONE": {"NAME": "build_resnet_backbone", "FREEZE_AT": 2},   # [D2-upstream]; coco_lsm.yaml -> FREEZE_AT 0
             "PROPOSAL_GENERATOR": {"NAME": "RPN", "MIN_SIZE": 0},     # [D2-upstream]
             "ANCHOR_GENERATOR": {                                  # [D2-upstream]
                 "NAME": "DefaultAnchorGenerator",
@@ -178,6 +179,7 @@ def get_cfg() -> CfgNode:
                 "NUM_GROUPS": 1, "WIDTH_PER_GROUP": 64, "RES2_OUT_CHANNELS": 256,
                 "STRIDE_IN_1X1": True, "NORM": "FrozenBN",
                 "DEFORM_ON_PER_STAGE": [False, False, False, False],
+                "DEPTH": 50, "OUT_FEATURES": ["res4"], "STEM_OUT_CHANNELS": 64, "RES5_DILATION": 1,     # [D2-upstream] (backbone.py)
             },
         },
         "TEST": {"DETECTIONS_PER_IMAGE": 100},                     # [D2-upstream]

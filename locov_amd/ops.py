@@ -1596,6 +1596,33 @@ def nhwc_to_nchw(x: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def resnet_stem_shape(H: int, W: int) -> Tuple[int, int]:
+    """(PH, PW) of the stem's pooled map for an H x W image: conv 7x7 / 2 / pad 3, then max-pool 3x3 / 2 / pad 1."""
+    CH, CW = (H + 1) // 2, (W + 1) // 2
+    return (CH + 1) // 2, (CW + 1) // 2
+
+
+def resnet_stem(images: torch.Tensor, weight: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """[D2-upstream] BasicStem in one launch (csrc/resnet_stem.hip): max_pool(relu(conv7x7/2(images) * scale + shift)).
+    images [N,3,H,W] NCHW, weight [64,3,7,7], scale / shift [64] (the FrozenBN fold) -> channels-last [N,PH,PW,64]."""
+    images, weight = _dev(images, "images"), _dev(weight, "weight")
+    scale, shift = _dev(scale, "scale"), _dev(shift, "shift")
+    if images.dim() != 4 or images.shape[1] != 3 or min(images.shape[2:]) < 1:
+        raise ValueError(f"resnet_stem: images must be [N,3,H,W], got {tuple(images.shape)}")
+    Cout = weight.shape[0]
+    if tuple(weight.shape) != (Cout, 3, 7, 7) or tuple(scale.shape) != (Cout,) or tuple(shift.shape) != (Cout,):
+        raise ValueError(f"resnet_stem: weight must be [Cout,3,7,7] and scale, shift [Cout], got {tuple(weight.shape)}, "
+                         f"{tuple(scale.shape)}, {tuple(shift.shape)}")
+    N, _, H, W = images.shape
+    PH, PW = resnet_stem_shape(H, W)
+    y = _out(out, (N, PH, PW, Cout), images, "resnet_stem")
+    with torch.cuda.device(images.device):
+        check(_lib.load().locov_resnet_stem_fwd(_ptr(images), N, H, W, _ptr(weight), _ptr(scale), _ptr(shift), Cout, _ptr(y),
+                                                _stream(images)), "locov_resnet_stem_fwd")
+    return y
+
+
 class _LinearFn(torch.autograd.Function):
     """y = x W^T + b on the f32 MFMA NT-GEMM kernel; backward: grad_x = g W as an NT GEMM against the transposed
     weight (one small weight-sized transpose), grad_W = g^T x on the TN kernel (no activation-sized transposes),
