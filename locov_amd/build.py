@@ -40,7 +40,7 @@ FILE_FLAGS = {
     "rpn.hip": ["-ffp-contract=off"],            # (the same decoding and IoU, through detect_common.h)
     "rpn_train.hip": ["-ffp-contract=off"],      # (the IoU of label.hip, the box deltas of losses.hip: the same roundings)
     "mha.hip": ["-ffp-contract=off"],            # (dP - delta must cancel exactly where one key holds a row: no fused dP * keep - delta)
-    "nms.hip": ["-ffp-contract=off"],            # (iou_gt must round as detect_common.h's det_iou_gt: the bit-identity tests)
+    "nms.hip": ["-ffp-contract=off"],            # (select_common.h's box_iou_gt, rounded as in detect.hip / rpn.hip: the bit-identity tests)
 }
 
 

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -18,6 +19,13 @@ inline hipStream_t as_stream(locov_stream_t s) { return reinterpret_cast<hipStre
 
 // Checks the launch that was just enqueued (no synchronisation).
 int check_launch(const char *what);
+
+// Raises `kernel`'s dynamic LDS limit to `bytes`, once per device a launch is made on (the attribute belongs to the kernel's code
+// object on ONE device).  per_device_state: the caller's `static std::atomic<int> [kMaxDevices]` for that kernel (0 = not asked yet,
+// 1 = raised, -1 = refused).  LOCOV_OK, or LOCOV_ERR_LAUNCH after set_error -- with who == nullptr the error text is left alone (a
+// caller for which a refusal is no error).  The state remembers the FIRST call's answer: a kernel is always raised to one constant.
+constexpr int kMaxDevices = 64;
+int raise_dynamic_lds(std::atomic<int> *per_device_state, const void *kernel, int bytes, const char *who);
 
 constexpr int kWave = 64;
 

@@ -1,7 +1,6 @@
 // Error handling, device info, and small element-wise kernels.
 #include "common.h"
 
-#include <atomic>
 #include <cstring>
 
 namespace locov {
@@ -27,6 +26,20 @@ int check_launch(const char *what)
     hipError_t e = hipGetLastError();
     if (e != hipSuccess)
         return set_error(LOCOV_ERR_LAUNCH, "%s: launch failed: %s", what, hipGetErrorString(e));
+    return LOCOV_OK;
+}
+
+int raise_dynamic_lds(std::atomic<int> *per_device_state, const void *kernel, int bytes, const char *who)
+{
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices)
+        return who ? set_error(LOCOV_ERR_LAUNCH, "%s: hipGetDevice", who) : LOCOV_ERR_LAUNCH;
+    std::atomic<int> &state = per_device_state[dev];
+    if (state.load(std::memory_order_relaxed) == 0)
+        state.store(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess ? 1 : -1,
+                    std::memory_order_relaxed);
+    if (state.load(std::memory_order_relaxed) != 1)
+        return who ? set_error(LOCOV_ERR_LAUNCH, "%s: cannot raise the dynamic LDS limit to %d bytes", who, bytes) : LOCOV_ERR_LAUNCH;
     return LOCOV_OK;
 }
 

@@ -28,14 +28,15 @@
 // Candidate order, tie-breaking and every fp32 operation equal the torch chain's (tests/test_gpu_postprocess.py: bit-identical
 // detections).  What the kernels cannot take is flagged on the device and read by the caller with the counts (its ONE host
 // read): non-finite boxes / scores (the reference drops such proposals with a warning) and an image with more candidates than
-// the LDS sort holds -- the caller then runs the torch chain.
+// the LDS sort holds -- the caller then runs the torch chain.  The IoU test, the block scan, the key layout and the top-k write-out
+// are select_common.h's (through detect_common.h).
 #include "detect_common.h"
 
 namespace locov {
 
 constexpr int kDetMaxCand = LOCOV_DETECT_MAX_CANDIDATES;       // candidates per image (64-bit keys sorted in LDS)
 constexpr int kDetThreads = 1024;
-constexpr int kRowBits = 14, kScoreBits = 32, kClsBits = 15;  // key = class << 46 | ~score << 14 | row
+// sort key = class << 46 | ~score << 14 | row  (kKeyRowBits, kKeyScoreBits: select_common.h)
 
 // a wave per proposal: candidates (p > thr among the K foreground columns); every one of the K + 1 columns must be finite
 __global__ __launch_bounds__(256) void det_count_kernel(const float *__restrict__ probs, int64_t ld, int K, int R, float thr,
@@ -63,7 +64,7 @@ __global__ __launch_bounds__(kDetThreads) void det_scan_kernel(const int *__rest
 {
     __shared__ int wave_sum[kDetThreads / 64];
     __shared__ int carry;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     for (int img = 0; img < g.n_img; img++) {
         const int r0 = g.roff[img], r1 = g.roff[img + 1];
         if (tid == 0) carry = 0;
@@ -71,19 +72,11 @@ __global__ __launch_bounds__(kDetThreads) void det_scan_kernel(const int *__rest
         for (int base = r0; base < r1; base += kDetThreads) {
             const int r = base + tid;
             const int v = r < r1 ? row_count[r] : 0;
-            int incl = v;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const int t = __shfl_up(incl, o);
-                if (lane >= o) incl += t;
-            }
-            if (lane == 63) wave_sum[wave] = incl;
-            __syncthreads();
-            int before = carry;
-            for (int w = 0; w < wave; w++) before += wave_sum[w];
-            if (r < r1) row_off[r] = before + incl - v;
-            __syncthreads();
-            if (tid == kDetThreads - 1) carry = before + incl;
+            // (carry is read in front of the scan's barrier and written behind it: the barrier that used to separate the two is gone)
+            const int before = carry;
+            const int at = before + block_exclusive_scan<kDetThreads>(v, wave_sum);
+            if (r < r1) row_off[r] = at;
+            if (tid == kDetThreads - 1) carry = at + v;
             __syncthreads();
         }
         if (tid == 0) img_count[img] = carry;
@@ -108,9 +101,9 @@ __global__ __launch_bounds__(256) void det_emit_kernel(const float *__restrict__
         const bool ok = c < K && v > thr;
         const unsigned long long b = __ballot(ok);
         if (ok) {
-            const int pos = at + __popcll(b & ((1ull << lane) - 1ull));
+            const int pos = at + lanes_below(b);
             if (pos < kDetMaxCand)
-                out[pos] = ((unsigned long long)c << (kRowBits + kScoreBits)) | ((unsigned long long)(~__float_as_uint(v)) << kRowBits) | row;
+                out[pos] = ((unsigned long long)c << (kKeyRowBits + kKeyScoreBits)) | ((unsigned long long)(~__float_as_uint(v)) << kKeyRowBits) | row;
         }
         at += __popcll(b);
     }
@@ -148,18 +141,16 @@ __global__ __launch_bounds__(kDetThreads) void det_sort_kernel(DetLists L, const
         return;
     }
     if (n == 0) return;
-    int P = 2;
-    while (P < n) P <<= 1;
+    const int P = next_pow2(n, 2);
     unsigned long long *keys_g = L.keys + (int64_t)img * kDetMaxCand;
     for (int i = tid; i < P; i += kDetThreads) key[i] = i < n ? keys_g[i] : ~0ull;
     __syncthreads();
     det_bitonic_sort<kDetThreads>(key, P, tid);                               // class-major; inside a class: descending score, ties by row
-    constexpr unsigned long long kRowMask = (1ull << kRowBits) - 1ull;
     const float4 *gbox = boxes + (int64_t)g.roff[img] * bk;
     // batched_nms's coordinate offset: class * (max coordinate of the image's candidate boxes + 1)
     float m = -__builtin_inff();
     for (int i = tid; i < n; i += kDetThreads) {
-        const float4 b = gbox[(int)(key[i] & kRowMask) * bk + (int)(key[i] >> (kRowBits + kScoreBits)) * cs];
+        const float4 b = gbox[(int)(key[i] & kKeyRowMask) * bk + (int)(key[i] >> (kKeyRowBits + kKeyScoreBits)) * cs];
         m = fmaxf(m, fmaxf(fmaxf(b.x, b.y), fmaxf(b.z, b.w)));
     }
 #pragma unroll
@@ -181,15 +172,15 @@ __global__ __launch_bounds__(kDetThreads) void det_sort_kernel(DetLists L, const
         words[q] = 0;
         if (i < n) {
             const unsigned long long k = key[i];
-            const int cls = (int)(k >> (kRowBits + kScoreBits));
-            const unsigned long long first_of_class = (unsigned long long)cls << (kRowBits + kScoreBits);
+            const int cls = (int)(k >> (kKeyRowBits + kKeyScoreBits));
+            const unsigned long long first_of_class = (unsigned long long)cls << (kKeyRowBits + kKeyScoreBits);
             int lo = 0, hi = i;
             while (lo < hi) {                                    // the first candidate of i's class (the keys are sorted)
                 const int mid = (lo + hi) >> 1;
                 if (key[mid] < first_of_class) lo = mid + 1;
                 else hi = mid;
             }
-            float4 b = gbox[(int)(k & kRowMask) * bk + cls * cs];
+            float4 b = gbox[(int)(k & kKeyRowMask) * bk + cls * cs];
             const float off = (float)cls * shift_unit;
             b.x += off;
             b.y += off;
@@ -202,16 +193,7 @@ __global__ __launch_bounds__(kDetThreads) void det_sort_kernel(DetLists L, const
         }
         run += words[q];
     }
-    int incl = run;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(incl, o);
-        if (lane >= o) incl += t;
-    }
-    if (lane == 63) wave_sum[wave] = incl;
-    __syncthreads();
-    int before = incl - run;
-    for (int w = 0; w < wave; w++) before += wave_sum[w];
+    int before = block_exclusive_scan<kDetThreads>(run, wave_sum);
 #pragma unroll
     for (int q = 0; q < kQ; q++) {
         const int i = tid * kQ + q;
@@ -237,7 +219,7 @@ __global__ __launch_bounds__(256) void det_pairs_kernel(DetLists L, const int *_
     const int lim = min(64, a - base);
     unsigned long long bits = 0;
 #pragma unroll 8
-    for (int j = 0; j < lim; j++) bits |= (unsigned long long)det_iou_gt(cbox[base + j], box_a, nms_thr) << j;
+    for (int j = 0; j < lim; j++) bits |= (unsigned long long)box_iou_gt(cbox[base + j], box_a, nms_thr) << j;
     L.ov[(int64_t)img * kDetOvWords + L.woff[(int64_t)img * (kDetMaxCand + 4) + a] + w] = bits;
 }
 
@@ -262,8 +244,7 @@ __global__ __launch_bounds__(kDetThreads) void det_nms_topk_kernel(DetLists L, c
         if (tid == 0) counts[img] = 0;
         return;
     }
-    int P = 2;
-    while (P < n) P <<= 1;
+    const int P = next_pow2(n, 2);
     const unsigned long long *keys_g = L.keys + (int64_t)img * kDetMaxCand;
     const int *cstart = L.cstart + (int64_t)img * kDetMaxCand, *woff = L.woff + (int64_t)img * (kDetMaxCand + 4);
     const unsigned long long *ov = L.ov + (int64_t)img * kDetOvWords;
@@ -309,14 +290,12 @@ __global__ __launch_bounds__(kDetThreads) void det_nms_topk_kernel(DetLists L, c
         if (__syncthreads_or(pending) == 0) break;
     }
     // the survivors in the reference's order: descending score, ties in candidate (row, class) order
-    constexpr unsigned long long kRowMask = (1ull << kRowBits) - 1ull;
     int mine_n = 0;
     for (int i = tid; i < P; i += kDetThreads) {
         unsigned long long v = ~0ull;
         if (i < n && ((kept[i >> 5] >> (i & 31)) & 1u)) {
             const unsigned long long k = keys_g[i];
-            const unsigned long long cls = k >> (kRowBits + kScoreBits), nscore = (k >> kRowBits) & 0xffffffffull, row = k & kRowMask;
-            v = (nscore << (kRowBits + kClsBits)) | (row << kClsBits) | cls;
+            v = merge_key(k & ((1ull << (kKeyRowBits + kKeyScoreBits)) - 1ull), (int)(k >> (kKeyRowBits + kKeyScoreBits)));
             mine_n++;
         }
         key[i] = v;
@@ -326,17 +305,8 @@ __global__ __launch_bounds__(kDetThreads) void det_nms_topk_kernel(DetLists L, c
     det_bitonic_sort<kDetThreads>(key, P, tid);
     const int n_keep = n_keep_s;
     const int count = n_keep < topk ? n_keep : topk;
-    const float4 *gbox = boxes + (int64_t)g.roff[img] * bk;
-    for (int j = tid; j < count; j += kDetThreads) {
-        const unsigned long long k = key[j];
-        const int cls = (int)(k & ((1ull << kClsBits) - 1ull)), row = (int)((k >> kClsBits) & kRowMask);
-        const unsigned nscore = (unsigned)(k >> (kRowBits + kClsBits));
-        const int64_t slot = (int64_t)img * topk + j;
-        out_boxes[slot] = gbox[row * bk + cls * cs];
-        out_scores[slot] = __uint_as_float(~nscore);
-        out_classes[slot] = cls;
-        out_rows[slot] = row;
-    }
+    merge_keys_write_out<kDetThreads>(key, count, boxes + (int64_t)g.roff[img] * bk, bk, cs, img, topk, out_boxes, out_scores, out_classes,
+                                      out_rows);
     if (tid == 0) counts[img] = count;
 }
 
@@ -375,7 +345,7 @@ static int det_run(const char *who, const float *probs, int64_t ld_probs, int nu
     LOCOV_REQUIRE(n_images >= 0 && n_images <= LOCOV_LABEL_MAX_IMAGES, "%s: 0..%d images per call", who, LOCOV_LABEL_MAX_IMAGES);
     if (n_images == 0) return LOCOV_OK;
     LOCOV_REQUIRE(row_offsets && image_hw, "%s: null host array", who);
-    LOCOV_REQUIRE(num_classes >= 1 && num_classes < (1 << kClsBits), "%s: 1..%d classes", who, (1 << kClsBits) - 1);
+    LOCOV_REQUIRE(num_classes >= 1 && num_classes < (1 << kKeyClsBits), "%s: 1..%d classes", who, (1 << kKeyClsBits) - 1);
     if (int rc = det_check_box_classes(num_classes, ld_deltas, box_classes, who)) return rc;
     LOCOV_REQUIRE(topk >= 1 && topk <= kDetMaxCand, "%s: 1 <= topk <= %d", who, kDetMaxCand);
     LOCOV_REQUIRE(ld_probs >= (int64_t)num_classes + 1, "%s: ld_probs must cover the K + 1 columns", who);
@@ -385,7 +355,7 @@ static int det_run(const char *who, const float *probs, int64_t ld_probs, int nu
     for (int i = 0; i <= n_images; i++) {
         g.roff[i] = row_offsets[i];
         LOCOV_REQUIRE(g.roff[i] >= 0 && (i == 0 || g.roff[i] >= g.roff[i - 1]), "%s: offsets must be non-decreasing", who);
-        LOCOV_REQUIRE(i == 0 || g.roff[i] - g.roff[i - 1] < (1 << kRowBits), "%s: at most %d proposals per image", who, (1 << kRowBits) - 1);
+        LOCOV_REQUIRE(i == 0 || g.roff[i] - g.roff[i - 1] < (1 << kKeyRowBits), "%s: at most %d proposals per image", who, (1 << kKeyRowBits) - 1);
     }
     LOCOV_REQUIRE(g.roff[0] == 0, "%s: offsets start at 0", who);
     for (int i = 0; i < n_images; i++) {
@@ -435,15 +405,9 @@ static int det_run(const char *who, const float *probs, int64_t ld_probs, int nu
                        row_off, keys);
     // (the sorts' LDS: 8 bytes per candidate slot, 64 KB; the attribute belongs to the kernel on ONE device)
     const size_t lds = (size_t)kDetMaxCand * 8;
-    static int attr_state[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return set_error(LOCOV_ERR_LAUNCH, "%s: hipGetDevice", who);
-    if (attr_state[dev] == 0)
-        attr_state[dev] = (hipFuncSetAttribute(reinterpret_cast<const void *>(det_sort_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               (int)lds) == hipSuccess &&
-                           hipFuncSetAttribute(reinterpret_cast<const void *>(det_nms_topk_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               (int)lds) == hipSuccess) ? 1 : -1;
-    if (attr_state[dev] != 1) return set_error(LOCOV_ERR_LAUNCH, "%s: cannot raise the dynamic LDS limit to %zu bytes", who, lds);
+    static std::atomic<int> sort_lds[kMaxDevices], topk_lds[kMaxDevices];
+    if (int rc = raise_dynamic_lds(sort_lds, reinterpret_cast<const void *>(det_sort_kernel), (int)lds, who)) return rc;
+    if (int rc = raise_dynamic_lds(topk_lds, reinterpret_cast<const void *>(det_nms_topk_kernel), (int)lds, who)) return rc;
     hipLaunchKernelGGL(det_sort_kernel, dim3((unsigned)n_images), dim3(kDetThreads), lds, s, L, img_count, boxes, g, bk, cs, flags);
     // (a class holds at most one candidate per proposal: its predecessors fit ceil(rows of the largest image / 64) words)
     int max_rows = 0;
@@ -463,7 +427,7 @@ int64_t locov_detect_postprocess_workspace_bytes(int64_t R, int n_images) { retu
 int64_t locov_detect_postprocess_cs_workspace_bytes(int64_t R, int n_images, int num_classes, int64_t ld_deltas, int box_classes)
 {
     const char *who = "locov_detect_postprocess_cs_workspace_bytes";
-    LOCOV_REQUIRE(num_classes >= 1 && num_classes < (1 << kClsBits), "%s: 1..%d classes", who, (1 << kClsBits) - 1);
+    LOCOV_REQUIRE(num_classes >= 1 && num_classes < (1 << kKeyClsBits), "%s: 1..%d classes", who, (1 << kKeyClsBits) - 1);
     if (int rc = det_check_box_classes(num_classes, ld_deltas, box_classes, who)) return rc;
     LOCOV_REQUIRE(R <= 0 || R * box_classes <= 0x7fffffff, "%s: rows x box_classes must stay below 2^31", who);
     return det_workspace_bytes(R, n_images, box_classes);

@@ -1,8 +1,8 @@
 // Device pieces shared by the two detection post-processing pipelines: detect.hip (candidates sorted in LDS, COCO-style
 // thresholds) and detect_wide.hip (any candidate count, LVIS-style thresholds).  Both files are compiled with -ffp-contract=off:
-// the box decoding and the IoU must round as the torch ops do.
+// the box decoding and the IoU must round as the torch ops do.  The IoU test, the scans and the key layout are select_common.h's.
 #pragma once
-#include "common.h"
+#include "select_common.h"
 
 namespace locov {
 namespace {     // (each pipeline's translation unit keeps its own copy of the kernel)
@@ -83,17 +83,6 @@ __global__ __launch_bounds__(256) void det_decode_clip_cs_kernel(const float *__
     if (!(det_finite(o.x) && det_finite(o.y) && det_finite(o.z) && det_finite(o.w))) atomicOr(flags, LOCOV_DETECT_FLAG_NONFINITE);
     const int img = det_image_of(g, r);
     boxes[t] = det_clip(o, g.w[img], g.h[img]);
-}
-
-// must round exactly as nms.hip's iou_gt does (all three files are compiled with -ffp-contract=off): change them together
-__device__ __forceinline__ bool det_iou_gt(const float4 a, const float4 b, float thr)        // (= nms.hip's iou_gt)
-{
-    const float left = fmaxf(a.x, b.x), right = fminf(a.z, b.z);
-    const float top = fmaxf(a.y, b.y), bottom = fminf(a.w, b.w);
-    const float w = fmaxf(right - left, 0.f), h = fmaxf(bottom - top, 0.f);
-    const float inter = w * h;
-    const float sa = (a.z - a.x) * (a.w - a.y), sb = (b.z - b.x) * (b.w - b.y);
-    return inter / (sa + sb - inter) > thr;
 }
 
 template <int kThreads>

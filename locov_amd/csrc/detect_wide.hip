@@ -34,12 +34,11 @@
 //                            ends as soon as the keys below a threshold number at least top-k and at most kDwCap
 //   dw_gather_kernel         those keys into one buffer per image
 //   dw_topk_kernel           a workgroup per image: bitonic sort of the <= kDwCap winners in LDS, the first top-k out.
+// The IoU test, the block scan, the radix digit pick, the compacting append and the key layout are select_common.h's.
 #include "detect_common.h"
 
 namespace locov {
 
-constexpr int kDwRowBits = 14, kDwClsBits = 15;
-constexpr unsigned long long kDwRowMask = (1ull << kDwRowBits) - 1ull;
 constexpr int kDwChunkRows = 64;                // rows per count / emit workgroup
 constexpr int kDwCap = 16384;                   // winners the last launch sorts in LDS (128 KB)
 constexpr int kDwDigit = 11, kDwBins = 1 << kDwDigit, kDwPasses = 6;     // 61-bit merge keys: 5 x 11 + 6 bits
@@ -148,7 +147,7 @@ __global__ __launch_bounds__(1024) void dw_scan_kernel(DwPlan p, DwWork w)
 {
     __shared__ int wave_sum[16];
     __shared__ int carry;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, K = p.K;
+    const int tid = threadIdx.x, K = p.K;
     if (tid == 0) carry = 0;
     __syncthreads();
     for (int img = 0; img < p.n_img; img++) {
@@ -156,19 +155,11 @@ __global__ __launch_bounds__(1024) void dw_scan_kernel(DwPlan p, DwWork w)
         for (int c0 = 0; c0 < K; c0 += 1024) {
             const int c = c0 + tid;
             const int v = c < K ? w.cnt[img * K + c] : 0;
-            int incl = v;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const int t = __shfl_up(incl, o);
-                if (lane >= o) incl += t;
-            }
-            if (lane == 63) wave_sum[wave] = incl;
-            __syncthreads();
-            int before = carry;
-            for (int q = 0; q < wave; q++) before += wave_sum[q];
-            if (c < K) w.seg_off[img * K + c] = w.cursor[img * K + c] = before + incl - v;
-            __syncthreads();
-            if (tid == 1023) carry = before + incl;
+            // (carry is read in front of the scan's barrier and written behind it: the barrier that used to separate the two is gone)
+            const int before = carry;
+            const int at = before + block_exclusive_scan<1024>(v, wave_sum);
+            if (c < K) w.seg_off[img * K + c] = w.cursor[img * K + c] = at;
+            if (tid == 1023) carry = at + v;
             __syncthreads();
         }
         if (tid == 0) {
@@ -196,7 +187,7 @@ __global__ __launch_bounds__(256) void dw_emit_kernel(const float *__restrict__ 
         const int j = __ffsll((long long)mask) - 1;
         mask &= mask - 1ull;
         const float v = probs[(int64_t)(r0 + j) * ld + c];
-        w.keys[at++] = ((unsigned long long)(~__float_as_uint(v)) << kDwRowBits) | (unsigned long long)(r0 + j - g.roff[img]);
+        w.keys[at++] = ((unsigned long long)(~__float_as_uint(v)) << kKeyRowBits) | (unsigned long long)(r0 + j - g.roff[img]);
     }
 }
 
@@ -207,8 +198,7 @@ __global__ __launch_bounds__(256) void dw_segsort_kernel(DwWork w)
     const int seg = blockIdx.x, tid = threadIdx.x;
     const int m = w.cnt[seg];
     if (m <= 1) return;
-    int P = 2;
-    while (P < m) P <<= 1;
+    const int P = next_pow2(m, 2);
     unsigned long long *keys = w.keys + w.seg_off[seg];
     for (int i = tid; i < P; i += 256) skey[i] = i < m ? keys[i] : ~0ull;
     __syncthreads();
@@ -233,7 +223,7 @@ __global__ __launch_bounds__(256) void dw_overlap_kernel(DetGeom g, DwPlan p, Dw
         const float4 a = gb[j];
         const int lim = min(64, rows - 64 * wd);
         unsigned long long bits = 0;
-        for (int k = 0; k < lim; k++) bits |= (unsigned long long)det_iou_gt(a, gb[64 * wd + k], nms_thr) << k;
+        for (int k = 0; k < lim; k++) bits |= (unsigned long long)box_iou_gt(a, gb[64 * wd + k], nms_thr) << k;
         w.M[p.mbase[img] + (int64_t)j * W + wd] = bits;
         return;
     }
@@ -248,7 +238,7 @@ __global__ __launch_bounds__(256) void dw_overlap_kernel(DetGeom g, DwPlan p, Dw
     }
     const int s = so[lo], pos = idx - s;
     const float off = (float)lo * (__uint_as_float(inf.umax) + 1.f);
-    float4 b = gb[(int)(w.keys[idx] & kDwRowMask) * bk + (CS ? lo : 0)];
+    float4 b = gb[(int)(w.keys[idx] & kKeyRowMask) * bk + (CS ? lo : 0)];
     b.x += off;
     b.y += off;
     b.z += off;
@@ -258,12 +248,12 @@ __global__ __launch_bounds__(256) void dw_overlap_kernel(DetGeom g, DwPlan p, Dw
         const int lim = min(64, pos - 64 * wd);
         unsigned long long bits = 0;
         for (int j = 0; j < lim; j++) {
-            float4 e = gb[(int)(w.keys[s + 64 * wd + j] & kDwRowMask) * bk + (CS ? lo : 0)];
+            float4 e = gb[(int)(w.keys[s + 64 * wd + j] & kKeyRowMask) * bk + (CS ? lo : 0)];
             e.x += off;
             e.y += off;
             e.z += off;
             e.w += off;
-            bits |= (unsigned long long)det_iou_gt(e, b, nms_thr) << j;
+            bits |= (unsigned long long)box_iou_gt(e, b, nms_thr) << j;
         }
         out[wd] = bits;
     }
@@ -299,7 +289,7 @@ __global__ __launch_bounds__(256) void dw_sweep_kernel(DwPlan p, DwWork w)
             for (int i = 0; i < 8; i++) {
                 const int a = a0 + b0 + i;
                 const unsigned long long ka = __shfl(mykey, (b0 + i) & 63);
-                const int row = (int)(ka & kDwRowMask);
+                const int row = (int)(ka & kKeyRowMask);
 #pragma unroll
                 for (int q = 0; q < NQ; q++) {
                     const int wd = lane + 64 * q;
@@ -321,12 +311,11 @@ __global__ __launch_bounds__(256) void dw_sweep_kernel(DwPlan p, DwWork w)
                 for (int q = 0; q < NQ; q++) hit |= (v[i][q] & kept[q]) != 0ull;
                 if (__ballot(hit) == 0ull) {
                     const unsigned long long ka = __shfl(mykey, b0 + i);
-                    const int idx = per_class ? (int)(ka & kDwRowMask) : a0 + b0 + i;
+                    const int idx = per_class ? (int)(ka & kKeyRowMask) : a0 + b0 + i;
 #pragma unroll
                     for (int q = 0; q < NQ; q++)
                         if ((idx >> 6) == lane + 64 * q) kept[q] |= 1ull << (idx & 63);
-                    if (lane == 0)
-                        keys[nk] = ((ka >> kDwRowBits) << (kDwRowBits + kDwClsBits)) | ((ka & kDwRowMask) << kDwClsBits) | (unsigned long long)cls;
+                    if (lane == 0) keys[nk] = merge_key(ka, cls);
                     nk++;
                 }
             }
@@ -336,16 +325,6 @@ __global__ __launch_bounds__(256) void dw_sweep_kernel(DwPlan p, DwWork w)
         w.kept[seg] = nk;
         atomicAdd(&w.info[img].surv, nk);
     }
-}
-
-__device__ __forceinline__ float4 dw_lane_box(const float4 v, int j)           // lane j's box (j uniform over the wave)
-{
-    float4 e;
-    e.x = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v.x), j));
-    e.y = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v.y), j));
-    e.z = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v.z), j));
-    e.w = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v.w), j));
-    return e;
 }
 
 // Class-specific boxes, per-class images: a wave per segment, the greedy sweep with the pair tests inside (every candidate has its own
@@ -370,19 +349,19 @@ __global__ __launch_bounds__(256) void dw_sweep_cs_kernel(DetGeom g, DwPlan p, D
         const int nb = min(64, m - a0);
         const bool have = lane < nb;
         const unsigned long long mykey = have ? keys[a0 + lane] : 0ull;
-        const float4 mine = have ? gb[(int64_t)(int)(mykey & kDwRowMask) * K] : none;
+        const float4 mine = have ? gb[(int64_t)(int)(mykey & kKeyRowMask) * K] : none;
         bool dead = !have;
         for (int k0 = 0; k0 < nk && __ballot(!dead) != 0ull; k0 += 64) {
             const int nkk = min(64, nk - k0);
             float4 kb = none;
             if (lane < nkk) {
                 const unsigned long long kk = __hip_atomic_load(&keys[k0 + lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                kb = gb[(int64_t)(int)((kk >> kDwClsBits) & kDwRowMask) * K];
+                kb = gb[(int64_t)(int)((kk >> kKeyClsBits) & kKeyRowMask) * K];
             }
-            for (int j = 0; j < nkk; j++) dead |= det_iou_gt(dw_lane_box(kb, j), mine, nms_thr);
+            for (int j = 0; j < nkk; j++) dead |= box_iou_gt(lane_box(kb, j), mine, nms_thr);
         }
         unsigned long long earlier = 0;         // bit j: the step's candidate j < lane overlaps mine
-        for (int j = 0; j < nb - 1; j++) earlier |= (unsigned long long)(j < lane && det_iou_gt(dw_lane_box(mine, j), mine, nms_thr)) << j;
+        for (int j = 0; j < nb - 1; j++) earlier |= (unsigned long long)(j < lane && box_iou_gt(lane_box(mine, j), mine, nms_thr)) << j;
         unsigned long long alive = __ballot(!dead), keep = 0;
         while (alive) {
             const int j = __ffsll((long long)alive) - 1;
@@ -390,9 +369,7 @@ __global__ __launch_bounds__(256) void dw_sweep_cs_kernel(DetGeom g, DwPlan p, D
             alive &= ~(1ull << j) & ~__ballot(((earlier >> j) & 1ull) != 0ull);
         }
         if ((keep >> lane) & 1ull)              // (slot <= a0 + lane: never a candidate that is still to be read)
-            __hip_atomic_store(&keys[nk + __popcll(keep & ((1ull << lane) - 1ull))],
-                               ((mykey >> kDwRowBits) << (kDwRowBits + kDwClsBits)) | ((mykey & kDwRowMask) << kDwClsBits) | (unsigned long long)cls,
-                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(&keys[nk + lanes_below(keep)], merge_key(mykey, cls), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         nk += __popcll(keep);
         __threadfence();                        // the next step's lanes read what other lanes wrote here
     }
@@ -411,8 +388,8 @@ __global__ __launch_bounds__(256) void dw_select_kernel(DwPlan p, DwWork w, int 
 {
     __shared__ int h[kDwBins];
     __shared__ int wave_sum[4];
-    __shared__ int last, pick_bin, pick_cum, pick_n;
-    const int img = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, K = p.K;
+    __shared__ int last, ctl[3];                          // ctl: picked bin, keys before it, keys in it (radix_pick)
+    const int img = blockIdx.y, tid = threadIdx.x, K = p.K;
     DwImage &inf = w.info[img];
     if (inf.surv <= kDwCap || inf.done) return;           // (uniform over the image's workgroups)
     const int lo = dw_lo_bit(pass), nd = dw_digits(pass);
@@ -440,37 +417,14 @@ __global__ __launch_bounds__(256) void dw_select_kernel(DwPlan p, DwWork w, int 
     __threadfence();
     // the last workgroup: find the bin of the need-th key under the prefix
     constexpr int kPer = kDwBins / 256;
-    int v[kPer], sum = 0;
+    int v[kPer];
 #pragma unroll
-    for (int q = 0; q < kPer; q++) {
-        v[q] = __hip_atomic_load(&gh[tid * kPer + q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        sum += v[q];
-    }
-    int incl = sum;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(incl, o);
-        if (lane >= o) incl += t;
-    }
-    if (lane == 63) wave_sum[wave] = incl;
-    __syncthreads();
-    int cum = incl - sum;
-    for (int q = 0; q < wave; q++) cum += wave_sum[q];
-    const int k = min(topk, inf.surv), need = k - inf.below;
-#pragma unroll
-    for (int q = 0; q < kPer; q++) {
-        if (cum < need && need <= cum + v[q]) {
-            pick_bin = tid * kPer + q;
-            pick_cum = cum;
-            pick_n = v[q];
-        }
-        cum += v[q];
-    }
-    __syncthreads();
+    for (int q = 0; q < kPer; q++) v[q] = __hip_atomic_load(&gh[tid * kPer + q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    radix_pick<256>(v, min(topk, inf.surv) - inf.below, wave_sum, ctl);
     if (tid == 0) {
-        const int b = pick_bin, below = inf.below + pick_cum;
-        const unsigned long long np = (pre << nd) | (unsigned long long)b;
-        if (below + pick_n <= kDwCap) {
+        const int below = inf.below + ctl[1];
+        const unsigned long long np = (pre << nd) | (unsigned long long)ctl[0];
+        if (below + ctl[2] <= kDwCap) {
             inf.thresh = (np + 1ull) << lo;
             inf.done = 1;
         } else {
@@ -483,7 +437,7 @@ __global__ __launch_bounds__(256) void dw_select_kernel(DwPlan p, DwWork w, int 
 // the winners' candidates: every survivor (at most kDwCap of them) or the survivors below the select's threshold
 __global__ __launch_bounds__(256) void dw_gather_kernel(DwPlan p, DwWork w)
 {
-    const int img = blockIdx.y, tid = threadIdx.x, lane = tid & 63, K = p.K;
+    const int img = blockIdx.y, tid = threadIdx.x, K = p.K;
     DwImage &inf = w.info[img];
     const unsigned long long T = inf.surv <= kDwCap ? ~0ull : inf.thresh;
     unsigned long long *out = w.gbuf + (int64_t)img * kDwCap;
@@ -495,12 +449,8 @@ __global__ __launch_bounds__(256) void dw_gather_kernel(DwPlan p, DwWork w)
             const int j = j0 + tid;
             const unsigned long long k = j < n ? keys[j] : ~0ull;
             const bool take = j < n && k < T;
-            const unsigned long long b = __ballot(take);
-            if (!b) continue;
-            int at = 0;
-            if (lane == 0) at = atomicAdd(&inf.gcount, __popcll(b));
-            at = __shfl(at, 0);
-            if (take) out[at + __popcll(b & ((1ull << lane) - 1ull))] = k;
+            const int at = wave_append(take, &inf.gcount);
+            if (take) out[at] = k;
         }
     }
 }
@@ -515,22 +465,13 @@ __global__ __launch_bounds__(1024) void dw_topk_kernel(DetGeom g, DwWork w, int 
         if (tid == 0) counts[img] = 0;
         return;
     }
-    int P = 2;
-    while (P < n) P <<= 1;
+    const int P = next_pow2(n, 2);
     const unsigned long long *in = w.gbuf + (int64_t)img * kDwCap;
     for (int i = tid; i < P; i += 1024) tkey[i] = i < n ? in[i] : ~0ull;
     __syncthreads();
     det_bitonic_sort<1024>(tkey, P, tid);
-    const float4 *gb = w.boxes + (int64_t)g.roff[img] * w_bk;
-    for (int j = tid; j < k; j += 1024) {
-        const unsigned long long key = tkey[j];
-        const int cls = (int)(key & ((1ull << kDwClsBits) - 1ull)), row = (int)((key >> kDwClsBits) & kDwRowMask);
-        const int64_t slot = (int64_t)img * topk + j;
-        out_boxes[slot] = gb[row * w_bk + cls * w_cs];
-        out_scores[slot] = __uint_as_float(~(unsigned)(key >> (kDwRowBits + kDwClsBits)));
-        out_classes[slot] = cls;
-        out_rows[slot] = row;
-    }
+    merge_keys_write_out<1024>(tkey, k, w.boxes + (int64_t)g.roff[img] * w_bk, w_bk, w_cs, img, topk, out_boxes, out_scores, out_classes,
+                               out_rows);
     if (tid == 0) counts[img] = k;
 }
 
@@ -541,7 +482,7 @@ static int64_t dw_plan(const int *row_offsets, int n_images, int K, int per_clas
     LOCOV_REQUIRE(n_images >= 0 && n_images <= kDwMaxImages, "%s: too many images (0..%d per call)", who, kDwMaxImages);
     if (n_images == 0) return 0;
     LOCOV_REQUIRE(row_offsets, "%s: null row_offsets", who);
-    LOCOV_REQUIRE(K >= 1 && K < (1 << kDwClsBits), "%s: too many classes (1..%d)", who, (1 << kDwClsBits) - 1);
+    LOCOV_REQUIRE(K >= 1 && K < (1 << kKeyClsBits), "%s: too many classes (1..%d)", who, (1 << kKeyClsBits) - 1);
     LOCOV_REQUIRE(box_classes == 1 || box_classes == K, "%s: box_classes must be 1 or num_classes (%d), got %d", who, K, box_classes);
     LOCOV_REQUIRE(ld_deltas >= 4 * (int64_t)box_classes && ld_deltas % 4 == 0,
                   "%s: ld_deltas must cover the 4 x box_classes columns and be a multiple of 4", who);
@@ -556,7 +497,7 @@ static int64_t dw_plan(const int *row_offsets, int n_images, int K, int per_clas
     for (int i = 0; i < n_images; i++) {
         const int64_t rows = (int64_t)row_offsets[i + 1] - row_offsets[i];
         LOCOV_REQUIRE(rows >= 0, "%s: offsets must be non-decreasing", who);
-        LOCOV_REQUIRE(rows < (1 << kDwRowBits), "%s: too many rows (at most %d proposals per image)", who, (1 << kDwRowBits) - 1);
+        LOCOV_REQUIRE(rows < (1 << kKeyRowBits), "%s: too many rows (at most %d proposals per image)", who, (1 << kKeyRowBits) - 1);
         const int64_t W = (rows + 63) / 64;
         const int64_t cap = per_class_above <= 0 ? 0 : (per_class_above - 1 < rows * K ? per_class_above - 1 : rows * K);
         p->W[i] = (int)W;
@@ -642,16 +583,10 @@ static int dw_run(const char *who, const float *probs, int64_t ld_probs, int num
     e = hipMemsetAsync(zero0, 0, zero_bytes, s);
     if (e != hipSuccess) return set_error(LOCOV_ERR_LAUNCH, "%s: memset: %s", who, hipGetErrorString(e));
 
-    static int attr_state[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return set_error(LOCOV_ERR_LAUNCH, "%s: hipGetDevice", who);
     const int lds_max = kDwCap * 8;
-    if (attr_state[dev] == 0)
-        attr_state[dev] = (hipFuncSetAttribute(reinterpret_cast<const void *>(dw_segsort_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               lds_max) == hipSuccess &&
-                           hipFuncSetAttribute(reinterpret_cast<const void *>(dw_topk_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               lds_max) == hipSuccess) ? 1 : -1;
-    if (attr_state[dev] != 1) return set_error(LOCOV_ERR_LAUNCH, "%s: cannot raise the dynamic LDS limit to %d bytes", who, lds_max);
+    static std::atomic<int> segsort_lds[kMaxDevices], topk_lds[kMaxDevices];
+    if (int rc = raise_dynamic_lds(segsort_lds, reinterpret_cast<const void *>(dw_segsort_kernel), lds_max, who)) return rc;
+    if (int rc = raise_dynamic_lds(topk_lds, reinterpret_cast<const void *>(dw_topk_kernel), lds_max, who)) return rc;
 
     const float inv_wx = 1.0f / wx, inv_wy = 1.0f / wy, inv_ww = 1.0f / ww, inv_wh = 1.0f / wh;
     if (p.bk == 1 && ld_deltas == 4)
@@ -679,9 +614,7 @@ static int dw_run(const char *who, const float *probs, int64_t ld_probs, int num
         const int64_t items = cells > cap ? cells : cap;
         max_items = items > max_items ? items : max_items;
     }
-    int P = 2;
-    while (P < max_rows) P <<= 1;
-    hipLaunchKernelGGL(dw_segsort_kernel, dim3((unsigned)nK), dim3(256), (size_t)P * 8, s, w);
+    hipLaunchKernelGGL(dw_segsort_kernel, dim3((unsigned)nK), dim3(256), (size_t)next_pow2(max_rows, 2) * 8, s, w);
     const dim3 ov_grid((unsigned)ceil_div(max_items, 256), (unsigned)n_images), sweep_grid((unsigned)ceil_div(nK, 4));
     if (!p.cs) {
         if (max_items > 0) hipLaunchKernelGGL(dw_overlap_kernel<false>, ov_grid, dim3(256), 0, s, g, p, w, nms_thresh);

@@ -6,8 +6,8 @@
 // One thread per proposal walks ITS image's ground-truth boxes (a handful): what the torch form does with ~80 small launches per
 // batch (a quarter of a training step's launch count) and a [sum M, sum R] matrix.  Every arithmetic step is the torch op it
 // replaces, rounded individually (this file is built with -ffp-contract=off): the IoU values, hence the argmax (first maximum, as
-// torch.max), the threshold tests and the labels are the torch form's, bit for bit.
-#include "common.h"
+// torch.max), the threshold tests and the labels are the torch form's, bit for bit.  The IoU is select_common.h's box_pairwise_iou.
+#include "select_common.h"
 
 namespace locov {
 
@@ -32,24 +32,14 @@ __global__ __launch_bounds__(256) void label_proposals_kernel(const float4 *__re
     int img = 0;
     while (i >= g.roff[img + 1]) img++;                   // (a few images: a short scalar walk)
     const float4 b = boxes[i];
-    const float bw = b.z - b.x, bh = b.w - b.y;
-    const float area_b = bw * bh;
+    const float bw = b.z - b.x, bh = b.w - b.y;          // (the degenerate test below)
     // matched_vals, matches = quality.max(dim=0) over this image's rows; rows of other images carry -1 in the torch form and can
     // never win, an image without ground truth leaves (-1, row 0)
     float best = -1.f;
     int best_j = 0;
     bool bad = false;
     for (int j = g.goff[img]; j < g.goff[img + 1]; j++) {
-        const float4 a = gt[j];
-        const float area_a = (a.z - a.x) * (a.w - a.y);
-        float w = fminf(a.z, b.z) - fmaxf(a.x, b.x), h = fminf(a.w, b.w) - fmaxf(a.y, b.y);
-        // torch.min / torch.max propagate NaN (fminf / fmaxf do not); clamp_(min=0) keeps it
-        if (a.z != a.z || b.z != b.z || a.x != a.x || b.x != b.x) w = __builtin_nanf("");
-        if (a.w != a.w || b.w != b.w || a.y != a.y || b.y != b.y) h = __builtin_nanf("");
-        w = w < 0.f ? 0.f : w;
-        h = h < 0.f ? 0.f : h;
-        const float inter = w * h;
-        const float q = inter > 0.f ? inter / ((area_a + area_b) - inter) : 0.f;
+        const float q = box_pairwise_iou(gt[j], b);
         bad |= !(q >= 0.f);
         const bool first = j == g.goff[img];
         if (first || q > best || (q != q && best == best)) {          // strict >: the FIRST maximum; NaN counts as the maximum
@@ -109,8 +99,7 @@ __global__ __launch_bounds__(kSampleThreads) void sample_proposals_kernel(
     const int img = blockIdx.x, part = blockIdx.y, tid = threadIdx.x;
     const int r0 = g.roff[img], n = g.roff[img + 1] - r0;
     if (n <= 0) return;
-    int P = 1;
-    while (P < n) P <<= 1;
+    const int P = next_pow2(n, 1);
     const double *key = (part == 0 ? key_pos : key_neg) + r0;
     for (int i = tid; i < P; i += kSampleThreads) {
         k[i] = i < n ? key[i] : __builtin_inf();

@@ -4,27 +4,16 @@
 // fast_rcnn_inference -> batched_nms (ovr/modeling/roi_heads/roi_emb_heads.py:280,357; SURVEY.md
 // 8a-10).  torchvision is not available on the ROCm box; its semantics are kept: boxes visited in
 // descending score order, a box is dropped when its IoU with an already kept box is > threshold,
-// IoU = inter / (area_a + area_b - inter) on XYXY boxes.
+// IoU = inter / (area_a + area_b - inter) on XYXY boxes (select_common.h's box_iou_gt, the test every NMS of the library shares).
 //
 // Two kernels: (1) a KxK "who suppresses whom" bit matrix, 64x64 box pairs per workgroup with the
 // column boxes staged in LDS; (2) one workgroup sweeps the rows in score order, keeping the
 // removed-set as K/64 words in LDS (a box's row is OR-ed in only if the box survives).  The sweep
 // is inherently sequential in K but stays on the GPU: K = a few thousand candidates -> a few ms,
 // and nothing is copied to the host.
-#include "common.h"
+#include "select_common.h"
 
 namespace locov {
-
-// must round exactly as detect_common.h's det_iou_gt does (both files are compiled with -ffp-contract=off): change them together
-__device__ __forceinline__ bool iou_gt(const float4 a, const float4 b, float thr)
-{
-    const float left = fmaxf(a.x, b.x), right = fminf(a.z, b.z);
-    const float top = fmaxf(a.y, b.y), bottom = fminf(a.w, b.w);
-    const float w = fmaxf(right - left, 0.f), h = fmaxf(bottom - top, 0.f);
-    const float inter = w * h;
-    const float sa = (a.z - a.x) * (a.w - a.y), sb = (b.z - b.x) * (b.w - b.y);
-    return inter / (sa + sb - inter) > thr;
-}
 
 // boxes are already sorted by descending score.  mask[i][cb] bit j = box (cb*64+j) is suppressed by box i.
 __global__ __launch_bounds__(64) void nms_mask_kernel(const float4 *__restrict__ boxes, int K, float thr,
@@ -42,7 +31,7 @@ __global__ __launch_bounds__(64) void nms_mask_kernel(const float4 *__restrict__
     const int ncols = min(64, K - cbase);
     unsigned long long bits = 0;
     for (int j = (rb == cb) ? t + 1 : 0; j < ncols; j++)
-        if (iou_gt(me, cols[j], thr)) bits |= 1ull << j;
+        if (box_iou_gt(me, cols[j], thr)) bits |= 1ull << j;
     mask[(int64_t)i * col_blocks + cb] = bits;
 }
 

@@ -361,17 +361,9 @@ int locov_roi_align_nhwc_bwd(const float *grad_rows, int64_t grad_ld, int N, int
     // developer A/B: LOCOV_POOL_BWD_WINDOW=<bytes>, 0 -> every proposal scatters straight to memory
     const char *we = getenv("LOCOV_POOL_BWD_WINDOW");          // (read per launch: tests flip it)
     const int win_bytes = we ? atoi(we) : 20480;
-    // (the attribute belongs to the kernel's code object on ONE device: set once per device a launch is made on -- a process that
-    // drives several GPUs, or whose first call failed on one of them, must not decide for the others)
-    static int attr_state[64] = {};                            // per device: 0 = not tried, 1 = set, -1 = refused
-    int dev = 0;
-    bool attr_ok = false;
-    if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64) {
-        if (attr_state[dev] == 0)
-            attr_state[dev] = hipFuncSetAttribute(reinterpret_cast<const void *>(&roi_align_nhwc_bwd_kernel),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, 65536) == hipSuccess ? 1 : -1;
-        attr_ok = attr_state[dev] == 1;
-    }
+    // (a refusal is no error here -- every proposal then scatters straight to memory -- so the error text stays as it is: no `who`)
+    static std::atomic<int> window_lds[kMaxDevices];
+    const bool attr_ok = raise_dynamic_lds(window_lds, reinterpret_cast<const void *>(&roi_align_nhwc_bwd_kernel), 65536, nullptr) == LOCOV_OK;
     const int wb = attr_ok && win_bytes > 0 ? (win_bytes < 65536 ? win_bytes : 65536) : 0;
     hipLaunchKernelGGL(roi_align_nhwc_bwd_kernel, grid, dim3(kNhwcThreads), (size_t)wb, as_stream(stream), grad_rows, grad_ld, grad_feat, N, H,
                        W, C, rois, pooled_h, pooled_w, spatial_scale, sampling_ratio, aligned, bin_stride, OH, OW, pos_major, nslices, R, wb / 4);

@@ -11,7 +11,7 @@
 //                        buffer; those keys are gathered and sorted in LDS (bitonic); the first P are decoded (det_apply_deltas),
 //                        tested for inf / NaN, clipped (det_clip) and size-filtered: boxes, logits, indices in selection order and
 //                        one bit per position (1 = passed the size filter)
-//   rpn_overlap_kernel   the upper triangle of the P x ceil(P / 64) bit matrix: bit k of word wd of row j = det_iou_gt(box j,
+//   rpn_overlap_kernel   the upper triangle of the P x ceil(P / 64) bit matrix: bit k of word wd of row j = box_iou_gt(box j,
 //                        box 64 wd + k); a wave per (64 rows, one word column), the column's boxes handed round from their lanes
 //   rpn_sweep_kernel     a workgroup per image, thread t owns word t of the removed set (filtered boxes start removed: they are
 //                        never kept, so they suppress nothing).  Per 64 positions: every wave walks the diagonal 64 x 64 block in
@@ -20,8 +20,6 @@
 //
 // The select is one workgroup per image: five passes over an image's logits at most (usually two), each read coalesced from L2.
 // Every cross-workgroup hand-off is a kernel boundary.
-#include <atomic>
-
 #include "detect_common.h"
 
 namespace locov {
@@ -83,6 +81,9 @@ __global__ __launch_bounds__(kRpnSelThreads) void rpn_select_kernel(const float 
             if ((key >> (shift + kRpnDigit)) == pre) atomicAdd(&hist[(int)(key >> shift) & (kRpnBins - 1)], 1);
         }
         __syncthreads();
+        // (The scan, the pick and the gather's append below are this kernel's own text, not select_common.h's radix_pick and
+        //  wave_append: with the helpers the compiler ordered the same instructions differently and the kernel measured 1 % slower
+        //  at 4 x 63 000 anchors -- docs/experiments.md.  With this text its machine code is what it was before the header existed.)
         const int v0 = hist[2 * tid], v1 = hist[2 * tid + 1], sum = v0 + v1;
         int incl = sum;
 #pragma unroll
@@ -135,8 +136,7 @@ __global__ __launch_bounds__(kRpnSelThreads) void rpn_select_kernel(const float 
     }
     __syncthreads();
     const int n = ctl[3];                                        // P <= n <= cap
-    int P2 = 2;
-    while (P2 < n) P2 <<= 1;
+    const int P2 = next_pow2(n, 2);
     for (int i = n + tid; i < P2; i += kRpnSelThreads) skey[i] = ~0ull;
     __syncthreads();
     det_bitonic_sort<kRpnSelThreads>(skey, P2, tid);
@@ -171,16 +171,6 @@ __global__ __launch_bounds__(kRpnSelThreads) void rpn_select_kernel(const float 
     if (__ballot(nonfinite) != 0ull && lane == 0) atomicOr(w.flags, LOCOV_RPN_FLAG_NONFINITE);
 }
 
-__device__ __forceinline__ float4 rpn_lane_box(const float4 v, int j)          // lane j's box (j uniform over the wave)
-{
-    float4 e;
-    e.x = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v.x), j));
-    e.y = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v.y), j));
-    e.z = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v.z), j));
-    e.w = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v.w), j));
-    return e;
-}
-
 // grid (row chunks, ceil(W / 4), images): wave `wave` of a workgroup has word column 4 blockIdx.y + wave of the 64 rows
 __global__ __launch_bounds__(256) void rpn_overlap_kernel(int P, float nms_thr, RpnWork w)
 {
@@ -192,7 +182,7 @@ __global__ __launch_bounds__(256) void rpn_overlap_kernel(int P, float nms_thr, 
     const float4 a = gb[row], col = gb[64 * wd + lane];          // (rows P .. Pa - 1 hold zero boxes)
     const int lim = min(64, P - 64 * wd);
     unsigned long long bits = 0;
-    for (int k = 0; k < lim; k++) bits |= (unsigned long long)det_iou_gt(a, rpn_lane_box(col, k), nms_thr) << k;
+    for (int k = 0; k < lim; k++) bits |= (unsigned long long)box_iou_gt(a, lane_box(col, k), nms_thr) << k;
     w.M[((int64_t)img * Pa + row) * W + wd] = bits;
 }
 
@@ -241,7 +231,7 @@ __global__ __launch_bounds__(256) void rpn_sweep_kernel(int P, int post, RpnWork
             }
         }
         if (t < 64 && ((keep >> lane) & 1ull)) {
-            const int slot = nk + __popcll(keep & ((1ull << lane) - 1ull));
+            const int slot = nk + lanes_below(keep);
             if (slot < post) {
                 const int64_t src = base + 64 * c + lane, dst = (int64_t)img * post + slot;
                 out_boxes[dst] = w.boxes[src];
@@ -301,8 +291,7 @@ int locov_rpn_proposals(const float *logits, const float *deltas, const float *a
     LOCOV_REQUIRE(((uintptr_t)deltas | (uintptr_t)anchors | (uintptr_t)workspace | (uintptr_t)out_boxes) % 16 == 0,
                   "%s: deltas / anchors / workspace / out_boxes must be 16-byte aligned", who);
     const int P = (int)(hwa < pre_nms_topk ? hwa : pre_nms_topk), W = (P + 63) / 64, Pa = 64 * W;
-    int cap = 64;                                                // the sort buffer: the next power of two at or above P
-    while (cap < P) cap <<= 1;
+    const int cap = next_pow2(P, 64);                            // the sort buffer: the next power of two at or above P
     RpnGeom g{};
     for (int i = 0; i < n_images; i++) {
         g.h[i] = image_hw[2 * i];
@@ -322,16 +311,9 @@ int locov_rpn_proposals(const float *logits, const float *deltas, const float *a
     w.sidx = reinterpret_cast<int *>(ws);
     w.flags = counts_and_flags + n_images;
 
-    static std::atomic<int> attr_state[64];                      // per device: 0 = not asked yet, 1 = raised, -1 = refused
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return set_error(LOCOV_ERR_LAUNCH, "%s: hipGetDevice", who);
-    const int lds_max = kRpnMaxPre * 8 + kRpnBins * 4 + 128;
-    if (attr_state[dev].load(std::memory_order_relaxed) == 0)
-        attr_state[dev].store(hipFuncSetAttribute(reinterpret_cast<const void *>(rpn_select_kernel),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, lds_max) == hipSuccess ? 1 : -1,
-                              std::memory_order_relaxed);
-    if (attr_state[dev].load(std::memory_order_relaxed) != 1)
-        return set_error(LOCOV_ERR_LAUNCH, "%s: cannot raise the dynamic LDS limit to %d bytes", who, lds_max);
+    static std::atomic<int> select_lds[kMaxDevices];
+    if (int rc = raise_dynamic_lds(select_lds, reinterpret_cast<const void *>(rpn_select_kernel), kRpnMaxPre * 8 + kRpnBins * 4 + 128, who))
+        return rc;
     hipStream_t s = as_stream(stream);
     hipError_t e = hipMemsetAsync(counts_and_flags, 0, sizeof(int) * (size_t)(n_images + 1), s);
     if (e != hipSuccess) return set_error(LOCOV_ERR_LAUNCH, "%s: memset: %s", who, hipGetErrorString(e));

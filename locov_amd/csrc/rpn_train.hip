@@ -20,9 +20,10 @@
 //                       and its gradient for labels == 1, zeros elsewhere; fp64 partials per block, summed in block order by
 //                       rpn_loss_finish_kernel (no float atomics: the same inputs give the same bits)
 //
-// rpn_iou is used by both phases of the labelling: the promotion's `==` needs the two to round identically.  Its expression is
-// label.hip's, which is torch's pairwise_iou step by step (this file is built with -ffp-contract=off).
+// Both phases of the labelling take the IoU from select_common.h's box_pairwise_iou (the promotion's `==` needs the two to round
+// identically; this file is built with -ffp-contract=off), and the sampler's digit pick is that header's radix_pick.
 #include "box_delta_common.h"
+#include "select_common.h"
 
 namespace locov {
 
@@ -32,21 +33,6 @@ constexpr int kRtGtChunk = 256;                                  // ground-truth
 constexpr int kRtMaxAnchors = 1 << 22;
 constexpr int kRtSelThreads = 1024, kRtSelWaves = kRtSelThreads / kWave;
 constexpr int kRtDigit = 11, kRtBins = 1 << kRtDigit, kRtPasses = 6;             // 64-bit keys: 9 + 5 x 11 bits
-
-// pairwise_iou of (ground-truth box a, anchor b): torch's ops, each rounded on its own
-__device__ __forceinline__ float rpn_iou(const float4 a, const float4 b)
-{
-    const float area_a = (a.z - a.x) * (a.w - a.y);
-    const float area_b = (b.z - b.x) * (b.w - b.y);
-    float w = fminf(a.z, b.z) - fmaxf(a.x, b.x), h = fminf(a.w, b.w) - fmaxf(a.y, b.y);
-    // torch.min / torch.max propagate NaN (fminf / fmaxf do not); clamp_(min=0) keeps it
-    if (a.z != a.z || b.z != b.z || a.x != a.x || b.x != b.x) w = __builtin_nanf("");
-    if (a.w != a.w || b.w != b.w || a.y != a.y || b.y != b.y) h = __builtin_nanf("");
-    w = w < 0.f ? 0.f : w;
-    h = h < 0.f ? 0.f : h;
-    const float inter = w * h;
-    return inter > 0.f ? inter / ((area_a + area_b) - inter) : 0.f;
-}
 
 __global__ __launch_bounds__(kRtThreads) void rpn_gt_max_kernel(const float4 *__restrict__ anchors, int hwa, const float4 *__restrict__ gt,
                                                                 int n_gt, unsigned *__restrict__ slots)
@@ -71,7 +57,7 @@ __global__ __launch_bounds__(kRtThreads) void rpn_gt_max_kernel(const float4 *__
             unsigned m = 0u;
 #pragma unroll
             for (int k = 0; k < kRtPerThread; k++) {
-                const unsigned q = live[k] ? __float_as_uint(rpn_iou(a, b[k])) : 0u;
+                const unsigned q = live[k] ? __float_as_uint(box_pairwise_iou(a, b[k])) : 0u;
                 m = q > m ? q : m;
             }
 #pragma unroll
@@ -113,7 +99,7 @@ __global__ __launch_bounds__(kRtThreads) void rpn_label_kernel(const float4 *__r
         int best_j = g0;
         bool promote = false;
         for (int j = g0; j < g1; j++) {
-            const float q = rpn_iou(gt[j], b);
+            const float q = box_pairwise_iou(gt[j], b);
             if (j == g0 || q > best || (q != q && best == best)) {
                 best = q;
                 best_j = j;
@@ -177,29 +163,8 @@ __global__ __launch_bounds__(kRtSelThreads) void rpn_sample_kernel(const signed 
                     atomicAdd(&hist[(int)(key >> shift) & (kRtBins - 1)], 1);                  // (integer counts in LDS: order-independent)
             }
             __syncthreads();
-            const int v0 = hist[2 * tid], v1 = hist[2 * tid + 1], sum = v0 + v1;
-            int incl = sum;
-#pragma unroll
-            for (int o = 1; o < kWave; o <<= 1) {
-                const int t = __shfl_up(incl, o);
-                if (lane >= o) incl += t;
-            }
-            if (lane == kWave - 1) wave_sum[wave] = incl;
-            __syncthreads();
-            int cum = incl - sum;
-            for (int q = 0; q < wave; q++) cum += wave_sum[q];
-            if (cum < need && need <= cum + v0) {
-                ctl[0] = 2 * tid;
-                ctl[1] = cum;
-                ctl[2] = v0;
-            }
-            cum += v0;
-            if (cum < need && need <= cum + v1) {
-                ctl[0] = 2 * tid + 1;
-                ctl[1] = cum;
-                ctl[2] = v1;
-            }
-            __syncthreads();
+            const int v[2] = {hist[2 * tid], hist[2 * tid + 1]};
+            radix_pick<kRtSelThreads>(v, need, wave_sum, ctl);
             pre = (pre << kRtDigit) | (unsigned long long)ctl[0];
             need -= ctl[1];
             const int in_bin = ctl[2];
@@ -237,7 +202,7 @@ __global__ __launch_bounds__(kRtSelThreads) void rpn_sample_kernel(const signed 
                 before += q < wave ? c : 0;
                 total += c;
             }
-            if (tie) take = before + (int)__popcll(bt & ((1ull << lane) - 1ull)) < need;
+            if (tie) take = before + lanes_below(bt) < need;
             ties_seen += total;
             __syncthreads();
         }

@@ -332,6 +332,66 @@ def test_nms_matches_oracle(ops, oracle, K):
     assert ops.nms(dev(boxes[:0]), dev(scores[:0]), 0.5).numel() == 0
 
 
+def _iou_decision_boxes():
+    """130 integer boxes (corners <= 1024) whose IoU decisions sit on and next to the thresholds 1/2 and 3/4.
+    Clusters live in cells of their own (256 x 12 pixels), so only a cluster's members overlap: a 200 x 8 base box and a probe of
+    the same height and corner, w pixels wide -- IoU = w / 200: exactly 1/2 (100), just above (101), just below (99), and the same
+    round 3/4 (150, 151, 149).  One exact duplicate of a base box; ONE zero-area box, inside a base box: its intersection with
+    anything is 0 and every union it is part of is the other box's positive area, so no 0 / 0 pair arises.  The positions are
+    shuffled, so that bases and probes meet inside a 64-bit word of the overlap sets and across words."""
+    cells = [(256 * (k % 4), 12 * (k // 4)) for k in range(66)]
+    boxes = []
+    for k in range(63):
+        ox, oy = cells[k]
+        boxes.append((ox, oy, ox + 200, oy + 8))
+        boxes.append((ox, oy, ox + (100, 101, 99, 150, 151, 149)[k % 6], oy + 8))
+    boxes.append(boxes[0])                                      # duplicate of cluster 0's base
+    boxes.append((256 + 50, 0, 256 + 50, 8))                    # zero area, inside cluster 1's base
+    for k in (63, 64):                                          # two boxes on their own
+        ox, oy = cells[k]
+        boxes.append((ox, oy, ox + 200, oy + 8))
+    tail = [boxes.pop(2 * 61 + 1), boxes.pop(2 * 60 + 1)]       # the probes of clusters 61 (101 wide) and 60 (100 wide) go last:
+    boxes = [boxes[i] for i in np.random.default_rng(130).permutation(len(boxes))] + tail       # positions 128, 129 = the third word
+    assert len(boxes) == 130 and max(max(b) for b in boxes) <= 1024
+    return boxes
+
+
+def _exact_iou_gt(a, b, thr):
+    from fractions import Fraction
+    inter = max(min(a[2], b[2]) - max(a[0], b[0]), 0) * max(min(a[3], b[3]) - max(a[1], b[1]), 0)
+    union = (a[2] - a[0]) * (a[3] - a[1]) + (b[2] - b[0]) * (b[3] - b[1]) - inter
+    return union != 0 and Fraction(inter, union) > thr          # (0 / 0: NaN > thr is False in fp32; the inputs hold no such pair)
+
+
+def test_nms_and_rpn_make_the_same_iou_decision(ops):
+    """ops.nms and ops.rpn_proposals (both through select_common.h's box_iou_gt) against a greedy sweep in exact rational
+    arithmetic.  Integer corners <= 1024: areas and unions are integers below 2^24, so the fp32 quotient compares with the dyadic
+    thresholds as the true ratio does.  Scores descend strictly: position = index in both pipelines."""
+    from fractions import Fraction
+    boxes_i = _iou_decision_boxes()
+    n = len(boxes_i)
+    half = [(i, j) for i in range(n) for j in range(i + 1, n)
+            if not _exact_iou_gt(boxes_i[i], boxes_i[j], Fraction(1, 2)) and _exact_iou_gt(boxes_i[i], boxes_i[j], Fraction(99, 200))]
+    assert any(i >> 6 == j >> 6 for i, j in half) and any(i >> 6 != j >> 6 for i, j in half)        # diagonal and off-diagonal words
+    assert any(j >> 6 == 2 for i in range(n) for j in range(max(i + 1, 128), n) if _exact_iou_gt(boxes_i[i], boxes_i[j], Fraction(1, 2)))
+    boxes = dev(np.asarray(boxes_i, dtype=np.float32))
+    scores = dev(np.linspace(1.0, 0.1, n).astype(np.float32))
+    assert bool((scores[1:] < scores[:-1]).all())
+    for thr in (Fraction(1, 2), Fraction(3, 4)):
+        want = []
+        for j in range(n):                                      # greedy: kept unless an earlier KEPT box overlaps it
+            if not any(_exact_iou_gt(boxes_i[i], boxes_i[j], thr) for i in want):
+                want.append(j)
+        assert 0 < len(want) < n
+        got = ops.nms(boxes, scores, float(thr)).cpu().tolist()
+        assert got == want, f"ops.nms at {thr}"
+        out = ops.rpn_proposals(scores[None], torch.zeros((1, n, 4), device="cuda"), boxes, [(2048, 2048)], (1.0, 1.0, 1.0, 1.0),
+                                4.135, n, n, -1.0, float(thr))
+        assert out is not None
+        got = out[2][0, :out[3][0]].cpu().tolist()
+        assert got == want, f"ops.rpn_proposals at {thr}"
+
+
 def test_batched_nms_and_inference_on_device(ops, oracle):
     from locov_amd.roi_heads import box_emb_head as beh
     rng = np.random.default_rng(4)
