@@ -37,7 +37,7 @@ extern "C" {
  *    locov_detect_postprocess_cs / _wide_cs (+ _workspace_bytes), locov_grounding_align_fwd / _bwd,
  *    locov_grounding_triplet_fwd / _bwd, locov_mha_fwd / _bwd, locov_rpn_proposals (+ _workspace_bytes),
  *    locov_rpn_label_anchors (+ _workspace_bytes), locov_rpn_sample_anchors, locov_rpn_loss (+ _workspace_bytes),
- *    locov_resnet_stem_fwd */
+ *    locov_resnet_stem_fwd, locov_resnet_stem_fwd_sel, locov_resnet_stem_wgrad (+ _workspace_bytes) */
 #define LOCOV_ABI_VERSION 8
 
 #define LOCOV_OK 0
@@ -1264,6 +1264,37 @@ int locov_mha_bwd(const float *q, int64_t ldq, const float *k, int64_t ldk, cons
  *   whose tiles leave the launch grid: LOCOV_ERR_INVALID_ARG before any launch.  N == 0: LOCOV_OK, nothing is read or written. */
 int locov_resnet_stem_fwd(const float *x, int N, int H, int W, const float *w, const float *scale, const float *shift, int Cout,
                           float *y, locov_stream_t stream);
+
+/* ---- the stem under autograd (csrc/resnet_stem.hip): its only trainable tensor is conv1.weight -------------------------------
+ * Added under ABI version 8.
+ *
+ * locov_resnet_stem_fwd_sel: the training forward.  The same kernel as locov_resnet_stem_fwd -- y is bit-identical -- that also
+ * writes, per pooled element, which conv position its gradient goes to:
+ *   sel   : out, uint8 [N, PH, PW, Cout].  3 di + dj (0 .. 8): the conv position (2p - 1 + di, 2q - 1 + dj) that FIRST attains the
+ *           window maximum in row-major scan (torch's max-pool rule) when that maximum is > 0; 9 when the pooled value is 0
+ *           (nothing passes the ReLU).  Only positions that exist (0 <= row < CH, 0 <= column < CW) compete.
+ *   Everything else, and every error, as locov_resnet_stem_fwd (sel must not be null).
+ *
+ * locov_resnet_stem_wgrad: the weight gradient.
+ *   gconv[n, i, j, o] = sum of g[n, p, q, o] over the (up to four) windows (p, q) whose sel names conv position (i, j)
+ *   dw[o, c, u, v]    = scale[o] * sum_{n, i, j} gconv[n, i, j, o] x[n, c, 2 i - 3 + u, 2 j - 3 + v]      (zero outside the image)
+ *   x     : fp32 [N, 3, H, W], NCHW, contiguous (the forward's).
+ *   g     : fp32 [N, PH, PW, Cout]: the gradient of the pooled map y, channels-last.
+ *   sel   : uint8 [N, PH, PW, Cout] of locov_resnet_stem_fwd_sel (an element with code 9 passes nothing, whatever its g).
+ *   scale : fp32 [Cout], the FrozenBN fold's scale.
+ *   dw    : out, fp32 [Cout, 3, 7, 7] (overwritten, not accumulated into).
+ *   workspace: at least locov_resnet_stem_wgrad_workspace_bytes(N, H, W) bytes, 4-byte aligned (per-workgroup partials; at most
+ *           512 x 147 x 64 floats whatever N is).
+ *   fp32 products and accumulation.  Per-wave partial sums are reduced in a fixed order (in the workgroup through LDS, across
+ *   workgroups by a second small launch): no atomics, two calls give the same bits, nothing is read by the host.
+ * Supported: Cout == 64.  Cout != 64, N < 0, H or W <= 0, a null or misaligned pointer, sizes whose element offsets leave int64,
+ *   a workspace that is too small: LOCOV_ERR_INVALID_ARG before any launch.  N == 0: LOCOV_OK, nothing is read or written.
+ * locov_resnet_stem_wgrad_workspace_bytes: 0 for N <= 0 or H, W <= 0. */
+int locov_resnet_stem_fwd_sel(const float *x, int N, int H, int W, const float *w, const float *scale, const float *shift, int Cout,
+                              float *y, uint8_t *sel, locov_stream_t stream);
+int64_t locov_resnet_stem_wgrad_workspace_bytes(int N, int H, int W);
+int locov_resnet_stem_wgrad(const float *x, int N, int H, int W, const float *g, const uint8_t *sel, const float *scale, int Cout,
+                            float *dw, void *workspace, int64_t workspace_bytes, locov_stream_t stream);
 
 #ifdef __cplusplus
 }

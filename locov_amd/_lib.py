@@ -216,6 +216,9 @@ SIGNATURES = {
     "locov_mha_bwd": (c_int, [_p, c_int64, _p, c_int64, _p, c_int64, _p, _p, c_float, c_float, c_int, c_int, c_int, c_int, _p,
                               c_int64, _p, _p, _p, c_int64, _p, c_int64, _p, c_int64, _p]),
     "locov_resnet_stem_fwd": (c_int, [_p, c_int, c_int, c_int, _p, _p, _p, c_int, _p, _p]),
+    "locov_resnet_stem_fwd_sel": (c_int, [_p, c_int, c_int, c_int, _p, _p, _p, c_int, _p, _p, _p]),
+    "locov_resnet_stem_wgrad_workspace_bytes": (c_int64, [c_int, c_int, c_int]),
+    "locov_resnet_stem_wgrad": (c_int, [_p, c_int, c_int, c_int, _p, _p, _p, c_int, _p, _p, c_int64, _p]),
 }
 
 _lib = None

@@ -6,7 +6,7 @@ OvrRCNN (ovr/modeling/meta_arch/ovr_rcnn.py) and the STT fine-tune.  This module
 names, constructor arguments, config keys, attributes and state-dict keys -- so that a Detectron2 checkpoint's
 backbone.{stem.conv1,res2.0.conv1,...}.{weight,norm.*} load unchanged.
 
-forward(x) -> {"res4": [N,1024,H/16,W/16]}, contiguous NCHW as upstream, takes one of two paths:
+forward(x) -> {"res4": [N,1024,H/16,W/16]}, contiguous NCHW as upstream, takes one of three paths:
 
   device path   x fp32 on a ROCm device, every norm FrozenBN, STRIDE_IN_1X1, ungrouped convolutions, a 64-channel stem, and no
                 gradient wanted (grad disabled, or nothing in the module requires grad).  The stem is ONE launch
@@ -14,11 +14,21 @@ forward(x) -> {"res4": [N,1024,H/16,W/16]}, contiguous NCHW as upstream, takes o
                 channels-last pixel rows through Res5Stage.forward_rows (fp32 MFMA GEMMs with FrozenBN / ReLU / residual in the
                 epilogue, the implicit 3x3) behind ops.rows_stride2 where it strides; ops.nhwc_to_nchw once per requested feature.
                 fp32 throughout.
-  torch path    everything else (CPU tensors, trainable weights with grad enabled, BN, grouped or STRIDE_IN_1X1=False blocks): the
-                plain differentiable torch expression of the same modules.  Silent; it is the definition of the result.
+  device training path   opt-in (MODEL.BACKBONE.TRAIN_ON_DEVICE / ResNet.train_on_device, default off): the same input and
+                structural conditions, a gradient wanted for some weight, none for x.  The frozen prefix (FREEZE_AT: the stem
+                and / or leading stages without a trainable parameter) runs the inference kernels above under no_grad; a
+                trainable stem is ops.resnet_stem_train / ops.resnet_stem_wgrad under autograd (the forward saves which conv
+                position every pooled element came from, the backward is the weight gradient alone: images carry no
+                gradient); every stage from the first trainable one on is res5_train.res5_rows (f32 MFMA GEMMs forward, masked
+                NT / TN GEMMs backward, im2col for the 3x3) behind res5_train.grid_rows where it strides -- also a frozen stage
+                behind a trainable one, whose input carries the graph; res5_train.to_nchw per requested feature.  fp32, no
+                range guard, no host wait in forward or backward.
+  torch path    everything else (CPU tensors, BN, grouped or STRIDE_IN_1X1=False blocks, x.requires_grad, and trainable weights
+                with grad enabled unless the training path was asked for): the plain differentiable torch expression of the
+                same modules.  Silent; it is the definition of the result.
 
-Not here: gradients through the device path (training through res2-res4 stays on the torch path), split-f16 arithmetic for the
-backbone, pixel normalisation and ImageList padding (the caller's, as upstream: they happen in the meta-architecture).
+Not here: split-f16 arithmetic for the backbone, trainable BN, a data gradient for the images, pixel normalisation and ImageList
+padding (the caller's, as upstream: they happen in the meta-architecture).
 """
 from __future__ import annotations
 
@@ -29,7 +39,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from . import ops
+from . import ops, res5_train
 from .registry import Registry
 from .res5 import BottleneckBlock, Conv2d, FrozenBatchNorm2d, Res5Stage, get_norm
 from .res5_operands import conv_version
@@ -56,6 +66,22 @@ def _freeze(module: nn.Module) -> nn.Module:
     return module
 
 
+class _StemTrainFn(torch.autograd.Function):
+    """The stem under autograd on the device: y = ops.resnet_stem_train(images, weight, scale, shift), differentiable in the
+    weight alone (FrozenBN is buffers, images carry no gradient).  saved_tensors: (images, sel, scale)."""
+
+    @staticmethod
+    def forward(ctx, images, weight, scale, shift):
+        y, sel = ops.resnet_stem_train(images, weight.detach(), scale, shift)
+        ctx.save_for_backward(images, sel, scale)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        images, sel, scale = ctx.saved_tensors
+        return None, ops.resnet_stem_wgrad(images, g, sel, scale), None, None
+
+
 class BasicStem(nn.Module):
     """[D2-upstream] the standard ResNet stem: conv1 7x7 / 2 (+ norm), ReLU, max-pool 3x3 / 2."""
 
@@ -77,14 +103,23 @@ class BasicStem(nn.Module):
         return self.in_channels == 3 and self.out_channels == 64 and isinstance(self.conv1.norm, FrozenBatchNorm2d)
 
     @torch.no_grad()
-    def forward_rows(self, x: torch.Tensor) -> torch.Tensor:
-        """x [N,3,H,W] on the device -> the pooled map, channels-last [N,PH,PW,64], in one launch."""
+    def _folded(self):
         version = conv_version(self.conv1, weight=False)
         if self._fold is None or self._fold[0] != version:
             n = self.conv1.norm
             self._fold = (version, ops.frozen_bn_fold(n.weight, n.bias, n.running_mean, n.running_var, n.eps))
-        scale, shift = self._fold[1]
+        return self._fold[1]
+
+    @torch.no_grad()
+    def forward_rows(self, x: torch.Tensor) -> torch.Tensor:
+        """x [N,3,H,W] on the device -> the pooled map, channels-last [N,PH,PW,64], in one launch."""
+        scale, shift = self._folded()
         return ops.resnet_stem(x, self.conv1.weight.detach(), scale, shift)
+
+    def forward_rows_train(self, x: torch.Tensor) -> torch.Tensor:
+        """forward_rows under autograd: the same values, differentiable in conv1.weight (one more launch pair in backward)."""
+        scale, shift = self._folded()
+        return _StemTrainFn.apply(x.detach(), self.conv1.weight, scale, shift)
 
 
 class ResNet(nn.Module):
@@ -92,8 +127,9 @@ class ResNet(nn.Module):
     nn.Sequential of blocks -- here a Res5Stage, which also owns the stage's folded GEMM operands)."""
 
     def __init__(self, stem: BasicStem, stages: List[List[nn.Module]], num_classes: Optional[int] = None,
-                 out_features: Optional[List[str]] = None, freeze_at: int = 0):
+                 out_features: Optional[List[str]] = None, freeze_at: int = 0, train_on_device: bool = False):
         super().__init__()
+        self.train_on_device = bool(train_on_device)      # MODEL.BACKBONE.TRAIN_ON_DEVICE: may be set afterwards
         if num_classes is not None:
             raise NotImplementedError("ResNet(num_classes=...): the classification head (avgpool + linear) is not part of the C4 backbone")
         self.stem = stem
@@ -155,6 +191,19 @@ class ResNet(nn.Module):
             return False
         if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
             return False
+        return self._rows_structure_ok()
+
+    def train_path_ok(self, x: torch.Tensor) -> bool:
+        """The device training path computes forward(x) and its weight gradients: asked for (train_on_device), the input and
+        structure of device_path_ok, a gradient wanted for some weight and none for x."""
+        if not (self.train_on_device and isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
+                and x.shape[0] > 0):
+            return False
+        if not torch.is_grad_enabled() or x.requires_grad or not any(p.requires_grad for p in self.parameters()):
+            return False
+        return self._rows_structure_ok()
+
+    def _rows_structure_ok(self) -> bool:
         return self.stem.supports_rows_path() and all(
             stage.supports_rows_path() and all(blk.stride in (1, 2) and blk.conv2.in_channels % 32 == 0 and
                                                (blk.shortcut is None or isinstance(blk.shortcut.norm, FrozenBatchNorm2d)) and
@@ -163,7 +212,9 @@ class ResNet(nn.Module):
 
     def forward(self, x: torch.Tensor) -> Dict[str, torch.Tensor]:
         assert x.dim() == 4, f"ResNet takes an input of shape (N, C, H, W). Got {x.shape} instead!"
-        return self._forward_device(x) if self.device_path_ok(x) else self._forward_torch(x)
+        if self.device_path_ok(x):
+            return self._forward_device(x)
+        return self._forward_device_train(x) if self.train_path_ok(x) else self._forward_torch(x)
 
     def _forward_torch(self, x: torch.Tensor) -> Dict[str, torch.Tensor]:
         outputs = {}
@@ -194,6 +245,54 @@ class ResNet(nn.Module):
             if name in self._out_features:
                 outputs[name] = ops.nhwc_to_nchw(rows.view(N, H, W, C))
         return outputs
+
+    def _forward_device_train(self, x: torch.Tensor) -> Dict[str, torch.Tensor]:
+        outputs = {}
+        N = x.shape[0]
+        graph = any(p.requires_grad for p in self.stem.parameters())       # does `rows` carry a graph yet?
+        nhwc = self.stem.forward_rows_train(x) if graph else self.stem.forward_rows(x)
+        H, W, C = nhwc.shape[1:]
+        if "stem" in self._out_features:
+            outputs["stem"] = res5_train.to_nchw(nhwc.view(N * H * W, C), N, H, W) if graph else ops.nhwc_to_nchw(nhwc)
+        rows = nhwc.view(N * H * W, C)
+        for name, stage in zip(self.stage_names, self.stages):
+            if not graph and not any(p.requires_grad for p in stage.parameters()):      # the frozen prefix: the inference kernels
+                with torch.no_grad():
+                    if stage[0].stride == 2:
+                        rows = ops.rows_stride2(rows.view(N, H, W, C), N, H, W, True)
+                        H, W = (H + 1) // 2, (W + 1) // 2
+                    rows = stage.forward_rows(rows, H, W, pos_major=False, winograd=False, split=False)
+            else:
+                if stage[0].stride == 2:
+                    rows = res5_train.grid_rows(rows.view(N, H, W, C))
+                    H, W = (H + 1) // 2, (W + 1) // 2
+                rows = res5_train.res5_rows(stage, rows, N, H, W, pooled=False, split=False, overflow_check=False)
+                graph = True
+            C = rows.shape[1]
+            if name in self._out_features:
+                outputs[name] = res5_train.to_nchw(rows, N, H, W) if graph else ops.nhwc_to_nchw(rows.view(N, H, W, C))
+        return outputs
+
+    def saved_training_state(self, out: torch.Tensor) -> Dict[str, object]:
+        """What the device training path kept for the backward of `out` (one of its outputs): {"stem": the stem's sel (uint8
+        [N,PH,PW,64]; absent when the stem is frozen), "res2": [(x, y1, y2, out) per block], ...} -- the post-ReLU activations
+        over the stage's pixel rows, i.e. the device's own active sets (stages of the frozen prefix keep nothing).  To be read
+        before out's backward, which frees what the nodes saved."""
+        state: Dict[str, object] = {}
+        stack, seen = [out.grad_fn], set()                  # (seen holds the nodes themselves: the id of a released wrapper is reused)
+        while stack:
+            n = stack.pop()
+            if n is None or n in seen:
+                continue
+            seen.add(n)
+            if "_StemTrainFn" in type(n).__name__:
+                state["stem"] = n.saved_tensors[1]
+            stack += [f for f, _ in n.next_functions]
+        for step, saved in res5_train.saved_activations_per_step(out):
+            for name, stage in zip(self.stage_names, self.stages):
+                if step.stage is stage:
+                    state[name] = [tuple(saved[4 * b:4 * b + 4]) for b in range(len(saved) // 4)]
+        return state
 
 
 @BACKBONE_REGISTRY.register()
@@ -232,7 +331,8 @@ def build_resnet_backbone(cfg, input_shape: ShapeSpec) -> ResNet:
         out_channels *= 2
         bottleneck_channels *= 2
         stages.append(blocks)
-    return ResNet(stem, stages, out_features=out_features, freeze_at=freeze_at)
+    return ResNet(stem, stages, out_features=out_features, freeze_at=freeze_at,
+                  train_on_device=bool(cfg.MODEL.BACKBONE.get("TRAIN_ON_DEVICE", False)))
 
 
 def build_backbone(cfg, input_shape: Optional[ShapeSpec] = None) -> ResNet:

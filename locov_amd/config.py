@@ -78,7 +78,9 @@ def get_cfg() -> CfgNode:
             "MASK_ON": False,
             "KEYPOINT_ON": False,
             "LOAD_EMB_PRED_FROM_MMSS_HEAD": False,                # config.py:13
-            "BACKBONE": {"NAME": "build_resnet_backbone", "FREEZE_AT": 2},   # [D2-upstream]; coco_lsm.yaml -> FREEZE_AT 0
+            # NAME, FREEZE_AT: [D2-upstream]; coco_lsm.yaml -> FREEZE_AT 0.  TRAIN_ON_DEVICE (this port): a backbone with trainable
+            # weights runs forward AND backward on the gfx950 kernels instead of the torch path (backbone.py; opt-in)
+            "BACKBONE": {"NAME": "build_resnet_backbone", "FREEZE_AT": 2, "TRAIN_ON_DEVICE": False},
             "PROPOSAL_GENERATOR": {"NAME": "RPN", "MIN_SIZE": 0},     # [D2-upstream]
             "ANCHOR_GENERATOR": {                                  # [D2-upstream]
                 "NAME": "DefaultAnchorGenerator",

@@ -1623,6 +1623,60 @@ def resnet_stem(images: torch.Tensor, weight: torch.Tensor, scale: torch.Tensor,
     return y
 
 
+def resnet_stem_train(images: torch.Tensor, weight: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor,
+                      out: Optional[torch.Tensor] = None, sel_out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """resnet_stem for a training step: (y, sel) with y bit-identical to resnet_stem's and sel uint8 [N,PH,PW,64], per pooled
+    element 3 di + dj of the conv position (2p - 1 + di, 2q - 1 + dj) that first attains the window maximum (torch's max-pool
+    rule), 9 where y is 0 -- what resnet_stem_wgrad routes the gradient by."""
+    images, weight = _dev(images, "images"), _dev(weight, "weight")
+    scale, shift = _dev(scale, "scale"), _dev(shift, "shift")
+    if images.dim() != 4 or images.shape[1] != 3 or min(images.shape[2:]) < 1:
+        raise ValueError(f"resnet_stem_train: images must be [N,3,H,W], got {tuple(images.shape)}")
+    Cout = weight.shape[0]
+    if tuple(weight.shape) != (Cout, 3, 7, 7) or tuple(scale.shape) != (Cout,) or tuple(shift.shape) != (Cout,):
+        raise ValueError(f"resnet_stem_train: weight must be [Cout,3,7,7] and scale, shift [Cout], got {tuple(weight.shape)}, "
+                         f"{tuple(scale.shape)}, {tuple(shift.shape)}")
+    N, _, H, W = images.shape
+    PH, PW = resnet_stem_shape(H, W)
+    y = _out(out, (N, PH, PW, Cout), images, "resnet_stem_train")
+    if sel_out is None:
+        sel = torch.empty((N, PH, PW, Cout), dtype=torch.uint8, device=images.device)
+    else:
+        sel = sel_out
+        if tuple(sel.shape) != (N, PH, PW, Cout) or sel.dtype != torch.uint8 or sel.device != images.device or not sel.is_contiguous():
+            raise ValueError(f"resnet_stem_train: sel_out must be a contiguous uint8 {(N, PH, PW, Cout)} tensor on {images.device}")
+    with torch.cuda.device(images.device):
+        check(_lib.load().locov_resnet_stem_fwd_sel(_ptr(images), N, H, W, _ptr(weight), _ptr(scale), _ptr(shift), Cout, _ptr(y),
+                                                    _ptr(sel), _stream(images)), "locov_resnet_stem_fwd_sel")
+    return y, sel
+
+
+def resnet_stem_wgrad(images: torch.Tensor, g: torch.Tensor, sel: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """The stem's weight gradient (csrc/resnet_stem.hip): dw [64,3,7,7] = scale[o] * sum gconv * x over the conv positions, gconv
+    the gradient g [N,PH,PW,64] of the pooled map routed by resnet_stem_train's sel.  Fixed-order reduction: no atomics, two
+    calls give the same bits."""
+    images, g, scale = _dev(images, "images"), _dev(g, "g"), _dev(scale, "scale")
+    sel = _dev(sel, "sel", dtype=torch.uint8)
+    if images.dim() != 4 or images.shape[1] != 3 or min(images.shape[2:]) < 1:
+        raise ValueError(f"resnet_stem_wgrad: images must be [N,3,H,W], got {tuple(images.shape)}")
+    N, _, H, W = images.shape
+    PH, PW = resnet_stem_shape(H, W)
+    Cout = scale.shape[0]
+    if tuple(g.shape) != (N, PH, PW, Cout) or tuple(sel.shape) != (N, PH, PW, Cout) or scale.dim() != 1:
+        raise ValueError(f"resnet_stem_wgrad: g and sel must be [{N},{PH},{PW},Cout] and scale [Cout], got {tuple(g.shape)}, "
+                         f"{tuple(sel.shape)}, {tuple(scale.shape)}")
+    lib = _lib.load()
+    dw = torch.empty((Cout, 3, 7, 7), dtype=torch.float32, device=images.device)
+    if N == 0:
+        return dw.zero_()
+    nbytes = int(lib.locov_resnet_stem_wgrad_workspace_bytes(N, H, W))
+    ws = _workspace("stem_wgrad", images, nbytes)
+    with torch.cuda.device(images.device):
+        check(lib.locov_resnet_stem_wgrad(_ptr(images), N, H, W, _ptr(g), _ptr(sel), _ptr(scale), Cout, _ptr(dw), _ptr(ws), ws.numel(),
+                                          _stream(images)), "locov_resnet_stem_wgrad")
+    return dw
+
+
 class _LinearFn(torch.autograd.Function):
     """y = x W^T + b on the f32 MFMA NT-GEMM kernel; backward: grad_x = g W as an NT GEMM against the transposed
     weight (one small weight-sized transpose), grad_W = g^T x on the TN kernel (no activation-sized transposes),

@@ -35,7 +35,7 @@ import torch
 from . import ops
 
 __all__ = ["res5_rows", "res5_grid", "res5_rois", "roi_align_even_rows", "to_nhwc", "Res5BlockFn", "Res5OutputFn", "Res5Step", "Segment",
-           "saved_activations"]
+           "saved_activations", "saved_activations_per_step"]
 
 _BWD_STREAMS = bool(int(os.environ.get("LOCOV_RES5_BWD_STREAMS", "1")))    # the grid segment's 3x3 gradients on a side stream (0: one stream)
 _SIDE_STREAMS = {}
@@ -611,6 +611,33 @@ def saved_activations(out: torch.Tensor) -> List[torch.Tensor]:
         _, y2, o = found[(bi, "tail")].saved_tensors
         saved += [x, y1, y2, o]
     return saved
+
+
+def saved_activations_per_step(out: torch.Tensor) -> List[Tuple["Res5Step", List[torch.Tensor]]]:
+    """saved_activations for a graph that chains several Res5Steps (the backbone's stages: saved_activations keys the nodes by
+    block index alone and cannot tell them apart): one (step, [x, y1, y2, out per block, block 0 first]) per step behind `out`,
+    in the order the walk from `out` meets them."""
+    found, order, stack, seen = {}, [], [out.grad_fn], set()    # (seen holds the nodes themselves: the id of a released wrapper is reused)
+    while stack:
+        n = stack.pop()
+        if n is None or n in seen:
+            continue
+        seen.add(n)
+        if "Res5BlockFn" in type(n).__name__:
+            if id(n.step) not in found:
+                found[id(n.step)] = {}
+                order.append(n.step)
+            found[id(n.step)][(n.bi, n.half)] = n
+        stack += [f for f, _ in n.next_functions]
+    result = []
+    for step in order:
+        nodes, saved = found[id(step)], []
+        for bi in sorted({k[0] for k in nodes}):
+            x, y1 = nodes[(bi, "head")].saved_tensors
+            _, y2, o = nodes[(bi, "tail")].saved_tensors
+            saved += [x, y1, y2, o]
+        result.append((step, saved))
+    return result
 
 
 def _guarded(stage, split, guard, device, build):

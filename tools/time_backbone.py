@@ -3,6 +3,7 @@ path (ops.resnet_stem + Res5Stage.forward_rows) against the module's own torch (
 
     timeout -k 10 900 python tools/time_backbone.py --images 1 [--iters 50] [--warmup 10] [--out records.json]
     timeout -k 10 900 python tools/time_backbone.py --images 8
+    timeout -k 10 900 python tools/time_backbone.py --train --images 4 [--freeze-at 0 2] [--iters 30]
 
   stem       ops.resnet_stem on N x 3 x 800 x 1333, device-event time of each call (median, 10th / 90th percentile) beside
              - the traffic floor: 29.9 MB of compulsory traffic per image (12.8 read + 17.1 written) at the HBM rate --peak-tbs
@@ -10,6 +11,11 @@ path (ops.resnet_stem + Res5Stage.forward_rows) against the module's own torch (
   backbone   forward of the same module through both paths under torch.no_grad(), alternating A/B/A/B (and swapping order) in one
              process, each side's own median and 10th / 90th percentile; the outputs are compared first.  From a torch.profiler run
              per side: the device time by kernel name, so that a slower side shows which launches lose.
+  --train    forward + backward (res4.backward(G)) of the same module with trainable weights through the device training path
+             (MODEL.BACKBONE.TRAIN_ON_DEVICE: ops.resnet_stem_train / resnet_stem_wgrad, res5_train.res5_rows per stage) and
+             through the torch (MIOpen, torch autograd) path, per MODEL.BACKBONE.FREEZE_AT of --freeze-at: alternating in one
+             process as above (>= 10 warm-up, >= 30 timed), the largest relative difference between the two sides' weight
+             gradients, each side's peak device memory over one step, and the device time by kernel name.
 SURVEY.md 8d protocol: >= 10 warm-up and >= 50 timed iterations, device events, one process.  Needs a ROCm GPU.
 """
 from __future__ import annotations
@@ -69,6 +75,61 @@ def kernels(step, top=12):
             "top": [[k[:96], v[0], round(v[1], 1)] for k, v in rows[:top]]}
 
 
+def peak_mb(step):
+    """Peak device memory of one call above what is allocated in front of it, MB."""
+    torch.cuda.synchronize()
+    base = torch.cuda.memory_allocated()
+    torch.cuda.reset_peak_memory_stats()
+    step()
+    torch.cuda.synchronize()
+    return (torch.cuda.max_memory_allocated() - base) / 1e6
+
+
+def train(args, dev):
+    """Forward + backward through both paths, per FREEZE_AT."""
+    import locov_amd
+    N = args.images
+    rec = {"device": torch.cuda.get_device_name(dev), "images": N, "input": [N, 3, H, W], "train": {}}
+    for freeze_at in args.freeze_at:
+        torch.manual_seed(0)
+        cfg = locov_amd.config.get_cfg()
+        cfg.MODEL.BACKBONE.FREEZE_AT = freeze_at
+        cfg.MODEL.BACKBONE.TRAIN_ON_DEVICE = True
+        model = locov_amd.build_backbone(cfg).to(dev)
+        x = torch.randn(N, 3, H, W, device=dev)
+        G = torch.randn(N, 1024, (H + 15) // 16, (W + 15) // 16, device=dev)
+
+        def step(on_device):
+            model.train_on_device = on_device
+            assert model.train_path_ok(x) == on_device and not model.device_path_ok(x)
+            model.zero_grad(set_to_none=True)
+            model(x)["res4"].backward(G)
+
+        sides = {"device": lambda: step(True), "torch": lambda: step(False)}
+        grads = {}
+        for name, side in sides.items():
+            side()
+            grads[name] = {k: p.grad.clone() for k, p in model.named_parameters() if p.grad is not None}
+        assert set(grads["device"]) == set(grads["torch"]) and grads["device"]
+        diff = {k: float((grads["device"][k] - g).abs().max() / g.abs().max().clamp_min(1e-30)) for k, g in grads["torch"].items()}
+        worst = max(diff, key=diff.get)
+        del grads
+        r = {"trained_tensors": len(diff), "max_rel_grad_diff": diff[worst], "max_rel_grad_diff_at": worst}
+        r["kernels"] = {k: kernels(s) for k, s in sides.items()}
+        r["peak_mb"] = {k: peak_mb(s) for k, s in sides.items()}
+        r["step"] = alternate(sides, args.iters, args.warmup)
+        r["device_path_not_slower"] = r["step"]["device"]["median_ms"] <= r["step"]["torch"]["median_ms"]
+        rec["train"][f"freeze_at_{freeze_at}"] = r
+        print(json.dumps({f"train freeze_at {freeze_at} images {N}": {k: v for k, v in r.items() if k != "kernels"}}), flush=True)
+        print(json.dumps({"kernels": r["kernels"]}), flush=True)
+        del model, x, G
+        torch.cuda.empty_cache()
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(rec, f, indent=1)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--images", type=int, default=1)
@@ -77,10 +138,18 @@ def main(argv=None):
     ap.add_argument("--peak-tbs", type=float, default=8.0, help="HBM rate the traffic floor is quoted at, TB/s")
     ap.add_argument("--peak-tflops", type=float, default=157.3, help="fp32 rate the arithmetic floor is quoted at, TFLOP/s")
     ap.add_argument("--stem-only", action="store_true", help="time the stem launch alone (LOCOV_STEM_BAND=<rows> forces its band height)")
+    ap.add_argument("--train", action="store_true", help="time forward + backward of the device training path against the torch path")
+    ap.add_argument("--freeze-at", type=int, nargs="+", default=[0, 2], help="--train: the MODEL.BACKBONE.FREEZE_AT settings timed")
     ap.add_argument("--out", default=None, help="also write the record as JSON here")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("time_backbone: needs a ROCm GPU")
+    if args.train:
+        if args.iters < 30 or args.warmup < 10:
+            raise SystemExit("time_backbone --train: >= 10 warm-up and >= 30 timed iterations")
+        dev = torch.device("cuda:0")
+        torch.cuda.set_device(dev)
+        return train(args, dev)
     if args.iters < 50 or args.warmup < 10:
         raise SystemExit("time_backbone: the protocol asks for >= 10 warm-up and >= 50 timed iterations")
     import locov_amd
