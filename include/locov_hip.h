@@ -37,7 +37,8 @@ extern "C" {
  *    locov_detect_postprocess_cs / _wide_cs (+ _workspace_bytes), locov_grounding_align_fwd / _bwd,
  *    locov_grounding_triplet_fwd / _bwd, locov_mha_fwd / _bwd, locov_rpn_proposals (+ _workspace_bytes),
  *    locov_rpn_label_anchors (+ _workspace_bytes), locov_rpn_sample_anchors, locov_rpn_loss (+ _workspace_bytes),
- *    locov_resnet_stem_fwd, locov_resnet_stem_fwd_sel, locov_resnet_stem_wgrad (+ _workspace_bytes) */
+ *    locov_resnet_stem_fwd, locov_resnet_stem_fwd_sel, locov_resnet_stem_wgrad (+ _workspace_bytes),
+ *    locov_preprocess_images, locov_detector_rescale */
 #define LOCOV_ABI_VERSION 8
 
 #define LOCOV_OK 0
@@ -1295,6 +1296,44 @@ int locov_resnet_stem_fwd_sel(const float *x, int N, int H, int W, const float *
 int64_t locov_resnet_stem_wgrad_workspace_bytes(int N, int H, int W);
 int locov_resnet_stem_wgrad(const float *x, int N, int H, int W, const float *g, const uint8_t *sel, const float *scale, int Cout,
                             float *dw, void *workspace, int64_t workspace_bytes, locov_stream_t stream);
+
+/* ---- the two ends of the detector call, one launch each for the whole batch (csrc/image_batch.hip) ---------------------------
+ * Added under ABI version 8.  What the meta-architecture does around backbone -> RPN -> ROI heads (ovr/modeling/meta_arch/
+ * ovr_rcnn.py:45,101,122; [D2-upstream] GeneralizedRCNN.preprocess_image / _postprocess, detector_postprocess).
+ *
+ * locov_preprocess_images: out[n, c, y, x] = (float(image_n[c, y, x]) - mean[c]) / std[c] inside image n, pad_value outside it.
+ *   images_host : host array of n_images DEVICE pointers; image n is [channels, heights_host[n], widths_host[n]], contiguous, of
+ *                 element type `dtype` (LOCOV_IMAGE_U8 or LOCOV_IMAGE_F32, one type per call), aligned to its element size only.
+ *   mean_host, std_host : host arrays of `channels` (1 .. LOCOV_IMAGE_MAX_CHANNELS) floats.
+ *   out         : fp32 [n_images, channels, Hb, Wb], 16-byte aligned.  EVERY element is written (the padding too): the caller
+ *                 need not clear it.  Hb * Wb < 2^31.
+ *   The subtraction and the division are two separately rounded fp32 operations, the division IEEE-correct: the bits of the CPU
+ *   torch expression (x - pixel_mean) / pixel_std followed by ImageList.from_tensors' padding (applied AFTER the normalisation).
+ *   Every table travels as a kernel argument: one launch, no copy, no workspace, nothing read by the host.
+ *   n_images == 0: LOCOV_OK, nothing is written.  More than LOCOV_LABEL_MAX_IMAGES images, a null pointer, an unknown dtype,
+ *   channels outside 1 .. 4, an image larger than Hb x Wb, a misaligned out: LOCOV_ERR_INVALID_ARG before any HIP call.
+ *
+ * locov_detector_rescale: detector_postprocess' box part for the results of a batch: Boxes.scale, Boxes.clip, Boxes.nonempty.
+ *   boxes       : fp32 [T, 4] XYXY, the images' results concatenated; image i owns rows [roff_host[i], roff_host[i + 1]).
+ *   scale_x_host, scale_y_host : per image, the fp32 factors (output size / image size, formed by the caller).
+ *   out_h_host, out_w_host     : per image, the output size the boxes are clipped to.
+ *   out_boxes   : fp32 [T, 4] (not `boxes`).  Per row x * scale_x, y * scale_y (one fp32 product each), clamped to [0, out_w] /
+ *                 [0, out_h] as torch.clamp does (NaN stays NaN); a row is kept iff (x2 - x1 > 0) & (y2 - y1 > 0).  The kept rows
+ *                 of image i stand at the front of its segment, in their original order; the rest of the segment is zero.
+ *   src         : int64 [T]: for a kept row, the row WITHIN its image it came from; -1 behind the image's count.
+ *   counts      : int32 [n_images], device: the number of kept rows per image (the caller's one host read).
+ *   One launch, one workgroup per image, any number of rows per image; vector stores only.  Two calls give the same bits.
+ *   n_images == 0: LOCOV_OK.  More than LOCOV_LABEL_MAX_IMAGES images, a null pointer, a decreasing roff, misaligned boxes:
+ *   LOCOV_ERR_INVALID_ARG before any HIP call.  (With T == 0 only `counts` is touched; boxes / out_boxes / src may be null.) */
+#define LOCOV_IMAGE_U8 0
+#define LOCOV_IMAGE_F32 1
+#define LOCOV_IMAGE_MAX_CHANNELS 4
+int locov_preprocess_images(const void *const *images_host, const int *heights_host, const int *widths_host, int n_images, int dtype,
+                            int channels, const float *mean_host, const float *std_host, float pad_value, float *out, int Hb, int Wb,
+                            locov_stream_t stream);
+int locov_detector_rescale(const float *boxes, const int *roff_host, const float *scale_x_host, const float *scale_y_host,
+                           const int *out_h_host, const int *out_w_host, int n_images, float *out_boxes, int64_t *src, int *counts,
+                           locov_stream_t stream);
 
 #ifdef __cplusplus
 }

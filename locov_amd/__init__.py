@@ -13,3 +13,5 @@ from .roi_heads import (EmbeddingFastRCNNOutputLayers, EmbeddingProposalsRes5ROI
                         EmbeddingRes5ROIHeads, build_box_predictor, build_roi_heads)
 from .proposal_generator import RPN, DefaultAnchorGenerator, StandardRPNHead, build_proposal_generator  # noqa: F401
 from .backbone import BasicStem, ResNet, build_backbone, build_resnet_backbone  # noqa: F401
+from . import meta_arch  # noqa: F401,E402
+from .meta_arch import META_ARCH_REGISTRY, GeneralizedRCNN, OvrRCNN, build_model, detector_postprocess  # noqa: F401

@@ -38,6 +38,7 @@ BOX_IOU_GIOU, BOX_IOU_DIOU, BOX_IOU_CIOU = 0, 1, 2
 REGIONS_MAX_B, REGIONS_MAX_CANDIDATES = 64, 4096
 REGIONS_GRID, REGIONS_GRID_ALL, REGIONS_BOXES = 0, 1, 2
 REGIONS_ROWS, REGIONS_NCHW = 0, 1
+IMAGE_U8, IMAGE_F32, IMAGE_MAX_CHANNELS = 0, 1, 4
 MHA_MAX_S, MHA_MAX_GRID, MHA_HEAD_DIMS = 4096, 65535, (32, 64, 96, 128)
 
 _p = c_void_p  # device pointer
@@ -219,6 +220,10 @@ SIGNATURES = {
     "locov_resnet_stem_fwd_sel": (c_int, [_p, c_int, c_int, c_int, _p, _p, _p, c_int, _p, _p, _p]),
     "locov_resnet_stem_wgrad_workspace_bytes": (c_int64, [c_int, c_int, c_int]),
     "locov_resnet_stem_wgrad": (c_int, [_p, c_int, c_int, c_int, _p, _p, _p, c_int, _p, _p, c_int64, _p]),
+    "locov_preprocess_images": (c_int, [POINTER(c_void_p), POINTER(c_int), POINTER(c_int), c_int, c_int, c_int, POINTER(c_float),
+                                        POINTER(c_float), c_float, _p, c_int, c_int, _p]),
+    "locov_detector_rescale": (c_int, [_p, POINTER(c_int), POINTER(c_float), POINTER(c_float), POINTER(c_int), POINTER(c_int), c_int,
+                                       _p, _p, _p, _p]),
 }
 
 _lib = None

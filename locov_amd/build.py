@@ -40,7 +40,8 @@ FILE_FLAGS = {
     "rpn.hip": ["-ffp-contract=off"],            # (the same decoding and IoU, through detect_common.h)
     "rpn_train.hip": ["-ffp-contract=off"],      # (the IoU of label.hip, the box deltas of losses.hip: the same roundings)
     "mha.hip": ["-ffp-contract=off"],            # (dP - delta must cancel exactly where one key holds a row: no fused dP * keep - delta)
-    "nms.hip": ["-ffp-contract=off"],            # (select_common.h's box_iou_gt, rounded as in detect.hip / rpn.hip: the bit-identity tests)
+    "image_batch.hip": ["-ffp-contract=off"],    # ((x - mean) / std and box * scale as the torch ops round them: the bit-identity tests)
+    "nms.hip": ["-ffp-contract=off"],          # (select_common.h's box_iou_gt, rounded as in detect.hip / rpn.hip: the bit-identity tests)
 }
 
 

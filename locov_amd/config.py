@@ -75,6 +75,9 @@ def get_cfg() -> CfgNode:
     return CfgNode({
         "MODEL": {
             "DEVICE": "cuda",
+            "META_ARCHITECTURE": "GeneralizedRCNN",                # [D2-upstream]; coco_stt.yaml -> "OvrRCNN" (meta_arch.py)
+            "PIXEL_MEAN": [103.530, 116.280, 123.675],             # [D2-upstream] (BGR)
+            "PIXEL_STD": [1.0, 1.0, 1.0],                          # [D2-upstream]
             "MASK_ON": False,
             "KEYPOINT_ON": False,
             "LOAD_EMB_PRED_FROM_MMSS_HEAD": False,                # config.py:13
@@ -184,6 +187,8 @@ def get_cfg() -> CfgNode:
                 "DEPTH": 50, "OUT_FEATURES": ["res4"], "STEM_OUT_CHANNELS": 64, "RES5_DILATION": 1,     # [D2-upstream] (backbone.py)
             },
         },
+        "INPUT": {"FORMAT": "BGR"},                                # [D2-upstream]
+        "VIS_PERIOD": 0,                                           # [D2-upstream]; > 0 is refused (meta_arch.py)
         "TEST": {"DETECTIONS_PER_IMAGE": 100},                     # [D2-upstream]
         "DATASETS": {"TRAIN": ()},                                 # [D2-upstream] (USE_FED_LOSS: whose class_image_count to read)
     })

@@ -2764,3 +2764,73 @@ def mha_packed(qkv: torch.Tensor, key_bias: torch.Tensor, num_heads: int, *, sca
     H = int(num_heads)
     scale = 1.0 / math.sqrt(qkv.shape[1] // (3 * H)) if scale is None else float(scale)
     return _MhaFn.apply(qkv, None, None, key_bias, keep, H, scale, float(p_drop), True)
+
+
+# --------------------------------------------------------------------------------------
+# The two ends of the detector call (csrc/image_batch.hip; meta_arch.py: preprocess_image / _postprocess)
+IMAGE_BATCH_MAX_IMAGES, IMAGE_BATCH_MAX_CHANNELS = _lib.LABEL_MAX_IMAGES, _lib.IMAGE_MAX_CHANNELS
+
+
+def preprocess_images(images: Sequence[torch.Tensor], mean: Sequence[float], std: Sequence[float], size_divisibility: int = 0,
+                      pad_value: float = 0.0, padding_constraints: Optional[dict] = None, out: Optional[torch.Tensor] = None):
+    """(x - mean[c]) / std[c] of N [C, h_i, w_i] device images (all uint8 or all fp32) padded with pad_value into ONE fp32
+    [N, C, Hb, Wb] batch, in one launch (locov_preprocess_images): the bits of the CPU torch expression followed by
+    ImageList.from_tensors, whose batch-shape rule (largest sizes, square_size, rounded up to size_divisibility) this follows.
+    Returns (tensor, image_sizes).  out: the caller's [N, C, Hb, Wb] tensor instead of a fresh one; every element of it is written.
+    No H2D copy, no workspace, nothing read by the host."""
+    from .structures import padded_batch_size
+    images = list(images)
+    if not images:
+        raise ValueError("preprocess_images: no image")
+    ims = [_dev(t, f"images[{i}]", dtype=None) for i, t in enumerate(images)]
+    dt, C = ims[0].dtype, ims[0].shape[0] if ims[0].dim() == 3 else -1
+    if dt not in (torch.uint8, torch.float32) or any(t.dtype != dt for t in ims):
+        raise TypeError("preprocess_images: the images must all be uint8 or all be fp32")
+    if any(t.dim() != 3 or t.shape[0] != C or t.device != ims[0].device for t in ims):
+        raise ValueError("preprocess_images: the images must be [C, H, W] with one channel count, on one device")
+    mean, std = [float(v) for v in mean], [float(v) for v in std]
+    if not (1 <= C <= IMAGE_BATCH_MAX_CHANNELS) or len(mean) != C or len(std) != C or len(ims) > IMAGE_BATCH_MAX_IMAGES:
+        raise ValueError(f"preprocess_images: outside the kernel's limits (1..{IMAGE_BATCH_MAX_CHANNELS} channels with one mean and "
+                         f"std each, at most {IMAGE_BATCH_MAX_IMAGES} images)")
+    image_sizes = [(int(t.shape[-2]), int(t.shape[-1])) for t in ims]
+    Hb, Wb = padded_batch_size(image_sizes, size_divisibility, padding_constraints)
+    n = len(ims)
+    out = _out(out, (n, C, Hb, Wb), ims[0], "preprocess_images")
+    ptrs = (ctypes.c_void_p * n)(*[t.data_ptr() for t in ims])
+    hs, ws = (ctypes.c_int * n)(*[s[0] for s in image_sizes]), (ctypes.c_int * n)(*[s[1] for s in image_sizes])
+    with torch.cuda.device(out.device):
+        check(_lib.load().locov_preprocess_images(ptrs, hs, ws, n, _lib.IMAGE_U8 if dt == torch.uint8 else _lib.IMAGE_F32, C,
+                                                  (ctypes.c_float * C)(*mean), (ctypes.c_float * C)(*std), float(pad_value),
+                                                  _ptr(out), Hb, Wb, _stream(out)), "locov_preprocess_images")
+    return out, image_sizes
+
+
+def detector_rescale(boxes: torch.Tensor, sizes: Sequence[int], image_sizes, output_sizes):
+    """detector_postprocess' box part for a batch in one launch (locov_detector_rescale) and ONE host read (the N counts).
+    boxes [T, 4] fp32: the images' results concatenated, sizes[i] rows of image i predicted at image_sizes[i] = (h, w) and wanted
+    at output_sizes[i] = (height, width).  Returns (out_boxes [T, 4], src int64 [T], counts): image i's kept boxes -- scaled by
+    fp32(width / w), fp32(height / h) as `tensor *= python_float` scales, clipped, non-empty -- are the first counts[i] rows of its
+    segment in their original order, src the row within the image each came from; the rest of the segment is 0 / -1."""
+    boxes = _dev(boxes, "boxes")
+    sizes = [int(s) for s in sizes]
+    n = len(sizes)
+    if boxes.dim() != 2 or boxes.shape[1] != 4 or sum(sizes) != boxes.shape[0] or min(sizes, default=0) < 0:
+        raise ValueError("detector_rescale: boxes must be [sum(sizes), 4]")
+    if not (len(image_sizes) == len(output_sizes) == n) or n > IMAGE_BATCH_MAX_IMAGES:
+        raise ValueError(f"detector_rescale: one image size and one output size per image, at most {IMAGE_BATCH_MAX_IMAGES} images")
+    T = boxes.shape[0]
+    out = torch.empty((T, 4), dtype=torch.float32, device=boxes.device)
+    src = torch.empty((T,), dtype=torch.int64, device=boxes.device)
+    if n == 0:
+        return out, src, []
+    if boxes.data_ptr() % 16:
+        boxes = boxes.clone()
+    counts = torch.empty((n,), dtype=torch.int32, device=boxes.device)
+    roff = (ctypes.c_int * (n + 1))(0, *itertools.accumulate(sizes))
+    sx = (ctypes.c_float * n)(*[float(o[1]) / float(s[1]) for o, s in zip(output_sizes, image_sizes)])    # (double, then ONE rounding)
+    sy = (ctypes.c_float * n)(*[float(o[0]) / float(s[0]) for o, s in zip(output_sizes, image_sizes)])
+    oh, ow = (ctypes.c_int * n)(*[int(o[0]) for o in output_sizes]), (ctypes.c_int * n)(*[int(o[1]) for o in output_sizes])
+    with torch.cuda.device(boxes.device):
+        check(_lib.load().locov_detector_rescale(_ptr(boxes), roff, sx, sy, oh, ow, n, _ptr(out), _ptr(src), _ptr(counts), _stream(boxes)),
+              "locov_detector_rescale")
+    return out, src, counts.tolist()

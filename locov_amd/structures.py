@@ -201,6 +201,23 @@ class Instances:
         return s
 
 
+def padded_batch_size(image_sizes: Sequence[Tuple[int, int]], size_divisibility: int = 0, padding_constraints=None) -> Tuple[int, int]:
+    """[D2-upstream] the (Hb, Wb) ImageList.from_tensors pads a batch to: the largest height and width; both replaced by
+    padding_constraints["square_size"] when that is > 0; then rounded up to a multiple of the divisibility when that is > 1
+    (padding_constraints["size_divisibility"] overrides the argument)."""
+    hb, wb = max(s[0] for s in image_sizes), max(s[1] for s in image_sizes)
+    if padding_constraints is not None:
+        square_size = padding_constraints.get("square_size", 0)
+        if square_size > 0:
+            hb = wb = int(square_size)
+        if "size_divisibility" in padding_constraints:
+            size_divisibility = padding_constraints["size_divisibility"]
+    if size_divisibility > 1:
+        d = int(size_divisibility)
+        hb, wb = (hb + d - 1) // d * d, (wb + d - 1) // d * d
+    return int(hb), int(wb)
+
+
 class ImageList:
     """Batched image tensor + per-image (h, w); the ROI heads only `del` it
     (roi_emb_heads.py:251,315) but callers construct one."""
@@ -211,6 +228,29 @@ class ImageList:
 
     def __len__(self) -> int:
         return len(self.image_sizes)
+
+    def __getitem__(self, idx: int) -> torch.Tensor:
+        """Image idx without its padding: a view of the batch."""
+        h, w = self.image_sizes[idx]
+        return self.tensor[idx, ..., :h, :w]
+
+    @staticmethod
+    def from_tensors(tensors: Sequence[torch.Tensor], size_divisibility: int = 0, pad_value: float = 0.0,
+                     padding_constraints=None) -> "ImageList":
+        """[D2-upstream] ImageList.from_tensors: (..., h_i, w_i) tensors of one dtype and one leading shape, each placed in the
+        top-left corner of a pad_value-filled [N, ..., Hb, Wb] batch (padded_batch_size).  Plain torch ops, on any device: the
+        definition of what ops.preprocess_images computes on the device, and the meta-architecture's fallback."""
+        tensors = list(tensors)
+        assert len(tensors) > 0
+        for t in tensors:
+            assert isinstance(t, torch.Tensor), type(t)
+            assert t.shape[:-2] == tensors[0].shape[:-2], t.shape
+        image_sizes = [(int(t.shape[-2]), int(t.shape[-1])) for t in tensors]
+        hb, wb = padded_batch_size(image_sizes, size_divisibility, padding_constraints)
+        batched = tensors[0].new_full((len(tensors),) + tuple(tensors[0].shape[:-2]) + (hb, wb), pad_value)
+        for t, out, (h, w) in zip(tensors, batched, image_sizes):
+            out[..., :h, :w].copy_(t)
+        return ImageList(batched.contiguous(), image_sizes)
 
     @property
     def device(self):
