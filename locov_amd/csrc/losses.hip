@@ -97,173 +97,177 @@ __global__ __launch_bounds__(kLossThreads) void box_reg_loss_kernel(const float4
     if (threadIdx.x == 0) loss[0] = total / n;
 }
 
-// out[tag * 4 + k], tag 0 = cost0 ("Words": w2r), 1 = cost1 ("Regions": r2w); k: 0 = CE choose caption (softmax over dim 0),
-// 1 = CE choose image (dim 1), 2 / 3 = the batch accuracies of the same two directions.  GRAD: d(sum_k up[tag*2+k] * CE_k) / d cost.
-// DIST (the head also returns its distributions): the forward writes the filled costs pw0 / pw1, the backward adds their upstream
-// gradients gpw0 / gpw1 (either may be null) on the ok pairs.
-template <bool GRAD, bool DIST>
-__device__ __forceinline__ void grounding_ce_body(const float *__restrict__ cost0, const float *__restrict__ cost1,
-                                                  const float *__restrict__ cmask, const float *__restrict__ rmask, int B, int T, int NR,
-                                                  float *__restrict__ out, const float *up0, const float *up1, const float *up2,
-                                                  const float *up3, float *__restrict__ d0, float *__restrict__ d1,
-                                                  float *__restrict__ pw0, float *__restrict__ pw1, const float *__restrict__ gpw0,
-                                                  const float *__restrict__ gpw1)
+// ---- the grounding tail (locov_grounding_ce[_dist]_fwd / _bwd, locov_grounding_triplet_fwd / _bwd) ----
+// Everything on the two [B, B] cost matrices after the alignment launch, one workgroup.  tag 0 = cost[0] ("Words": w2r), 1 = cost[1]
+// ("Regions": r2w); an alignment that is off has a null cost.  Forward: out[tag * 4 + k], k: 0 = the loss choosing the caption (over
+// dim 0), 1 = choosing the image (dim 1), 2 / 3 = the batch accuracies of the same two directions; pw[tag], where non-null (the head
+// also returns its distributions), receives the filled cost.  Backward: d[tag] = d(sum_k up[tag * 2 + k] * loss_k) / d cost, plus
+// gpw[tag] (pw's upstream gradient) where non-null, on the pairs that are not filled; a null up reads as 0.  mining, margin and
+// neg_idx belong to the triplet loss alone.
+struct TailArgs {
+    const float *cost[2], *cmask, *rmask;
+    int B, T, NR, mining;
+    float margin;
+    const int64_t *neg_idx;
+    float *out, *pw[2];
+    const float *up[4], *gpw[2];
+    float *d[2];
+};
+
+namespace {
+
+constexpr int kTailMaxB = LOCOV_GROUNDING_CE_MAX_B;
+
+// nw[i] / nr[i]: the words of caption i / the regions of image i
+__device__ __forceinline__ void tail_mask_counts(const TailArgs &a, float *nw, float *nr)
 {
-    __shared__ float red[kLossThreads];
-    __shared__ float z[LOCOV_GROUNDING_CE_MAX_B * LOCOV_GROUNDING_CE_MAX_B];       // -cost' of the current tag
-    __shared__ float nw[LOCOV_GROUNDING_CE_MAX_B], nr[LOCOV_GROUNDING_CE_MAX_B];
-    __shared__ float cmx[LOCOV_GROUNDING_CE_MAX_B], cls_[LOCOV_GROUNDING_CE_MAX_B]; // per column: max, log-sum-exp term (softmax over dim 0)
-    __shared__ float rmx[LOCOV_GROUNDING_CE_MAX_B], rls_[LOCOV_GROUNDING_CE_MAX_B]; // per row (softmax over dim 1)
-    const int t = threadIdx.x, BB = B * B;
-    for (int i = t; i < B; i += kLossThreads) {
-        float a = 0.f, b = 0.f;
-        for (int k = 0; k < T; k++) a = a + cmask[i * T + k];
-        for (int k = 0; k < NR; k++) b = b + rmask[i * NR + k];
-        nw[i] = a;
-        nr[i] = b;
+    for (int i = threadIdx.x; i < a.B; i += kLossThreads) {
+        float w = 0.f, r = 0.f;
+        for (int k = 0; k < a.T; k++) w = w + a.cmask[i * a.T + k];
+        for (int k = 0; k < a.NR; k++) r = r + a.rmask[i * a.NR + k];
+        nw[i] = w;
+        nr[i] = r;
     }
     __syncthreads();
+}
+
+// pair e = (caption i, image j) keeps its cost unless it has neither words nor regions
+__device__ __forceinline__ bool tail_ok(const float *nw, const float *nr, int B, int e)
+{
+    const int i = e / B, j = e - i * B;
+    return nw[i] > 0.f || nr[j] > 0.f;
+}
+
+// cf = the cost with the pairs that are not ok replaced by max + 100 (:239-251), also written to pw when that is non-null
+__device__ __forceinline__ void tail_fill(const float *cost, int B, const float *nw, const float *nr, float *red, float *cf, float *pw)
+{
+    const int t = threadIdx.x, BB = B * B;
+    float m = -INFINITY;
+    for (int e = t; e < BB; e += kLossThreads) m = fmaxf(m, cost[e]);
+    const float fill = block_max(m, red) + 100.0f;
+    for (int e = t; e < BB; e += kLossThreads) {
+        const float c = tail_ok(nw, nr, B, e) ? cost[e] : fill;
+        cf[e] = c;
+        if (pw) pw[e] = c;
+    }
+    __syncthreads();
+}
+
+// an alignment that is off: its four outputs are zeros
+__device__ __forceinline__ void tail_absent(float *out, int tag)
+{
+    if (threadIdx.x < 4) out[tag * 4 + threadIdx.x] = 0.f;
+}
+
+// the batch accuracies' terms of column k (choose caption) and row k (choose image): is the argmin, first index on ties, k itself
+__device__ __forceinline__ void tail_accuracy(const float *cf, int B, int k, float &ac, float &ai)
+{
+    int bc = 0, bi = 0;
+    for (int v = 1; v < B; v++) {
+        if (cf[v * B + k] < cf[bc * B + k]) bc = v;
+        if (cf[k * B + v] < cf[k * B + bi]) bi = v;
+    }
+    ac = bc == k ? 1.f : 0.f;
+    ai = bi == k ? 1.f : 0.f;
+}
+
+// out[tag * 4 ..] = the four means over k (B <= kLossThreads: thread k holds the terms of k, every other thread zeros)
+__device__ __forceinline__ void tail_store_means(float *out, int tag, int B, float lc, float li, float ac, float ai, float *red)
+{
+    const float slc = block_sum(lc, red), sli = block_sum(li, red), sac = block_sum(ac, red), sai = block_sum(ai, red);
+    if (threadIdx.x == 0) {
+        out[tag * 4 + 0] = slc / (float)B;
+        out[tag * 4 + 1] = sli / (float)B;
+        out[tag * 4 + 2] = sac / (float)B;
+        out[tag * 4 + 3] = sai / (float)B;
+    }
+}
+
+// what one loss term's mean passes down to each of its B terms
+__device__ __forceinline__ float tail_upstream(const float *up, int B) { return (up ? up[0] : 0.f) / (float)B; }
+
+// d[e] for the loss's own dc: pw's gradient joins it, and the replaced pairs are constants
+__device__ __forceinline__ void tail_store_grad(float *d, const float *gp, int e, bool ok, float dc)
+{
+    if (gp) dc = dc + gp[e];
+    d[e] = ok ? dc : 0.f;
+}
+
+// The cross-entropy tail (grounding_head.py:273-290): log_softmax of z = -cost' over captions and over images, the diagonal means.
+template <bool GRAD>
+__device__ __forceinline__ void grounding_ce_body(const TailArgs &a)
+{
+    __shared__ float red[kLossThreads];
+    __shared__ float cf[kTailMaxB * kTailMaxB];               // the filled cost of the current tag
+    __shared__ float nw[kTailMaxB], nr[kTailMaxB];
+    __shared__ float cmx[kTailMaxB], cls_[kTailMaxB];         // per column: max, log-sum-exp term (softmax over dim 0)
+    __shared__ float rmx[kTailMaxB], rls_[kTailMaxB];         // per row (softmax over dim 1)
+    const int t = threadIdx.x, B = a.B, BB = B * B;
+    tail_mask_counts(a, nw, nr);
     for (int tag = 0; tag < 2; tag++) {
-        const float *cost = tag ? cost1 : cost0;
-        if (!cost) {                                          // (workgroup-uniform)
-            if (DIST && !GRAD && t < 4) out[tag * 4 + t] = 0.f;   // (the plain entry's caller zero-fills out8 itself)
+        if (!a.cost[tag]) {                                   // (workgroup-uniform)
+            if (!GRAD) tail_absent(a.out, tag);
             continue;
         }
-        float m = -INFINITY;
-        for (int e = t; e < BB; e += kLossThreads) m = fmaxf(m, cost[e]);
-        const float fill = block_max(m, red) + 100.0f;       // pairs with neither words nor regions: max + 100 (:239-251)
-        for (int e = t; e < BB; e += kLossThreads) {
-            const int i = e / B, j = e - i * B;
-            const bool ok = nw[i] > 0.f || nr[j] > 0.f;
-            const float c = ok ? cost[e] : fill;
-            z[e] = -c;
-            if (DIST && !GRAD) (tag ? pw1 : pw0)[e] = c;
-        }
-        __syncthreads();
+        tail_fill(a.cost[tag], B, nw, nr, red, cf, a.pw[tag]);
         // log_softmax's pieces: x - max - log(sum exp(x - max)), per column (dim 0) and per row (dim 1)
         for (int u = t; u < 2 * B; u += kLossThreads) {
             const bool col = u < B;
             const int k = col ? u : u - B;
             float mx = -INFINITY;
-            for (int v = 0; v < B; v++) mx = fmaxf(mx, col ? z[v * B + k] : z[k * B + v]);
+            for (int v = 0; v < B; v++) mx = fmaxf(mx, -(col ? cf[v * B + k] : cf[k * B + v]));
             float s = 0.f;
-            for (int v = 0; v < B; v++) s = s + expf((col ? z[v * B + k] : z[k * B + v]) - mx);
+            for (int v = 0; v < B; v++) s = s + expf(-(col ? cf[v * B + k] : cf[k * B + v]) - mx);
             (col ? cmx : rmx)[k] = mx;
             (col ? cls_ : rls_)[k] = logf(s);
         }
         __syncthreads();
         if (!GRAD) {
             float lc = 0.f, li = 0.f, ac = 0.f, ai = 0.f;
-            for (int k = t; k < B; k += kLossThreads) {
-                const float zkk = z[k * B + k];
-                lc = -((zkk - cmx[k]) - cls_[k]);
-                li = -((zkk - rmx[k]) - rls_[k]);
-                // argmin of cost' = argmax of z, first index on ties
-                int bc = 0, bi = 0;
-                for (int v = 1; v < B; v++) {
-                    if (z[v * B + k] > z[bc * B + k]) bc = v;
-                    if (z[k * B + v] > z[k * B + bi]) bi = v;
-                }
-                ac = bc == k ? 1.f : 0.f;
-                ai = bi == k ? 1.f : 0.f;
+            if (t < B) {
+                const float zkk = -cf[t * B + t];
+                lc = -((zkk - cmx[t]) - cls_[t]);
+                li = -((zkk - rmx[t]) - rls_[t]);
+                tail_accuracy(cf, B, t, ac, ai);
             }
-            // (B <= kLossThreads: one diagonal element per thread, so the four partials above are that element's values)
-            const float slc = block_sum(lc, red), sli = block_sum(li, red), sac = block_sum(ac, red), sai = block_sum(ai, red);
-            if (t == 0) {
-                out[tag * 4 + 0] = slc / (float)B;
-                out[tag * 4 + 1] = sli / (float)B;
-                out[tag * 4 + 2] = sac / (float)B;
-                out[tag * 4 + 3] = sai / (float)B;
-            }
+            tail_store_means(a.out, tag, B, lc, li, ac, ai, red);
         } else {
-            const float *pc = tag ? up2 : up0, *pi = tag ? up3 : up1;
-            const float gc = (pc ? pc[0] : 0.f) / (float)B, gi = (pi ? pi[0] : 0.f) / (float)B;
-            float *d = tag ? d1 : d0;
+            const float gc = tail_upstream(a.up[tag * 2], B), gi = tail_upstream(a.up[tag * 2 + 1], B);
             for (int e = t; e < BB; e += kLossThreads) {
                 const int i = e / B, j = e - i * B;
-                const bool ok = nw[i] > 0.f || nr[j] > 0.f;
-                const float pcol = expf((z[e] - cmx[j]) - cls_[j]), prow = expf((z[e] - rmx[i]) - rls_[i]);
+                const float z = -cf[e];
+                const float pcol = expf((z - cmx[j]) - cls_[j]), prow = expf((z - rmx[i]) - rls_[i]);
                 const float dz = gc * (pcol - (i == j ? 1.f : 0.f)) + gi * (prow - (i == j ? 1.f : 0.f));
-                float dc = -dz;                               // z = -cost'; the replaced pairs are constants
-                if (DIST) {
-                    const float *gp = tag ? gpw1 : gpw0;
-                    if (gp) dc = dc + gp[e];
-                }
-                d[e] = ok ? dc : 0.f;
+                tail_store_grad(a.d[tag], a.gpw[tag], e, tail_ok(nw, nr, B, e), -dz);      // z = -cost'
             }
         }
         __syncthreads();
     }
 }
 
+// The triplet tail (grounding_head.py:279-343): positive = the diagonal; the negative of column j ("choose caption") / row i ("choose
+// image") is the off-diagonal minimum (hardest), maximum (easiest) or the entry a given index names in the matrix without its
+// diagonal (reduced index k -> k below the diagonal position, k + 1 from it on: what gather on remove_diag picks; an index outside
+// [0, B - 1) is clamped into it, never followed out of the matrix).  The loss terms are mean(relu(positive - negative + margin)).
+// B < 2: negative = positive + margin, no gradient.  GRAD: the hinge's gradient on the diagonal entry and on the selected negative.
 template <bool GRAD>
-__global__ __launch_bounds__(kLossThreads) void grounding_ce_kernel(const float *__restrict__ cost0, const float *__restrict__ cost1,
-                                                                    const float *__restrict__ cmask, const float *__restrict__ rmask, int B,
-                                                                    int T, int NR, float *__restrict__ out, const float *up0,
-                                                                    const float *up1, const float *up2, const float *up3,
-                                                                    float *__restrict__ d0, float *__restrict__ d1)
-{
-    grounding_ce_body<GRAD, false>(cost0, cost1, cmask, rmask, B, T, NR, out, up0, up1, up2, up3, d0, d1, nullptr, nullptr, nullptr,
-                                   nullptr);
-}
-
-template <bool GRAD>
-__global__ __launch_bounds__(kLossThreads) void grounding_ce_dist_kernel(const float *__restrict__ cost0, const float *__restrict__ cost1,
-                                                                         const float *__restrict__ cmask, const float *__restrict__ rmask,
-                                                                         int B, int T, int NR, float *__restrict__ out, const float *up0,
-                                                                         const float *up1, const float *up2, const float *up3,
-                                                                         float *__restrict__ d0, float *__restrict__ d1,
-                                                                         float *__restrict__ pw0, float *__restrict__ pw1,
-                                                                         const float *__restrict__ gpw0, const float *__restrict__ gpw1)
-{
-    grounding_ce_body<GRAD, true>(cost0, cost1, cmask, rmask, B, T, NR, out, up0, up1, up2, up3, d0, d1, pw0, pw1, gpw0, gpw1);
-}
-
-
-// The triplet tail (grounding_head.py:279-343) on the same [B, B] costs, one workgroup: positive = the diagonal; the negative of
-// column j ("choose caption") / row i ("choose image") is the off-diagonal minimum (hardest), maximum (easiest) or the entry a given
-// index names in the matrix without its diagonal (reduced index k -> k below the diagonal position, k + 1 from it on: what gather on
-// remove_diag picks; an index outside [0, B - 1) is clamped into it, never followed out of the matrix).  out as grounding_ce_body's,
-// the two CE values replaced by mean(relu(positive - negative + margin)).  B < 2: negative = positive + margin, no gradient.
-// GRAD: the hinge's gradient on the diagonal entry and on the selected negative, plus gpw on the pairs that are not filled.
-template <bool GRAD>
-__global__ __launch_bounds__(kLossThreads) void grounding_triplet_kernel(
-    const float *__restrict__ cost0, const float *__restrict__ cost1, const float *__restrict__ cmask, const float *__restrict__ rmask,
-    int B, int T, int NR, int mining, float margin, const int64_t *__restrict__ neg_idx, float *__restrict__ out,
-    float *__restrict__ pw0, float *__restrict__ pw1, const float *up0, const float *up1, const float *up2, const float *up3,
-    const float *__restrict__ gpw0, const float *__restrict__ gpw1, float *__restrict__ d0, float *__restrict__ d1)
+__device__ __forceinline__ void grounding_triplet_body(const TailArgs &a)
 {
     __shared__ float red[kLossThreads];
-    __shared__ float cf[LOCOV_GROUNDING_CE_MAX_B * LOCOV_GROUNDING_CE_MAX_B];      // the filled cost of the current tag
-    __shared__ float dacc[GRAD ? LOCOV_GROUNDING_CE_MAX_B * LOCOV_GROUNDING_CE_MAX_B : 1];
-    __shared__ float nw[LOCOV_GROUNDING_CE_MAX_B], nr[LOCOV_GROUNDING_CE_MAX_B];
-    const int t = threadIdx.x, BB = B * B;
-    for (int i = t; i < B; i += kLossThreads) {
-        float a = 0.f, b = 0.f;
-        for (int k = 0; k < T; k++) a = a + cmask[i * T + k];
-        for (int k = 0; k < NR; k++) b = b + rmask[i * NR + k];
-        nw[i] = a;
-        nr[i] = b;
-    }
-    __syncthreads();
+    __shared__ float cf[kTailMaxB * kTailMaxB];               // the filled cost of the current tag
+    __shared__ float dacc[GRAD ? kTailMaxB * kTailMaxB : 1];
+    __shared__ float nw[kTailMaxB], nr[kTailMaxB];
+    const int t = threadIdx.x, B = a.B, BB = B * B;
+    const float margin = a.margin;
+    tail_mask_counts(a, nw, nr);
     for (int tag = 0; tag < 2; tag++) {
-        const float *cost = tag ? cost1 : cost0;
-        if (!cost) {                                          // (workgroup-uniform)
-            if (!GRAD && t < 4) out[tag * 4 + t] = 0.f;
+        if (!a.cost[tag]) {                                   // (workgroup-uniform)
+            if (!GRAD) tail_absent(a.out, tag);
             continue;
         }
-        float m = -INFINITY;
-        for (int e = t; e < BB; e += kLossThreads) m = fmaxf(m, cost[e]);
-        const float fill = block_max(m, red) + 100.0f;       // pairs with neither words nor regions: max + 100 (:239-251)
-        for (int e = t; e < BB; e += kLossThreads) {
-            const int i = e / B, j = e - i * B;
-            const float c = (nw[i] > 0.f || nr[j] > 0.f) ? cost[e] : fill;
-            cf[e] = c;
-            if (GRAD) dacc[e] = 0.f;
-            float *pw = tag ? pw1 : pw0;
-            if (!GRAD && pw) pw[e] = c;
-        }
-        __syncthreads();
+        if (GRAD)
+            for (int e = t; e < BB; e += kLossThreads) dacc[e] = 0.f;
+        tail_fill(a.cost[tag], B, nw, nr, red, cf, a.pw[tag]);
         // thread k: column k (choose caption) and row k (choose image)
         const int k = t;
         int nc = -1, ni = -1;                                 // the selected negatives: cf[nc * B + k], cf[k * B + ni]
@@ -273,17 +277,17 @@ __global__ __launch_bounds__(kLossThreads) void grounding_triplet_kernel(
             float negc, negi;
             if (B < 2) {
                 negc = negi = pos + margin;
-            } else if (mining == LOCOV_TRIPLET_GIVEN) {
-                const int64_t *idx = neg_idx + (int64_t)tag * 2 * B;
-                int64_t a = idx[k], b = idx[B + k];
-                a = a < 0 ? 0 : (a > B - 2 ? B - 2 : a);
-                b = b < 0 ? 0 : (b > B - 2 ? B - 2 : b);
-                nc = (int)(a < k ? a : a + 1);
-                ni = (int)(b < k ? b : b + 1);
+            } else if (a.mining == LOCOV_TRIPLET_GIVEN) {
+                const int64_t *idx = a.neg_idx + (int64_t)tag * 2 * B;
+                int64_t p = idx[k], q = idx[B + k];
+                p = p < 0 ? 0 : (p > B - 2 ? B - 2 : p);
+                q = q < 0 ? 0 : (q > B - 2 ? B - 2 : q);
+                nc = (int)(p < k ? p : p + 1);
+                ni = (int)(q < k ? q : q + 1);
                 negc = cf[nc * B + k];
                 negi = cf[k * B + ni];
             } else {
-                const bool easiest = mining == LOCOV_TRIPLET_EASIEST;
+                const bool easiest = a.mining == LOCOV_TRIPLET_EASIEST;
                 for (int v = 0; v < B; v++) {
                     if (v == k) continue;
                     const float xc = cf[v * B + k], xi = cf[k * B + v];
@@ -296,27 +300,12 @@ __global__ __launch_bounds__(kLossThreads) void grounding_triplet_kernel(
             hc = fmaxf((pos - negc) + margin, 0.f);
             hi = fmaxf((pos - negi) + margin, 0.f);
             if (B < 2) nc = ni = -1;
-            if (!GRAD) {
-                int bc = 0, bi = 0;                           // argmin, first index on ties
-                for (int v = 1; v < B; v++) {
-                    if (cf[v * B + k] < cf[bc * B + k]) bc = v;
-                    if (cf[k * B + v] < cf[k * B + bi]) bi = v;
-                }
-                ac = bc == k ? 1.f : 0.f;
-                ai = bi == k ? 1.f : 0.f;
-            }
+            if (!GRAD) tail_accuracy(cf, B, k, ac, ai);
         }
         if (!GRAD) {
-            const float shc = block_sum(hc, red), shi = block_sum(hi, red), sac = block_sum(ac, red), sai = block_sum(ai, red);
-            if (t == 0) {
-                out[tag * 4 + 0] = shc / (float)B;
-                out[tag * 4 + 1] = shi / (float)B;
-                out[tag * 4 + 2] = sac / (float)B;
-                out[tag * 4 + 3] = sai / (float)B;
-            }
+            tail_store_means(a.out, tag, B, hc, hi, ac, ai, red);
         } else {
-            const float *pc = tag ? up2 : up0, *pi = tag ? up3 : up1;
-            const float gc = (pc ? pc[0] : 0.f) / (float)B, gi = (pi ? pi[0] : 0.f) / (float)B;
+            const float gc = tail_upstream(a.up[tag * 2], B), gi = tail_upstream(a.up[tag * 2 + 1], B);
             // column k's two entries belong to thread k alone, row k's likewise; the two passes meet, so a barrier parts them
             if (k < B && nc >= 0 && hc > 0.f) {
                 dacc[k * B + k] += gc;
@@ -328,18 +317,25 @@ __global__ __launch_bounds__(kLossThreads) void grounding_triplet_kernel(
                 dacc[k * B + ni] -= gi;
             }
             __syncthreads();
-            float *d = tag ? d1 : d0;
-            const float *gp = tag ? gpw1 : gpw0;
-            for (int e = t; e < BB; e += kLossThreads) {
-                const int i = e / B, j = e - i * B;
-                float dc = dacc[e];
-                if (gp) dc = dc + gp[e];
-                d[e] = (nw[i] > 0.f || nr[j] > 0.f) ? dc : 0.f;   // the replaced pairs are constants
-            }
+            for (int e = t; e < BB; e += kLossThreads) tail_store_grad(a.d[tag], a.gpw[tag], e, tail_ok(nw, nr, B, e), dacc[e]);
         }
         __syncthreads();
     }
 }
+
+}  // namespace
+
+// The kernels: thin shells, one workgroup of kLossThreads each.  _ce and _ce_dist are the same body under the two names the entry
+// points of include/locov_hip.h launch (without and with pw / gpw).
+template <bool GRAD>
+__global__ __launch_bounds__(kLossThreads) void grounding_ce_kernel(TailArgs a) { grounding_ce_body<GRAD>(a); }
+
+template <bool GRAD>
+__global__ __launch_bounds__(kLossThreads) void grounding_ce_dist_kernel(TailArgs a) { grounding_ce_body<GRAD>(a); }
+
+template <bool GRAD>
+__global__ __launch_bounds__(kLossThreads) void grounding_triplet_kernel(TailArgs a) { grounding_triplet_body<GRAD>(a); }
+
 
 // ---- the distillation losses (locov_distill_loss_fwd / _bwd; include/locov_hip.h states the arithmetic) ----
 constexpr int kDistMaxB = LOCOV_DISTILL_MAX_B;
@@ -538,23 +534,35 @@ extern "C" int locov_box_reg_loss(const float *proposal_boxes, const float *gt_b
     return check_launch("locov_box_reg_loss");
 }
 
-static int grounding_ce_args(const float *c0, const float *c1, const float *cm, const float *rm, int B, int T, int NR)
+// The grounding tail's entry points: the checks they share under the family's name `who`, each one's own null-output requirement,
+// one launch.  (The cross-entropy entries pass a valid mining, which their kernels do not read.)
+static int tail_args(const char *who, const locov::TailArgs &a)
 {
     using namespace locov;
-    LOCOV_REQUIRE(B >= 1 && B <= LOCOV_GROUNDING_CE_MAX_B && T >= 0 && NR >= 0, "locov_grounding_ce: 1 <= B <= %d", LOCOV_GROUNDING_CE_MAX_B);
-    LOCOV_REQUIRE((c0 || c1) && cm && rm, "locov_grounding_ce: null pointer");
+    LOCOV_REQUIRE(a.B >= 1 && a.B <= LOCOV_GROUNDING_CE_MAX_B && a.T >= 0 && a.NR >= 0, "%s: 1 <= B <= %d", who, LOCOV_GROUNDING_CE_MAX_B);
+    LOCOV_REQUIRE(a.mining == LOCOV_TRIPLET_HARDEST || a.mining == LOCOV_TRIPLET_EASIEST || a.mining == LOCOV_TRIPLET_GIVEN,
+                  "%s: unknown mining %d", who, a.mining);
+    LOCOV_REQUIRE(a.mining != LOCOV_TRIPLET_GIVEN || a.neg_idx, "%s: given negatives need their indices", who);
+    LOCOV_REQUIRE((a.cost[0] || a.cost[1]) && a.cmask && a.rmask, "%s: null pointer", who);
     return LOCOV_OK;
+}
+
+template <class Kernel>
+static int tail_launch(Kernel kernel, const char *what, const locov::TailArgs &a, locov_stream_t stream)
+{
+    using namespace locov;
+    hipLaunchKernelGGL(kernel, dim3(1), dim3(kLossThreads), 0, as_stream(stream), a);
+    return check_launch(what);
 }
 
 extern "C" int locov_grounding_ce_fwd(const float *cost_w2r, const float *cost_r2w, const float *caption_mask, const float *region_mask, int B,
                                       int T, int NR, float *out8, locov_stream_t stream)
 {
     using namespace locov;
-    if (int rc = grounding_ce_args(cost_w2r, cost_r2w, caption_mask, region_mask, B, T, NR)) return rc;
+    const TailArgs a = {{cost_w2r, cost_r2w}, caption_mask, region_mask, B, T, NR, LOCOV_TRIPLET_HARDEST, 0.f, nullptr, out8};
+    if (int rc = tail_args("locov_grounding_ce", a)) return rc;
     LOCOV_REQUIRE(out8, "locov_grounding_ce_fwd: null output");
-    hipLaunchKernelGGL(grounding_ce_kernel<false>, dim3(1), dim3(kLossThreads), 0, as_stream(stream), cost_w2r, cost_r2w, caption_mask,
-                       region_mask, B, T, NR, out8, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
-    return check_launch("locov_grounding_ce_fwd");
+    return tail_launch(grounding_ce_kernel<false>, "locov_grounding_ce_fwd", a, stream);
 }
 
 extern "C" int locov_grounding_ce_bwd(const float *cost_w2r, const float *cost_r2w, const float *caption_mask, const float *region_mask, int B,
@@ -562,31 +570,22 @@ extern "C" int locov_grounding_ce_bwd(const float *cost_w2r, const float *cost_r
                                       const float *g_r2w_image, float *dcost_w2r, float *dcost_r2w, locov_stream_t stream)
 {
     using namespace locov;
-    if (int rc = grounding_ce_args(cost_w2r, cost_r2w, caption_mask, region_mask, B, T, NR)) return rc;
+    const TailArgs a = {{cost_w2r, cost_r2w}, caption_mask, region_mask, B, T, NR, LOCOV_TRIPLET_HARDEST, 0.f, nullptr, nullptr, {},
+                        {g_w2r_caption, g_w2r_image, g_r2w_caption, g_r2w_image}, {}, {dcost_w2r, dcost_r2w}};
+    if (int rc = tail_args("locov_grounding_ce", a)) return rc;
     LOCOV_REQUIRE((!cost_w2r || dcost_w2r) && (!cost_r2w || dcost_r2w), "locov_grounding_ce_bwd: null gradient output");
-    hipLaunchKernelGGL(grounding_ce_kernel<true>, dim3(1), dim3(kLossThreads), 0, as_stream(stream), cost_w2r, cost_r2w, caption_mask,
-                       region_mask, B, T, NR, nullptr, g_w2r_caption, g_w2r_image, g_r2w_caption, g_r2w_image, dcost_w2r, dcost_r2w);
-    return check_launch("locov_grounding_ce_bwd");
-}
-
-static int grounding_ce_dist_args(const float *c0, const float *c1, const float *cm, const float *rm, int B, int T, int NR)
-{
-    using namespace locov;
-    LOCOV_REQUIRE(B >= 1 && B <= LOCOV_GROUNDING_CE_MAX_B && T >= 0 && NR >= 0, "locov_grounding_ce_dist: 1 <= B <= %d",
-                  LOCOV_GROUNDING_CE_MAX_B);
-    LOCOV_REQUIRE((c0 || c1) && cm && rm, "locov_grounding_ce_dist: null pointer");
-    return LOCOV_OK;
+    return tail_launch(grounding_ce_kernel<true>, "locov_grounding_ce_bwd", a, stream);
 }
 
 extern "C" int locov_grounding_ce_dist_fwd(const float *cost_w2r, const float *cost_r2w, const float *caption_mask, const float *region_mask,
                                            int B, int T, int NR, float *out8, float *pw_w2r, float *pw_r2w, locov_stream_t stream)
 {
     using namespace locov;
-    if (int rc = grounding_ce_dist_args(cost_w2r, cost_r2w, caption_mask, region_mask, B, T, NR)) return rc;
+    const TailArgs a = {{cost_w2r, cost_r2w}, caption_mask, region_mask, B, T, NR, LOCOV_TRIPLET_HARDEST, 0.f, nullptr, out8,
+                        {pw_w2r, pw_r2w}};
+    if (int rc = tail_args("locov_grounding_ce_dist", a)) return rc;
     LOCOV_REQUIRE(out8 && (!cost_w2r || pw_w2r) && (!cost_r2w || pw_r2w), "locov_grounding_ce_dist_fwd: null output");
-    hipLaunchKernelGGL(grounding_ce_dist_kernel<false>, dim3(1), dim3(kLossThreads), 0, as_stream(stream), cost_w2r, cost_r2w, caption_mask,
-                       region_mask, B, T, NR, out8, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, pw_w2r, pw_r2w, nullptr, nullptr);
-    return check_launch("locov_grounding_ce_dist_fwd");
+    return tail_launch(grounding_ce_dist_kernel<false>, "locov_grounding_ce_dist_fwd", a, stream);
 }
 
 extern "C" int locov_grounding_ce_dist_bwd(const float *cost_w2r, const float *cost_r2w, const float *caption_mask, const float *region_mask,
@@ -595,25 +594,11 @@ extern "C" int locov_grounding_ce_dist_bwd(const float *cost_w2r, const float *c
                                            const float *g_pw_r2w, float *dcost_w2r, float *dcost_r2w, locov_stream_t stream)
 {
     using namespace locov;
-    if (int rc = grounding_ce_dist_args(cost_w2r, cost_r2w, caption_mask, region_mask, B, T, NR)) return rc;
+    const TailArgs a = {{cost_w2r, cost_r2w}, caption_mask, region_mask, B, T, NR, LOCOV_TRIPLET_HARDEST, 0.f, nullptr, nullptr, {},
+                        {g_w2r_caption, g_w2r_image, g_r2w_caption, g_r2w_image}, {g_pw_w2r, g_pw_r2w}, {dcost_w2r, dcost_r2w}};
+    if (int rc = tail_args("locov_grounding_ce_dist", a)) return rc;
     LOCOV_REQUIRE((!cost_w2r || dcost_w2r) && (!cost_r2w || dcost_r2w), "locov_grounding_ce_dist_bwd: null gradient output");
-    hipLaunchKernelGGL(grounding_ce_dist_kernel<true>, dim3(1), dim3(kLossThreads), 0, as_stream(stream), cost_w2r, cost_r2w, caption_mask,
-                       region_mask, B, T, NR, nullptr, g_w2r_caption, g_w2r_image, g_r2w_caption, g_r2w_image, dcost_w2r, dcost_r2w,
-                       nullptr, nullptr, cost_w2r ? g_pw_w2r : nullptr, cost_r2w ? g_pw_r2w : nullptr);
-    return check_launch("locov_grounding_ce_dist_bwd");
-}
-
-static int grounding_triplet_args(const float *c0, const float *c1, const float *cm, const float *rm, int B, int T, int NR, int mining,
-                                  const int64_t *neg_idx)
-{
-    using namespace locov;
-    LOCOV_REQUIRE(B >= 1 && B <= LOCOV_GROUNDING_CE_MAX_B && T >= 0 && NR >= 0, "locov_grounding_triplet: 1 <= B <= %d",
-                  LOCOV_GROUNDING_CE_MAX_B);
-    LOCOV_REQUIRE(mining == LOCOV_TRIPLET_HARDEST || mining == LOCOV_TRIPLET_EASIEST || mining == LOCOV_TRIPLET_GIVEN,
-                  "locov_grounding_triplet: unknown mining %d", mining);
-    LOCOV_REQUIRE(mining != LOCOV_TRIPLET_GIVEN || neg_idx, "locov_grounding_triplet: given negatives need their indices");
-    LOCOV_REQUIRE((c0 || c1) && cm && rm, "locov_grounding_triplet: null pointer");
-    return LOCOV_OK;
+    return tail_launch(grounding_ce_dist_kernel<true>, "locov_grounding_ce_dist_bwd", a, stream);
 }
 
 extern "C" int locov_grounding_triplet_fwd(const float *cost_w2r, const float *cost_r2w, const float *caption_mask, const float *region_mask,
@@ -621,12 +606,10 @@ extern "C" int locov_grounding_triplet_fwd(const float *cost_w2r, const float *c
                                            float *pw_w2r, float *pw_r2w, locov_stream_t stream)
 {
     using namespace locov;
-    if (int rc = grounding_triplet_args(cost_w2r, cost_r2w, caption_mask, region_mask, B, T, NR, mining, neg_idx)) return rc;
+    const TailArgs a = {{cost_w2r, cost_r2w}, caption_mask, region_mask, B, T, NR, mining, margin, neg_idx, out8, {pw_w2r, pw_r2w}};
+    if (int rc = tail_args("locov_grounding_triplet", a)) return rc;
     LOCOV_REQUIRE(out8, "locov_grounding_triplet_fwd: null output");
-    hipLaunchKernelGGL(grounding_triplet_kernel<false>, dim3(1), dim3(kLossThreads), 0, as_stream(stream), cost_w2r, cost_r2w,
-                       caption_mask, region_mask, B, T, NR, mining, margin, neg_idx, out8, cost_w2r ? pw_w2r : nullptr,
-                       cost_r2w ? pw_r2w : nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
-    return check_launch("locov_grounding_triplet_fwd");
+    return tail_launch(grounding_triplet_kernel<false>, "locov_grounding_triplet_fwd", a, stream);
 }
 
 extern "C" int locov_grounding_triplet_bwd(const float *cost_w2r, const float *cost_r2w, const float *caption_mask, const float *region_mask,
@@ -636,14 +619,13 @@ extern "C" int locov_grounding_triplet_bwd(const float *cost_w2r, const float *c
                                            float *dcost_r2w, locov_stream_t stream)
 {
     using namespace locov;
-    if (int rc = grounding_triplet_args(cost_w2r, cost_r2w, caption_mask, region_mask, B, T, NR, mining, neg_idx)) return rc;
+    const TailArgs a = {{cost_w2r, cost_r2w}, caption_mask, region_mask, B, T, NR, mining, margin, neg_idx, nullptr, {},
+                        {g_w2r_caption, g_w2r_image, g_r2w_caption, g_r2w_image}, {g_pw_w2r, g_pw_r2w}, {dcost_w2r, dcost_r2w}};
+    if (int rc = tail_args("locov_grounding_triplet", a)) return rc;
     LOCOV_REQUIRE((!cost_w2r || dcost_w2r) && (!cost_r2w || dcost_r2w), "locov_grounding_triplet_bwd: null gradient output");
-    hipLaunchKernelGGL(grounding_triplet_kernel<true>, dim3(1), dim3(kLossThreads), 0, as_stream(stream), cost_w2r, cost_r2w,
-                       caption_mask, region_mask, B, T, NR, mining, margin, neg_idx, nullptr, nullptr, nullptr, g_w2r_caption,
-                       g_w2r_image, g_r2w_caption, g_r2w_image, cost_w2r ? g_pw_w2r : nullptr, cost_r2w ? g_pw_r2w : nullptr,
-                       dcost_w2r, dcost_r2w);
-    return check_launch("locov_grounding_triplet_bwd");
+    return tail_launch(grounding_triplet_kernel<true>, "locov_grounding_triplet_bwd", a, stream);
 }
+
 
 static int distill_args(const float *trans, const float *w2r, const float *r2w, int B, int kind, float temperature)
 {

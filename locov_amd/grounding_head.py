@@ -100,27 +100,13 @@ class GroundingHead(nn.Module):
                                  region_mask.sum(dim=1))
         # :150-228 temperature, masked softmax both ways, aligned-local distances -> [caption, image] costs
         cost_w2r, cost_r2w = ops.grounding_costs(S, caption_mask, region_mask, self.temperature)
-        losses, other_info = {}, {}
         if S.is_cuda and B <= ops.GROUNDING_CE_MAX_B and os.environ.get("LOCOV_FUSED_LOSSES", "1") != "0":
             # :239-290, :357-377 in one launch (ops.grounding_ce = locov_grounding_ce_fwd / _bwd): the (max + 100) replacement, both
             # log-softmaxes, the diagonal means and the batch accuracies of both alignments; with the distributions requested the
             # same launch also writes the filled costs (ops.grounding_ce_dist = locov_grounding_ce_dist_fwd / _bwd)
-            c0, c1 = cost_w2r if self.align_words else None, cost_r2w if self.align_regions else None
-            if self.return_dist:
-                vals, pw0, pw1 = ops.grounding_ce_dist(c0, c1, caption_mask, region_mask)
-            else:
-                vals = ops.grounding_ce(c0, c1, caption_mask, region_mask)
-            for k, (on, tag) in enumerate(((self.align_words, "Words"), (self.align_regions, "Regions"))):
-                if not on:
-                    continue
-                losses[f"CE_loss (Align {tag}, Choose Caption)"] = vals[4 * k]
-                losses[f"CE_loss (Align {tag}, Choose Image)"] = vals[4 * k + 1]
-                other_info[f"Batch Accuracy (Align {tag}, Choose Caption)"] = vals[4 * k + 2]
-                other_info[f"Batch Accuracy (Align {tag}, Choose Image)"] = vals[4 * k + 3]
-            self.log_info = {**losses, **other_info}
-            if self.return_dist:
-                return other_info, losses, {"w2r": pw0, "r2w": pw1}
-            return other_info, losses
+            return self._ce_tail(cost_w2r if self.align_words else None, cost_r2w if self.align_regions else None, caption_mask,
+                                 region_mask)
+        losses, other_info = {}, {}
         # :232-243 pairs with neither words nor regions get (max + 100)
         num_words, num_regions = caption_mask.sum(dim=1), region_mask.sum(dim=1)
         ok = (num_words[:, None] > 0) | (num_regions[None, :] > 0)
@@ -147,29 +133,31 @@ class GroundingHead(nn.Module):
         """:150-343 for ALIGNMENT softmax | hardmax and LOSS cross_entropy | triplet: one alignment launch, one tail launch."""
         c0, c1 = ops.grounding_costs(S, caption_mask, region_mask, self.temperature, alignment=self.alignment,
                                      words=self.align_words, regions=self.align_regions)
-        pw0 = pw1 = None
         if self.loss_type == "cross_entropy":
-            name = "CE_loss"
-            if self.return_dist:
-                vals, pw0, pw1 = ops.grounding_ce_dist(c0, c1, caption_mask, region_mask)
-            else:
-                vals = ops.grounding_ce(c0, c1, caption_mask, region_mask)
-        else:
-            name = "Triplet Loss"
-            mining, neg_idx = self.negative_mining, None
-            if B < 2:
-                mining = "hardest"                            # (:296 negative = positive + margin whatever the mining; nothing is drawn)
-            elif mining == "random":
-                # the draws of `_general`, same calls in the same order: per direction that is on, (1, B) then (B, 1)
-                draws = [None] * 4
-                for k, on in enumerate((self.align_words, self.align_regions)):
-                    if on:
-                        draws[2 * k] = torch.randint(B - 1, (1, B), device=S.device).view(B)
-                        draws[2 * k + 1] = torch.randint(B - 1, (B, 1), device=S.device).view(B)
-                spare = next(d for d in draws if d is not None)                  # (a direction that is off is not read)
-                mining, neg_idx = "given", torch.stack([d if d is not None else spare for d in draws]).view(2, 2, B)
-            res = ops.grounding_triplet(c0, c1, caption_mask, region_mask, mining, self.margin, neg_idx, with_dist=self.return_dist)
-            vals, pw0, pw1 = res if self.return_dist else (res, None, None)
+            return self._ce_tail(c0, c1, caption_mask, region_mask)
+        mining, neg_idx = self.negative_mining, None
+        if B < 2:
+            mining = "hardest"                                # (:296 negative = positive + margin whatever the mining; nothing is drawn)
+        elif mining == "random":
+            # the draws of `_general`, same calls in the same order: per direction that is on, (1, B) then (B, 1)
+            draws = [None] * 4
+            for k, on in enumerate((self.align_words, self.align_regions)):
+                if on:
+                    draws[2 * k] = torch.randint(B - 1, (1, B), device=S.device).view(B)
+                    draws[2 * k + 1] = torch.randint(B - 1, (B, 1), device=S.device).view(B)
+            spare = next(d for d in draws if d is not None)                      # (a direction that is off is not read)
+            mining, neg_idx = "given", torch.stack([d if d is not None else spare for d in draws]).view(2, 2, B)
+        res = ops.grounding_triplet(c0, c1, caption_mask, region_mask, mining, self.margin, neg_idx, with_dist=self.return_dist)
+        return self._tail_result("Triplet Loss", *(res if self.return_dist else (res, None, None)))
+
+    def _ce_tail(self, c0, c1, caption_mask, region_mask):
+        """The cross-entropy tail on the costs that are on, with the filled costs where the distributions are returned."""
+        if self.return_dist:
+            return self._tail_result("CE_loss", *ops.grounding_ce_dist(c0, c1, caption_mask, region_mask))
+        return self._tail_result("CE_loss", ops.grounding_ce(c0, c1, caption_mask, region_mask), None, None)
+
+    def _tail_result(self, name, vals, pw0, pw1):
+        """The tail's 8 scalars (ops.grounding_ce's layout) and filled costs as forward returns them; fills log_info."""
         losses, other_info = {}, {}
         for k, (on, tag) in enumerate(((self.align_words, "Words"), (self.align_regions, "Regions"))):
             if not on:

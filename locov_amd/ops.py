@@ -1713,40 +1713,12 @@ def linear_autograd(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.
     return linear(x.detach(), weight.detach(), bias.detach() if bias is not None else None)
 
 
-class _GroundingFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, S, cmask, rmask, B, T, NR, temperature):
-        S = _dev(S, "S")
-        cmask, rmask = _dev(cmask, "caption_mask"), _dev(rmask, "region_mask")
-        w2r = torch.empty((B, B), dtype=torch.float32, device=S.device)
-        r2w = torch.empty((B, B), dtype=torch.float32, device=S.device)
-        with torch.cuda.device(S.device):
-            check(_lib.load().locov_grounding_fwd(_ptr(S), B, T, NR, _ptr(cmask), _ptr(rmask), float(temperature),
-                                                  _ptr(w2r), _ptr(r2w), _stream(S)), "locov_grounding_fwd")
-        ctx.save_for_backward(S, cmask, rmask)
-        ctx.dims = (B, T, NR, temperature)
-        return w2r, r2w
-
-    @staticmethod
-    def backward(ctx, g_w2r, g_r2w):
-        S, cmask, rmask = ctx.saved_tensors
-        B, T, NR, temperature = ctx.dims
-        g_w2r = _dev(g_w2r if g_w2r is not None else torch.zeros(B, B, device=S.device), "grad_w2r")
-        g_r2w = _dev(g_r2w if g_r2w is not None else torch.zeros(B, B, device=S.device), "grad_r2w")
-        dS = torch.empty_like(S)
-        with torch.cuda.device(S.device):
-            check(_lib.load().locov_grounding_bwd(_ptr(S), B, T, NR, _ptr(cmask), _ptr(rmask), float(temperature),
-                                                  _ptr(g_w2r), _ptr(g_r2w), _ptr(dS), _stream(S)),
-                  "locov_grounding_bwd")
-        return dS, None, None, None, None, None, None
-
-
 GROUNDING_ALIGNMENTS = {"softmax": _lib.GROUNDING_ALIGN_SOFTMAX, "hardmax": _lib.GROUNDING_ALIGN_HARDMAX}
 
 
 class _GroundingAlignFn(torch.autograd.Function):
-    """_GroundingFn with the alignment rule chosen and either direction optional (locov_grounding_align_fwd / _bwd): returns the
-    costs of the directions that are on."""
+    """The alignment launch with its rule chosen and either direction optional (locov_grounding_align_fwd / _bwd): returns the costs
+    of the directions that are on."""
 
     @staticmethod
     def forward(ctx, S, cmask, rmask, B, T, NR, temperature, alignment, words, regions):
@@ -1797,51 +1769,89 @@ def grounding_costs(S: torch.Tensor, caption_mask: torch.Tensor, region_mask: to
         raise ValueError(f"grounding_costs: unknown alignment {alignment!r} (softmax | hardmax)")
     if not (words or regions):
         raise ValueError("grounding_costs: both alignment directions are off")
-    if alignment == "softmax" and words and regions:
-        return _GroundingFn.apply(S, caption_mask.to(torch.float32), region_mask.to(torch.float32), B, T, NR,
-                                  float(temperature))
     res = list(_GroundingAlignFn.apply(S, caption_mask.to(torch.float32), region_mask.to(torch.float32), B, T, NR, float(temperature),
                                        GROUNDING_ALIGNMENTS[alignment], bool(words), bool(regions)))
     return (res.pop(0) if words else None), (res.pop(0) if regions else None)
 
 
 GROUNDING_CE_MAX_B = 64        # LOCOV_GROUNDING_CE_MAX_B
+TRIPLET_MINING = {"hardest": _lib.TRIPLET_HARDEST, "easiest": _lib.TRIPLET_EASIEST, "given": _lib.TRIPLET_GIVEN}
 
 
-class _GroundingCEFn(torch.autograd.Function):
+class _GroundingTailFn(torch.autograd.Function):
+    """The tail of GroundingHead.forward on the [B, B] costs, one launch each way: loss "cross_entropy" without the filled costs
+    (locov_grounding_ce_fwd / _bwd) or with them (locov_grounding_ce_dist_), or "triplet" (locov_grounding_triplet_; mining, margin
+    and neg_idx are its alone).  Returns the 8 scalars, then with_dist the filled cost of every direction that is on."""
+
     @staticmethod
-    def forward(ctx, cost_w2r, cost_r2w, cmask, rmask):
-        ref = cost_w2r if cost_w2r is not None else cost_r2w
+    def _head(ctx, c0, c1, cmask, rmask, neg_idx):
+        """(the costs' reference tensor, the arguments every entry point of ctx.entry starts with)"""
+        ref = c0 if c0 is not None else c1
+        head = (_ptr(c0), _ptr(c1), _ptr(cmask), _ptr(rmask), ref.shape[0], cmask.shape[1], rmask.shape[1])
+        return ref, head + ((*ctx.triplet, _ptr(neg_idx)) if ctx.triplet else ())
+
+    @staticmethod
+    def forward(ctx, cost_w2r, cost_r2w, cmask, rmask, loss, mining, margin, neg_idx, with_dist):
+        ctx.set_materialize_grads(False)                  # unused outputs send NULL, not zero-filled upstream gradients
         c0 = _dev(cost_w2r, "cost_w2r") if cost_w2r is not None else None
         c1 = _dev(cost_r2w, "cost_r2w") if cost_r2w is not None else None
         cmask, rmask = _dev(cmask, "caption_mask"), _dev(rmask, "region_mask")
-        B, T, NR = ref.shape[0], cmask.shape[1], rmask.shape[1]
-        out = torch.zeros(8, dtype=torch.float32, device=ref.device) if (c0 is None or c1 is None) else \
-            torch.empty(8, dtype=torch.float32, device=ref.device)
+        ctx.triplet = (mining, margin) if loss == "triplet" else None
+        ctx.entry = "locov_grounding_triplet" if ctx.triplet else "locov_grounding_ce_dist" if with_dist else "locov_grounding_ce"
+        ctx.pw_args = ctx.entry != "locov_grounding_ce"   # (the plain cross-entropy pair has no pw / gpw arguments)
+        ref, head = _GroundingTailFn._head(ctx, c0, c1, cmask, rmask, neg_idx)
+        # locov_grounding_ce_fwd's caller zero-fills an absent alignment's four outputs; the other entry points' kernels do
+        out = (torch.empty if ctx.pw_args or (c0 is not None and c1 is not None) else torch.zeros)(8, dtype=torch.float32, device=ref.device)
+        pw0 = torch.empty_like(c0) if with_dist and c0 is not None else None
+        pw1 = torch.empty_like(c1) if with_dist and c1 is not None else None
         with torch.cuda.device(ref.device):
-            check(_lib.load().locov_grounding_ce_fwd(_ptr(c0), _ptr(c1), _ptr(cmask), _ptr(rmask), B, T, NR, _ptr(out), _stream(ref)),
-                  "locov_grounding_ce_fwd")
-        ctx.save_for_backward(*(t for t in (c0, c1) if t is not None), cmask, rmask)
-        ctx.have = (c0 is not None, c1 is not None)
+            check(getattr(_lib.load(), ctx.entry + "_fwd")(*head, _ptr(out), *((_ptr(pw0), _ptr(pw1)) if ctx.pw_args else ()), _stream(ref)),
+                  ctx.entry + "_fwd")
+        ctx.save_for_backward(*(t for t in (c0, c1, neg_idx) if t is not None), cmask, rmask)
+        ctx.have = (c0 is not None, c1 is not None, neg_idx is not None)
+        ctx.with_dist = with_dist
         vals = out.unbind(0)
         ctx.mark_non_differentiable(vals[2], vals[3], vals[6], vals[7])
-        return vals
+        return vals + tuple(p for p in (pw0, pw1) if p is not None)
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, *g):
         saved = list(ctx.saved_tensors)
-        c0 = saved.pop(0) if ctx.have[0] else None
-        c1 = saved.pop(0) if ctx.have[1] else None
+        c0, c1, neg_idx = (saved.pop(0) if on else None for on in ctx.have)
         cmask, rmask = saved
-        ref = c0 if c0 is not None else c1
-        B, T, NR = ref.shape[0], cmask.shape[1], rmask.shape[1]
+        ref, head = _GroundingTailFn._head(ctx, c0, c1, cmask, rmask, neg_idx)
         ups = [(_dev(g[i].reshape(1), "grad") if g[i] is not None else None) for i in (0, 1, 4, 5)]
+        gpw = list(g[8:])
+        g0 = gpw.pop(0) if ctx.with_dist and ctx.have[0] else None
+        g1 = gpw.pop(0) if ctx.with_dist and ctx.have[1] else None
+        g0 = _dev(g0, "grad_pw_w2r") if g0 is not None else None
+        g1 = _dev(g1, "grad_pw_r2w") if g1 is not None else None
         d0 = torch.empty_like(c0) if c0 is not None else None
         d1 = torch.empty_like(c1) if c1 is not None else None
         with torch.cuda.device(ref.device):
-            check(_lib.load().locov_grounding_ce_bwd(_ptr(c0), _ptr(c1), _ptr(cmask), _ptr(rmask), B, T, NR, *(_ptr(u) for u in ups),
-                                                     _ptr(d0), _ptr(d1), _stream(ref)), "locov_grounding_ce_bwd")
-        return d0, d1, None, None
+            check(getattr(_lib.load(), ctx.entry + "_bwd")(*head, *(_ptr(u) for u in ups), *((_ptr(g0), _ptr(g1)) if ctx.pw_args else ()),
+                                                          _ptr(d0), _ptr(d1), _stream(ref)), ctx.entry + "_bwd")
+        return (d0, d1) + (None,) * 7
+
+
+def _grounding_tail(cost_w2r, cost_r2w, caption_mask, region_mask, loss, mining=0, margin=0.0, neg_idx=None, with_dist=False):
+    """What grounding_ce, grounding_ce_dist and grounding_triplet share: (the 8 scalars, pw_w2r, pw_r2w), the two None without
+    with_dist or for an absent alignment."""
+    res = _GroundingTailFn.apply(cost_w2r, cost_r2w, caption_mask.to(torch.float32), region_mask.to(torch.float32), loss, mining, margin,
+                                 neg_idx, with_dist)
+    pw = list(res[8:])
+    pw0 = pw.pop(0) if with_dist and cost_w2r is not None else None
+    pw1 = pw.pop(0) if with_dist and cost_r2w is not None else None
+    return tuple(res[:8]), pw0, pw1
+
+
+def _tail_costs(fn: str, cost_w2r: Optional[torch.Tensor], cost_r2w: Optional[torch.Tensor]) -> torch.Tensor:
+    """The cost that is there, after the check the three tail functions share."""
+    ref = cost_w2r if cost_w2r is not None else cost_r2w
+    if ref is None or ref.dim() != 2 or ref.shape[0] != ref.shape[1] or ref.shape[0] > GROUNDING_CE_MAX_B:
+        raise ValueError(f"{fn}: costs must be [B, B] with B <= {GROUNDING_CE_MAX_B}")
+    return ref
 
 
 def grounding_ce(cost_w2r: Optional[torch.Tensor], cost_r2w: Optional[torch.Tensor], caption_mask: torch.Tensor,
@@ -1849,56 +1859,8 @@ def grounding_ce(cost_w2r: Optional[torch.Tensor], cost_r2w: Optional[torch.Tens
     """The cross-entropy tail of GroundingHead.forward (grounding_head.py:239-290,357-377) on the [B, B] costs of grounding_costs, one
     launch (and one in backward): returns 8 scalars -- for w2r, then r2w: CE choose caption, CE choose image, batch accuracy choose
     caption, batch accuracy choose image (zeros for a cost that is None).  Differentiable in the costs."""
-    ref = cost_w2r if cost_w2r is not None else cost_r2w
-    if ref is None or ref.dim() != 2 or ref.shape[0] != ref.shape[1] or ref.shape[0] > GROUNDING_CE_MAX_B:
-        raise ValueError(f"grounding_ce: costs must be [B, B] with B <= {GROUNDING_CE_MAX_B}")
-    return _GroundingCEFn.apply(cost_w2r, cost_r2w, caption_mask.to(torch.float32), region_mask.to(torch.float32))
-
-
-
-class _GroundingCEDistFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, cost_w2r, cost_r2w, cmask, rmask):
-        ctx.set_materialize_grads(False)                  # unused outputs send NULL, not zero-filled upstream gradients
-        ref = cost_w2r if cost_w2r is not None else cost_r2w
-        c0 = _dev(cost_w2r, "cost_w2r") if cost_w2r is not None else None
-        c1 = _dev(cost_r2w, "cost_r2w") if cost_r2w is not None else None
-        cmask, rmask = _dev(cmask, "caption_mask"), _dev(rmask, "region_mask")
-        B, T, NR = ref.shape[0], cmask.shape[1], rmask.shape[1]
-        out = torch.empty(8, dtype=torch.float32, device=ref.device)          # (the kernel zeroes an absent alignment's four)
-        pw0 = torch.empty_like(c0) if c0 is not None else None
-        pw1 = torch.empty_like(c1) if c1 is not None else None
-        with torch.cuda.device(ref.device):
-            check(_lib.load().locov_grounding_ce_dist_fwd(_ptr(c0), _ptr(c1), _ptr(cmask), _ptr(rmask), B, T, NR, _ptr(out), _ptr(pw0),
-                                                          _ptr(pw1), _stream(ref)), "locov_grounding_ce_dist_fwd")
-        ctx.save_for_backward(*(t for t in (c0, c1) if t is not None), cmask, rmask)
-        ctx.have = (c0 is not None, c1 is not None)
-        vals = out.unbind(0)
-        ctx.mark_non_differentiable(vals[2], vals[3], vals[6], vals[7])
-        return vals + tuple(p for p in (pw0, pw1) if p is not None)
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, *g):
-        saved = list(ctx.saved_tensors)
-        c0 = saved.pop(0) if ctx.have[0] else None
-        c1 = saved.pop(0) if ctx.have[1] else None
-        cmask, rmask = saved
-        ref = c0 if c0 is not None else c1
-        B, T, NR = ref.shape[0], cmask.shape[1], rmask.shape[1]
-        ups = [(_dev(g[i].reshape(1), "grad") if g[i] is not None else None) for i in (0, 1, 4, 5)]
-        gpw = list(g[8:])
-        g0 = gpw.pop(0) if ctx.have[0] else None
-        g1 = gpw.pop(0) if ctx.have[1] else None
-        g0 = _dev(g0, "grad_pw_w2r") if g0 is not None else None
-        g1 = _dev(g1, "grad_pw_r2w") if g1 is not None else None
-        d0 = torch.empty_like(c0) if c0 is not None else None
-        d1 = torch.empty_like(c1) if c1 is not None else None
-        with torch.cuda.device(ref.device):
-            check(_lib.load().locov_grounding_ce_dist_bwd(_ptr(c0), _ptr(c1), _ptr(cmask), _ptr(rmask), B, T, NR, *(_ptr(u) for u in ups),
-                                                          _ptr(g0), _ptr(g1), _ptr(d0), _ptr(d1), _stream(ref)),
-                  "locov_grounding_ce_dist_bwd")
-        return d0, d1, None, None
+    _tail_costs("grounding_ce", cost_w2r, cost_r2w)
+    return _grounding_tail(cost_w2r, cost_r2w, caption_mask, region_mask, "cross_entropy")[0]
 
 
 def grounding_ce_dist(cost_w2r: Optional[torch.Tensor], cost_r2w: Optional[torch.Tensor], caption_mask: torch.Tensor,
@@ -1906,66 +1868,8 @@ def grounding_ce_dist(cost_w2r: Optional[torch.Tensor], cost_r2w: Optional[torch
     """grounding_ce for a GroundingHead that also returns its distributions (MMSS_HEAD.DISTILLATION_LOSS): one launch each way
     (locov_grounding_ce_dist_fwd / _bwd).  Returns (the 8 scalars of grounding_ce, pw_w2r, pw_r2w): the filled [B, B] costs
     (grounding_head.py:239-251, None for an absent alignment), differentiable in the costs on the pairs that are not filled."""
-    ref = cost_w2r if cost_w2r is not None else cost_r2w
-    if ref is None or ref.dim() != 2 or ref.shape[0] != ref.shape[1] or ref.shape[0] > GROUNDING_CE_MAX_B:
-        raise ValueError(f"grounding_ce_dist: costs must be [B, B] with B <= {GROUNDING_CE_MAX_B}")
-    res = _GroundingCEDistFn.apply(cost_w2r, cost_r2w, caption_mask.to(torch.float32), region_mask.to(torch.float32))
-    pw = list(res[8:])
-    pw0 = pw.pop(0) if cost_w2r is not None else None
-    pw1 = pw.pop(0) if cost_r2w is not None else None
-    return tuple(res[:8]), pw0, pw1
-
-
-TRIPLET_MINING = {"hardest": _lib.TRIPLET_HARDEST, "easiest": _lib.TRIPLET_EASIEST, "given": _lib.TRIPLET_GIVEN}
-
-
-class _GroundingTripletFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, cost_w2r, cost_r2w, cmask, rmask, mining, margin, neg_idx, with_dist):
-        ctx.set_materialize_grads(False)                  # unused outputs send NULL, not zero-filled upstream gradients
-        ref = cost_w2r if cost_w2r is not None else cost_r2w
-        c0 = _dev(cost_w2r, "cost_w2r") if cost_w2r is not None else None
-        c1 = _dev(cost_r2w, "cost_r2w") if cost_r2w is not None else None
-        cmask, rmask = _dev(cmask, "caption_mask"), _dev(rmask, "region_mask")
-        B, T, NR = ref.shape[0], cmask.shape[1], rmask.shape[1]
-        out = torch.empty(8, dtype=torch.float32, device=ref.device)          # (the kernel zeroes an absent alignment's four)
-        pw0 = torch.empty_like(c0) if with_dist and c0 is not None else None
-        pw1 = torch.empty_like(c1) if with_dist and c1 is not None else None
-        with torch.cuda.device(ref.device):
-            check(_lib.load().locov_grounding_triplet_fwd(_ptr(c0), _ptr(c1), _ptr(cmask), _ptr(rmask), B, T, NR, mining, margin,
-                                                          _ptr(neg_idx), _ptr(out), _ptr(pw0), _ptr(pw1), _stream(ref)),
-                  "locov_grounding_triplet_fwd")
-        ctx.save_for_backward(*(t for t in (c0, c1, neg_idx) if t is not None), cmask, rmask)
-        ctx.have = (c0 is not None, c1 is not None, neg_idx is not None)
-        ctx.args = (mining, margin, with_dist)
-        vals = out.unbind(0)
-        ctx.mark_non_differentiable(vals[2], vals[3], vals[6], vals[7])
-        return vals + tuple(p for p in (pw0, pw1) if p is not None)
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, *g):
-        saved = list(ctx.saved_tensors)
-        c0 = saved.pop(0) if ctx.have[0] else None
-        c1 = saved.pop(0) if ctx.have[1] else None
-        neg_idx = saved.pop(0) if ctx.have[2] else None
-        cmask, rmask = saved
-        mining, margin, with_dist = ctx.args
-        ref = c0 if c0 is not None else c1
-        B, T, NR = ref.shape[0], cmask.shape[1], rmask.shape[1]
-        ups = [(_dev(g[i].reshape(1), "grad") if g[i] is not None else None) for i in (0, 1, 4, 5)]
-        gpw = list(g[8:])
-        g0 = gpw.pop(0) if with_dist and ctx.have[0] else None
-        g1 = gpw.pop(0) if with_dist and ctx.have[1] else None
-        g0 = _dev(g0, "grad_pw_w2r") if g0 is not None else None
-        g1 = _dev(g1, "grad_pw_r2w") if g1 is not None else None
-        d0 = torch.empty_like(c0) if c0 is not None else None
-        d1 = torch.empty_like(c1) if c1 is not None else None
-        with torch.cuda.device(ref.device):
-            check(_lib.load().locov_grounding_triplet_bwd(_ptr(c0), _ptr(c1), _ptr(cmask), _ptr(rmask), B, T, NR, mining, margin,
-                                                          _ptr(neg_idx), *(_ptr(u) for u in ups), _ptr(g0), _ptr(g1), _ptr(d0),
-                                                          _ptr(d1), _stream(ref)), "locov_grounding_triplet_bwd")
-        return d0, d1, None, None, None, None, None, None
+    _tail_costs("grounding_ce_dist", cost_w2r, cost_r2w)
+    return _grounding_tail(cost_w2r, cost_r2w, caption_mask, region_mask, "cross_entropy", with_dist=True)
 
 
 def grounding_triplet(cost_w2r: Optional[torch.Tensor], cost_r2w: Optional[torch.Tensor], caption_mask: torch.Tensor,
@@ -1976,9 +1880,7 @@ def grounding_triplet(cost_w2r: Optional[torch.Tensor], cost_r2w: Optional[torch
     [2 (w2r, r2w), 2 (choose caption, choose image), B] with values in [0, B - 1): indices into the matrix without its diagonal, as
     NEGATIVE_MINING "random" draws them (the values stay on the device and are not inspected here).  Returns the 8 scalars in
     grounding_ce's layout (the hinge means in the CE slots); with_dist: (the 8 scalars, pw_w2r, pw_r2w) as grounding_ce_dist."""
-    ref = cost_w2r if cost_w2r is not None else cost_r2w
-    if ref is None or ref.dim() != 2 or ref.shape[0] != ref.shape[1] or ref.shape[0] > GROUNDING_CE_MAX_B:
-        raise ValueError(f"grounding_triplet: costs must be [B, B] with B <= {GROUNDING_CE_MAX_B}")
+    ref = _tail_costs("grounding_triplet", cost_w2r, cost_r2w)
     if mining not in TRIPLET_MINING:
         raise ValueError(f"grounding_triplet: unknown mining {mining!r} (hardest | easiest | given)")
     B = ref.shape[0]
@@ -1988,14 +1890,10 @@ def grounding_triplet(cost_w2r: Optional[torch.Tensor], cost_r2w: Optional[torch
         neg_idx = neg_idx.contiguous()
     else:
         neg_idx = None
-    res = _GroundingTripletFn.apply(cost_w2r, cost_r2w, caption_mask.to(torch.float32), region_mask.to(torch.float32),
-                                    TRIPLET_MINING[mining], float(margin), neg_idx, bool(with_dist))
-    if not with_dist:
-        return tuple(res[:8])
-    pw = list(res[8:])
-    pw0 = pw.pop(0) if cost_w2r is not None else None
-    pw1 = pw.pop(0) if cost_r2w is not None else None
-    return tuple(res[:8]), pw0, pw1
+    res = _grounding_tail(cost_w2r, cost_r2w, caption_mask, region_mask, "triplet", TRIPLET_MINING[mining], float(margin), neg_idx,
+                          bool(with_dist))
+    return res if with_dist else res[0]
+
 
 
 DISTILL_MAX_B = _lib.DISTILL_MAX_B   # LOCOV_DISTILL_MAX_B
