@@ -1335,6 +1335,56 @@ int locov_detector_rescale(const float *boxes, const int *roff_host, const float
                            const int *out_h_host, const int *out_w_host, int n_images, float *out_boxes, int64_t *src, int *counts,
                            locov_stream_t stream);
 
+/* ---- the caption path of the LSM step in one launch (csrc/caption.hip): BertEmbedding after the tokenizer --------------------
+ * (ovr/modeling/language/transf_models.py:105-154).  Added under ABI version 8.
+ *
+ * locov_caption_embed_fwd, for N = B * T tokens (flat position n = i * T + j):
+ *   packed  : int32 [4, N]: input_ids, token_type_ids, attention_mask, special_tokens_mask as the tokenizer produced them.  The
+ *             CALLER has validated 0 <= id < V and 0 <= type < type_vocab on the host (they are host integers before the upload).
+ *   draws   : float64 [2, N], or NULL when masked language modelling is inactive (neither training nor ..._VALIDATION).
+ *   The rule of :114-137, every comparison in double.  eligible = draws && !special && attention.  Eligible, u = draws[0][n]:
+ *     u < p: mlm_mask = 1 and q = u / p; q < p_mask: id = mask_id, special = 1; else q < p_mask_noise (the HOST's double sum
+ *     p_mask + p_noise): id = min((int)(draws[1][n] * len_tok), len_tok - 1); else the id stays.  u >= p, or not eligible: nothing
+ *     changes and mlm_mask = 0.  target_ids is the id before the rule.
+ *   ints    : out, int64 [int_rows, N]: input_ids, token_type_ids, attention_mask, special_tokens_mask and, with int_rows == 6,
+ *             target_ids and mlm_mask.  int_rows is 4 (MASKED_LANGUAGE_MODELING off; draws must be NULL) or 6.
+ *   W       : fp32 [V, H], the word table.  input_emb: out, fp32 [N, H] = W[input_ids] (the ids AFTER the rule), bit copies.
+ *   P       : fp32 [max_pos, H] or NULL.  NULL (ADD_POSITION_EMBEDDING off): encoded_tokens has the values of input_emb and
+ *             nothing else is read or written.  Otherwise, with Tt fp32 [type_vocab, H], gamma / beta fp32 [H] and eps:
+ *               x = (W[id] + Tt[type]) + P[j];  mean = sum x / H;  rstd = 1 / sqrt(sum (x - mean)^2 / H + eps)
+ *               encoded [N, H] = ((x - mean) * rstd * gamma + beta) * (keep ? keep[n, c] / (1 - p_drop) : 1)
+ *             in fp32, the row in registers, both sums by wave shuffles; mean / rstd: out, fp32 [N] (what the backward reads).
+ *   keep    : optional uint8 [N, H] keep mask drawn by the caller (the convention of locov_mha_fwd); NULL: no dropout.
+ *   One launch, one wave per token; 16-byte lanes when H % 4 == 0 and every pointer is 16-byte aligned (keep: 4-byte), scalar
+ *   lanes otherwise.  The kernel never reads outside the tables given valid ids: mask_id < V and len_tok <= V are checked here.
+ *   N > LOCOV_CAPTION_MAX_TOKENS or H > LOCOV_CAPTION_MAX_HIDDEN: LOCOV_ERR_UNSUPPORTED, never a truncation.  A null pointer,
+ *   N % T != 0, T > max_pos, mask_id >= V, len_tok > V, p outside (0, 1], p_drop outside [0, 1): LOCOV_ERR_INVALID_ARG.  Every
+ *   check happens before any HIP call.  N == 0: LOCOV_OK, nothing is read or written.
+ *
+ * locov_caption_embed_bwd: dW [V, H], the gradient of the word table (the only trainable tensor, :156-164).
+ *   ints    : the forward's output (rows 0 and 1 are read: the ids after the rule, the token types).
+ *   g_in    : fp32 [N, H], gradient of input_emb (may be NULL on the LayerNorm path); g_enc: fp32 [N, H], gradient of encoded
+ *             (LayerNorm path only; without it the caller passes the sum of its gradients as g_in).
+ *   P, Tt, gamma, mean, rstd, keep, p_drop: as in the forward (P == NULL: the gather-only path).
+ *   Three launches at most: the tokens are ranked by (id, flat position) by one workgroup (ids in LDS); on the LayerNorm path one
+ *   wave per token forms dx = LN-backward(g_enc * keep / (1 - p_drop)) + g_in into the workspace; then one wave per vocabulary
+ *   row binary-searches its run of tokens and writes 0.0f + their gradient rows, added in ascending flat position -- zeros for
+ *   an id no token has.  No atomics, a fixed summation order, every element of dW written by the launch (no memset): two calls
+ *   give the same bits.  workspace: locov_caption_embed_bwd_workspace_bytes(N, H, P != NULL) bytes, 16-byte aligned.
+ *   Limits and errors as in the forward.  V == 0 or H == 0: LOCOV_OK.  N == 0: dW is written as zeros. */
+#define LOCOV_CAPTION_MAX_TOKENS 8192
+#define LOCOV_CAPTION_MAX_HIDDEN 4096
+int locov_caption_embed_fwd(const int *packed, const double *draws, int N, int T, int H, int V, const float *W, const float *P,
+                            int max_pos, const float *Tt, int type_vocab, const float *gamma, const float *beta, float eps,
+                            const uint8_t *keep, float p_drop, double p, double p_mask, double p_mask_noise, int mask_id, int len_tok,
+                            int int_rows, int64_t *ints, float *input_emb, float *encoded, float *mean, float *rstd,
+                            locov_stream_t stream);
+int64_t locov_caption_embed_bwd_workspace_bytes(int N, int H, int layer_norm);
+int locov_caption_embed_bwd(const int64_t *ints, int N, int T, int H, int V, const float *W, const float *P, const float *Tt,
+                            const float *gamma, const float *mean, const float *rstd, const uint8_t *keep, float p_drop,
+                            const float *g_enc, const float *g_in, float *dW, void *workspace, int64_t workspace_bytes,
+                            locov_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -40,6 +40,7 @@ REGIONS_GRID, REGIONS_GRID_ALL, REGIONS_BOXES = 0, 1, 2
 REGIONS_ROWS, REGIONS_NCHW = 0, 1
 IMAGE_U8, IMAGE_F32, IMAGE_MAX_CHANNELS = 0, 1, 4
 MHA_MAX_S, MHA_MAX_GRID, MHA_HEAD_DIMS = 4096, 65535, (32, 64, 96, 128)
+CAPTION_MAX_TOKENS, CAPTION_MAX_HIDDEN = 8192, 4096
 
 _p = c_void_p  # device pointer
 
@@ -224,6 +225,10 @@ SIGNATURES = {
                                         POINTER(c_float), c_float, _p, c_int, c_int, _p]),
     "locov_detector_rescale": (c_int, [_p, POINTER(c_int), POINTER(c_float), POINTER(c_float), POINTER(c_int), POINTER(c_int), c_int,
                                        _p, _p, _p, _p]),
+    "locov_caption_embed_fwd": (c_int, [_p, _p, c_int, c_int, c_int, c_int, _p, _p, c_int, _p, c_int, _p, _p, c_float, _p, c_float, c_double,
+                                        c_double, c_double, c_int, c_int, c_int, _p, _p, _p, _p, _p, _p]),
+    "locov_caption_embed_bwd_workspace_bytes": (c_int64, [c_int, c_int, c_int]),
+    "locov_caption_embed_bwd": (c_int, [_p, c_int, c_int, c_int, c_int, _p, _p, _p, _p, _p, _p, _p, c_float, _p, _p, _p, _p, c_int64, _p]),
 }
 
 _lib = None

@@ -120,13 +120,29 @@ def get_cfg() -> CfgNode:
                 # never defined in ovr/config/config.py; defined here so that the predictor can be built
                 "MAX_TOKENS": 8,
             },
+            # config.py:23-28 (language_backbone.py).  coco_lsm.yaml -> TYPE "build_bertemb_backbone"; the default names the full BERT
+            # class, which is not built here.  VOCAB_FILE (this port): the vocab.txt the default WordPieceTokenizer is built from
+            "LANGUAGE_BACKBONE": {"TYPE": "build_bert_backbone", "FREEZE": True, "EMBEDDING_PATH": "", "ADD_POSITION_EMBEDDING": False,
+                                  "PRETRAINED": True, "VOCAB_FILE": ""},
             "MMSS_HEAD": {
-                "GROUNDING": {                                     # config.py:51-55 (keys the box predictor reads)
+                "TYPES": ("GroundingHead",), "DEFAULT_HEAD": "GroundingHead",          # config.py:36-41
+                "TIE_VL_PROJECTION_WEIGHTS": False, "IN_FEATURES": "res5",
+                "SPATIAL_DROPOUT": -1,                             # coco_lsm.yaml -> 100
+                "GROUNDING": {                                     # config.py:51-63
                     "LOCAL_METRIC": "dot", "GLOBAL_METRIC": "aligned_local", "ALIGNMENT": "softmax",
                     "ALIGNMENT_TEMPERATURE": 10.0,
+                    "LOSS": "cross_entropy", "NEGATIVE_MINING": "random", "TRIPLET_MARGIN": 1.0,
+                    "ALIGN_WORDS_TO_REGIONS": True, "ALIGN_REGIONS_TO_WORDS": True,
+                    "TEXT_INPUT": "input_embeddings",
                 },
                 "DISTILLATION_LOSS": False,                        # config.py:43; coco_lsm.yaml -> True
+                "DISTILLATION_LOSS_TYPE": "KD", "DISTILLATION_TEMPERATURE": 1.0, "DISTILLATION_LOSS_WEIGHT": 1.0,      # config.py:44-48
+                "DISTILLATION_DETACH_TEACHER": False, "DISTILLATION_TEACHER_TRANSFORMER": True,
                 "TRANSFORMER": {                                   # config.py:66-102 (keys TransformerHead reads)
+                    "MASKED_LANGUAGE_MODELING": False,             # config.py:67-79 (language_backbone.py, meta_arch.py)
+                    "MASKED_LANGUAGE_MODELING_PROB": 0.15, "MASKED_LANGUAGE_MODELING_PROB_MASK": 0.9,
+                    "MASKED_LANGUAGE_MODELING_PROB_NOISE": 0.0, "MASKED_LANGUAGE_MODELING_VALIDATION": True,
+                    "MASKED_VISUAL_MODELING": False,
                     "MVM_LOSS": "",                                # "", "reconstruction_error" or "contrastive_cross_entropy"
                     "MVM_LOSS_NUM_NEGATIVE": 128,
                     "MMM_LOSS": "",                                # "" or "cross_entropy"; coco_lsm.yaml -> "cross_entropy"

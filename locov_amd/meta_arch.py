@@ -28,12 +28,14 @@ from .structures import ImageList, boxes_class_of, cat_rows
 
 META_ARCH_REGISTRY = Registry("META_ARCH")
 
-__all__ = ["META_ARCH_REGISTRY", "GeneralizedRCNN", "OvrRCNN", "build_model", "detector_postprocess"]
+__all__ = ["META_ARCH_REGISTRY", "GeneralizedRCNN", "OvrRCNN", "DistillProposalMMSSRCNN", "DistillOnlyProposalMMSSRCNN", "build_model",
+           "detector_postprocess"]
 
 
-def build_model(cfg) -> nn.Module:
-    """[D2-upstream] build_model: the meta-architecture named by MODEL.META_ARCHITECTURE, on MODEL.DEVICE."""
-    model = META_ARCH_REGISTRY.get(cfg.MODEL.META_ARCHITECTURE)(cfg)
+def build_model(cfg, **kwargs) -> nn.Module:
+    """[D2-upstream] build_model: the meta-architecture named by MODEL.META_ARCHITECTURE, on MODEL.DEVICE.  kwargs go to its
+    from_config (the LSM models take tokenizer=...)."""
+    model = META_ARCH_REGISTRY.get(cfg.MODEL.META_ARCHITECTURE)(cfg, **kwargs)
     model.to(torch.device(cfg.MODEL.DEVICE))
     return model
 
@@ -196,3 +198,137 @@ class OvrRCNN(GeneralizedRCNN):
         if not self.training:
             return self.inference(batched_inputs)
         return {}, self._losses(batched_inputs)
+
+
+@META_ARCH_REGISTRY.register()
+class DistillProposalMMSSRCNN(GeneralizedRCNN):
+    """The LSM training model (ovr/modeling/meta_arch/distill_prop_mmss_gcnn.py:30-559, what configs/coco_lsm.yaml names): the
+    detector, the language backbone, the grounding / transformer heads on the whole-image grid and on the sampled boxes, and the
+    distillation losses between them.  Inference, preprocess_image and _postprocess are GeneralizedRCNN's kernel paths.
+
+    The training forward follows :210-477 statement by statement; the region dictionaries are mmss_regions.grid_regions /
+    box_regions, the caption dictionary language_backbone.BertEmbedding's one launch.  Differences, all on the host side:
+      * a caption is x["caption"] (a string, tokenized by the language backbone) or, when every input carries x["tokens"] -- a dict
+        of the four token lists [T] --, the tokens themselves;
+      * forward(batched_inputs, sample=None): `sample` may hold "mlm_draws" [2, B, T] float64, "grid_keys" [B, gh * gw] and "box_keys"
+        [sum of the sampled proposals] to replay the step's random choices; a missing entry is drawn from torch's device generator;
+      * the per-loss torch.isnan loop (:444-449, one host wait per loss) is ONE stacked test and one host read at the end of the
+        forward (ValueError, as the reference raises);
+      * self.log(...) statistics are not computed (each is a host sync); the heads' log_info stays lazy."""
+
+    @configurable
+    def __init__(self, *, language_backbone: nn.Module, mmss_heads: nn.Module, distill_loss: Optional[nn.Module] = None,
+                 vis_in_features: str = "res5", mvm: Optional[bool] = False, spatial_dropout: int = 100, **kwargs):
+        super().__init__(**kwargs)
+        self.language_backbone = language_backbone
+        self.vis_in_features = vis_in_features
+        self.mmss_heads = mmss_heads
+        self.mvm = mvm
+        self.spatial_dropout = spatial_dropout
+        self.distill_loss = distill_loss
+
+    @classmethod
+    def from_config(cls, cfg, tokenizer=None) -> Dict[str, Any]:
+        from .distill_losses import MultiDistillLoss, MultiDistillLossJS, MultiDistillLossL2
+        from .language_backbone import build_language_backbone
+        from .mmss_heads import build_mmss_heads
+        ret = super().from_config(cfg)
+        roi_heads, head_cfg = ret["roi_heads"], cfg.MODEL.MMSS_HEAD
+        language_backbone = build_language_backbone(cfg, tokenizer)
+        mmss_heads = build_mmss_heads(cfg, v_dim=roi_heads.output_shape, l_dim=language_backbone.out_channels, loc_dim=2,
+                                      backbone=language_backbone.body)
+        if cfg.MODEL.LOAD_EMB_PRED_FROM_MMSS_HEAD:            # :116-125 the detector's embedding layer IS the default head's projection
+            weight = mmss_heads[head_cfg.DEFAULT_HEAD].v2l_projection.weight
+            bias = mmss_heads[head_cfg.DEFAULT_HEAD].v2l_projection.bias
+            assert hasattr(roi_heads.box_predictor, "emb_pred")
+            assert weight.shape[0] == roi_heads.box_predictor.emb_pred.weight.shape[0]
+            assert weight.shape[1] == roi_heads.box_predictor.emb_pred.weight.shape[1]
+            roi_heads.box_predictor.emb_pred.weight = weight
+            roi_heads.box_predictor.emb_pred.bias = bias
+        distill_loss = None
+        if head_cfg.DISTILLATION_LOSS:                        # :127-150 (an unknown type leaves the name unbound there: an error here too)
+            kinds = {"KD": MultiDistillLoss, "JS": MultiDistillLossJS, "MSE": MultiDistillLossL2}
+            if head_cfg.DISTILLATION_LOSS_TYPE not in kinds:
+                raise UnboundLocalError(f"DISTILLATION_LOSS_TYPE {head_cfg.DISTILLATION_LOSS_TYPE!r}: one of {sorted(kinds)}")
+            distill_loss = kinds[head_cfg.DISTILLATION_LOSS_TYPE](head_cfg.DISTILLATION_TEMPERATURE, head_cfg.DISTILLATION_LOSS_WEIGHT,
+                                                                  head_cfg.DISTILLATION_DETACH_TEACHER,
+                                                                  head_cfg.DISTILLATION_TEACHER_TRANSFORMER)
+        ret.update(language_backbone=language_backbone, vis_in_features=head_cfg.IN_FEATURES, mmss_heads=mmss_heads,
+                   mvm=head_cfg.TRANSFORMER.MASKED_VISUAL_MODELING, spatial_dropout=head_cfg.SPATIAL_DROPOUT, distill_loss=distill_loss)
+        return ret
+
+    # ------------------------------------------------------------------------------------------------------------------- the call
+
+    grid_branch = True                                        # (DistillOnlyProposalMMSSRCNN: the sampled boxes only)
+
+    def preprocess_text(self, batched_inputs):
+        return [x["caption"] for x in batched_inputs]
+
+    def _caption(self, batched_inputs, draws):
+        body = self.language_backbone.body
+        if all("tokens" in x for x in batched_inputs):
+            keys = ("input_ids", "token_type_ids", "attention_mask", "special_tokens_mask")
+            return body.forward_tokenized({k: [x["tokens"][k] for x in batched_inputs] for k in keys}, draws)
+        from .language_backbone import MAX_LENGTH
+        return body.forward_tokenized(body.tokenizer(self.preprocess_text(batched_inputs), max_length=MAX_LENGTH), draws)
+
+    def _heads(self, regions, input_caption, prefix_out: str, prefix_dist: str, outputs, losses, distributions):
+        """:337-346 / :403-417: every head on one region dictionary, the results under the branch's prefixes."""
+        for head in self.mmss_heads:
+            if self.distill_loss is not None:
+                o, l, d = self.mmss_heads[head](regions, input_caption)
+                distributions.update({prefix_dist + k: v for k, v in d.items()})
+            else:
+                o, l = self.mmss_heads[head](regions, input_caption)
+            outputs.update({prefix_out + k: v for k, v in o.items()})
+            losses.update({prefix_out + k: v for k, v in l.items()})
+
+    def forward(self, batched_inputs: List[Dict[str, Any]], sample: Optional[Dict[str, torch.Tensor]] = None):
+        from .mmss_regions import box_regions, grid_regions
+        if not self.training:
+            return self.inference(batched_inputs)
+        if self.mvm:                                          # :330-331 / :400-401, before anything is enqueued
+            raise NotImplementedError("MASKED_VISUAL_MODELING is not implemented (nor is it in the reference)")
+        sample = sample or {}
+        input_caption = self._caption(batched_inputs, sample.get("mlm_draws"))                       # :229-230
+        images = self.preprocess_image(batched_inputs)
+        gt_instances = [x["instances"].to(self.device) for x in batched_inputs] if "instances" in batched_inputs[0] else None
+        features = self.backbone(images.tensor)
+        proposals, proposal_losses = self._proposals(batched_inputs, images, features, gt_instances)
+        visual_grid_features, box_features, box_proposals, detector_losses = self.roi_heads(images, features, proposals, gt_instances)
+        losses = {}
+        losses.update(detector_losses)
+        losses.update(proposal_losses)
+
+        mmss_outputs, mmss_losses, mmss_distributions = {}, {}, {}
+        if self.grid_branch:                                                                         # :273-346
+            input_image = grid_regions(visual_grid_features, images.image_sizes, images.tensor.shape[-2:], self.spatial_dropout,
+                                       self.training, keys=sample.get("grid_keys"))
+            self._heads(input_image, input_caption, "", "", mmss_outputs, mmss_losses, mmss_distributions)
+        input_boxes, _ = box_regions(box_features, box_proposals, self.spatial_dropout, self.training, keys=sample.get("box_keys"))   # :348-399
+        self._heads(input_boxes, input_caption, "Box ", "box_", mmss_outputs, mmss_losses, mmss_distributions)
+
+        if self.distill_loss is not None or not self.grid_branch:                                    # :424-442 / :692-699
+            d = mmss_distributions
+            if self.grid_branch:
+                mmss_losses["kd_loss"] = self.distill_loss(d["trans"], d["w2r"], d["r2w"])
+            mmss_losses["box_kd_loss"] = self.distill_loss(d["box_trans"], d["box_w2r"], d["box_r2w"])
+            if self.grid_branch:
+                mmss_losses["mixbox_kd_loss"] = self.distill_loss(d["trans"], d["box_w2r"], d["box_r2w"])
+
+        if mmss_losses:                                                                              # :444-449, one host read
+            if bool(torch.isnan(torch.stack([v.detach().reshape(()) for v in mmss_losses.values()])).any()):
+                for head in self.mmss_heads:
+                    print(head, self.mmss_heads[head].log_info)
+                print(images.image_sizes)
+                raise ValueError()
+        losses.update(mmss_losses)
+        return mmss_outputs, losses
+
+
+@META_ARCH_REGISTRY.register()
+class DistillOnlyProposalMMSSRCNN(DistillProposalMMSSRCNN):
+    """distill_prop_mmss_gcnn.py:561-: the same model without the whole-image grid branch -- the heads run on the sampled boxes
+    only, always with their distributions (the reference unpacks three results whatever DISTILLATION_LOSS says), and box_kd_loss is
+    the one distillation loss."""
+    grid_branch = False

@@ -2732,3 +2732,113 @@ def detector_rescale(boxes: torch.Tensor, sizes: Sequence[int], image_sizes, out
         check(_lib.load().locov_detector_rescale(_ptr(boxes), roff, sx, sy, oh, ow, n, _ptr(out), _ptr(src), _ptr(counts), _stream(boxes)),
               "locov_detector_rescale")
     return out, src, counts.tolist()
+
+
+# --------------------------------------------------------------------------------------
+# The caption path of the LSM step (csrc/caption.hip; language_backbone.py: BertEmbedding.forward_tokenized)
+CAPTION_MAX_TOKENS = _lib.CAPTION_MAX_TOKENS      # LOCOV_CAPTION_MAX_TOKENS
+CAPTION_MAX_HIDDEN = _lib.CAPTION_MAX_HIDDEN      # LOCOV_CAPTION_MAX_HIDDEN
+
+
+class CaptionMlm(NamedTuple):
+    """The masked-language-modelling rule's host numbers (transf_models.py:126-134): p = ..._PROB, p_mask = ..._PROB_MASK,
+    p_mask_noise = ..._PROB_MASK + ..._PROB_NOISE summed in double, the [MASK] id and len(tokenizer)."""
+    p: float
+    p_mask: float
+    p_mask_noise: float
+    mask_id: int
+    len_tok: int
+
+
+class _CaptionEmbedFn(torch.autograd.Function):
+    """locov_caption_embed_fwd / _bwd.  Returns (ints [rows, N] int64, input_emb [N, H], encoded [N, H] or None); differentiable
+    in `weight` only (BertEmbedding.freeze, transf_models.py:156-164)."""
+
+    @staticmethod
+    def forward(ctx, weight, packed, draws, T, mlm, int_rows, position, token_type, ln_weight, ln_bias, eps, keep, p_drop):
+        N, (V, H) = packed.shape[1], weight.shape
+        dev = weight.device
+        ints = torch.empty((int_rows, N), dtype=torch.int64, device=dev)
+        input_emb = torch.empty((N, H), dtype=torch.float32, device=dev)
+        layer_norm = position is not None
+        encoded = torch.empty((N, H), dtype=torch.float32, device=dev) if layer_norm else None
+        mean = torch.empty((N,), dtype=torch.float32, device=dev) if layer_norm else None
+        rstd = torch.empty((N,), dtype=torch.float32, device=dev) if layer_norm else None
+        m = mlm if draws is not None else CaptionMlm(1.0, 0.0, 0.0, 0, 1)
+        with torch.cuda.device(dev):
+            check(_lib.load().locov_caption_embed_fwd(
+                _ptr(packed), _ptr(draws), N, int(T), H, V, _ptr(weight), _ptr(position), position.shape[0] if layer_norm else 0,
+                _ptr(token_type), token_type.shape[0] if layer_norm else 0, _ptr(ln_weight), _ptr(ln_bias), float(eps), _ptr(keep),
+                float(p_drop), float(m.p), float(m.p_mask), float(m.p_mask_noise), int(m.mask_id), int(m.len_tok), int(int_rows),
+                _ptr(ints), _ptr(input_emb), _ptr(encoded), _ptr(mean), _ptr(rstd), _stream(weight)), "locov_caption_embed_fwd")
+        ctx.mark_non_differentiable(ints)
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(weight, ints, position, token_type, ln_weight, mean, rstd, keep)
+            ctx.args = (int(T), float(p_drop))
+        return ints, input_emb, encoded
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, _, g_in, g_enc):
+        weight, ints, position, token_type, ln_weight, mean, rstd, keep = ctx.saved_tensors
+        T, p_drop = ctx.args
+        N, (V, H) = ints.shape[1], weight.shape
+        layer_norm = position is not None
+        g_in = _dev(g_in, "grad_input_embeddings") if g_in is not None else None
+        g_enc = _dev(g_enc, "grad_encoded_tokens") if g_enc is not None else None
+        lib = _lib.load()
+        dW = torch.empty((V, H), dtype=torch.float32, device=weight.device)
+        nbytes = int(lib.locov_caption_embed_bwd_workspace_bytes(N, H, int(layer_norm)))
+        ws = _workspace("caption_bwd", weight, nbytes)
+        with torch.cuda.device(weight.device):
+            check(lib.locov_caption_embed_bwd(_ptr(ints), N, T, H, V, _ptr(weight), _ptr(position), _ptr(token_type), _ptr(ln_weight),
+                                              _ptr(mean), _ptr(rstd), _ptr(keep), p_drop, _ptr(g_enc), _ptr(g_in), _ptr(dW), _ptr(ws),
+                                              ws.numel(), _stream(weight)), "locov_caption_embed_bwd")
+        return (dW,) + (None,) * 12
+
+
+def caption_embed(packed: torch.Tensor, draws: Optional[torch.Tensor], T: int, weight: torch.Tensor, *, mlm: Optional[CaptionMlm] = None,
+                  with_targets: bool = True, position: Optional[torch.Tensor] = None, token_type: Optional[torch.Tensor] = None,
+                  ln_weight: Optional[torch.Tensor] = None, ln_bias: Optional[torch.Tensor] = None, eps: float = 1e-12,
+                  keep: Optional[torch.Tensor] = None, p_drop: float = 0.0):
+    """BertEmbedding's forward after the tokenizer (transf_models.py:114-152) in one launch (locov_caption_embed_fwd).
+
+    packed int32 [4, N] on the device: input_ids, token_type_ids, attention_mask, special_tokens_mask, N = B * T tokens, whose ids
+    and types the CALLER has validated against the tables on the host.  draws float64 [2, N] or None (masked language modelling
+    inactive); mlm: the rule's numbers, required with draws.  weight fp32 [V, H].  with_targets: also produce target_ids and
+    mlm_mask (MASKED_LANGUAGE_MODELING configured on).  position [max_pos, H], token_type [types, H], ln_weight / ln_bias [H], eps:
+    the ADD_POSITION_EMBEDDING path, dropout(LayerNorm((W[id] + Tt[type]) + P[j])); keep: optional uint8 [N, H] keep mask drawn by
+    the caller, kept values are multiplied by 1 / (1 - p_drop).
+
+    Returns (ints int64 [4 | 6, N], input_embeddings [N, H], encoded_tokens [N, H] or None without the position path).
+    Differentiable in `weight` only (locov_caption_embed_bwd: no atomics, bitwise reproducible).  N > CAPTION_MAX_TOKENS or
+    H > CAPTION_MAX_HIDDEN raises LocovError (LOCOV_ERR_UNSUPPORTED): a caller with a torch expression checks the limits first."""
+    packed = _dev(packed, "packed", torch.int32)
+    weight = _dev(weight, "weight")
+    if packed.dim() != 2 or packed.shape[0] != 4 or weight.dim() != 2:
+        raise ValueError("caption_embed: packed must be [4, N] and weight [V, H]")
+    N, (V, H) = packed.shape[1], weight.shape
+    if T < 1 or N % T:
+        raise ValueError(f"caption_embed: N = {N} tokens is not a multiple of T = {T}")
+    if draws is not None:
+        draws = _dev(draws, "draws", torch.float64)
+        if tuple(draws.shape) != (2, N) or mlm is None or not with_targets:
+            raise ValueError(f"caption_embed: draws must be [2, {N}] and come with `mlm` and with_targets")
+        if not (0 <= mlm.mask_id < V and 1 <= mlm.len_tok <= V):
+            raise ValueError(f"caption_embed: mask_id {mlm.mask_id} / len(tokenizer) {mlm.len_tok} outside the {V}-row word table")
+    ln = (position, token_type, ln_weight, ln_bias)
+    if any(t is not None for t in ln):
+        if any(t is None for t in ln):
+            raise ValueError("caption_embed: the position path needs position, token_type, ln_weight and ln_bias")
+        position, token_type, ln_weight, ln_bias = (_dev(t.detach(), n) for t, n in zip(ln, ("position", "token_type", "ln_weight", "ln_bias")))
+        if position.dim() != 2 or token_type.dim() != 2 or position.shape[1] != H or token_type.shape[1] != H or \
+                tuple(ln_weight.shape) != (H,) or tuple(ln_bias.shape) != (H,) or position.shape[0] < T:
+            raise ValueError(f"caption_embed: position [>= {T}, {H}], token_type [types, {H}], ln_weight / ln_bias [{H}] expected")
+        if keep is not None:
+            keep = _dev(keep, "keep", torch.uint8)
+            if keep.numel() != N * H or not 0.0 <= p_drop < 1.0:
+                raise ValueError(f"caption_embed: keep must hold {N} x {H} values and p_drop lie in [0, 1)")
+    elif keep is not None:
+        raise ValueError("caption_embed: keep without the position path")
+    return _CaptionEmbedFn.apply(weight, packed, draws, int(T), mlm, 6 if with_targets else 4, position, token_type, ln_weight, ln_bias,
+                                 float(eps), keep, float(p_drop))
