@@ -64,15 +64,44 @@ def scatter(ids, g, V, dtype=np.float32):
     return dW
 
 
-def make_case(B, T, H, V, seed, p_noise=0.05):
+OPERANDS = ("W", "P", "Tt", "gamma", "beta", "keep")        # what make_case's `misalign` may name
+
+
+def offset_view(a, offset):
+    """A contiguous copy of `a` that starts `offset` bytes past a 16-byte boundary of a larger allocation."""
+    buf = np.empty(a.nbytes + 32, dtype=np.uint8)
+    start = (-buf.ctypes.data) % 16 + offset
+    v = buf[start:start + a.nbytes].view(a.dtype).reshape(a.shape)
+    v[...] = a
+    return v
+
+
+def make_case(B, T, H, V, seed, p_noise=0.05, plant_ids=(), pad_ids="zero", misalign=()):
     """Tokens with heavy duplication (padding id 0 on the last third of every caption, one word ten times when there is room),
-    [CLS] / [SEP] specials, and draws that contain the boundary values; tables for the LayerNorm path."""
+    [CLS] / [SEP] specials, and draws that contain the boundary values; tables for the LayerNorm path.
+
+    The options leave the default case as it is, bit for bit (none of them draws from the generator):
+      plant_ids   vocabulary ids forced onto body tokens, from the last body token backwards, tokens that the masked-language-
+                  modelling rule never selects (draw >= p) first: those keep their id through the rule.  Their positions come back
+                  as "plant_pos".
+      pad_ids     "zero": as above.  "spread": every id that the layout repeats -- the padding, [CLS], [SEP] -- cycles through a
+                  block reserved at the top of the vocabulary and the repeated word appears eight times, so that no id of the
+                  tokenizer's output occurs more than 8 times unless the random body ids collide that often.
+      misalign    names out of OPERANDS: each is a contiguous view that starts 4 bytes (`keep`: 1 byte) past a 16-byte boundary."""
+    assert pad_ids in ("zero", "spread") and set(misalign) <= set(OPERANDS)
     rng = np.random.default_rng(seed)
-    ids = rng.integers(5, V, size=(B, T))
     pad_from = T - T // 3
-    ids[:, 0], ids[:, pad_from - 1], ids[:, pad_from:] = 2, 3, 0
+    spread = pad_ids == "spread"
+    laid_out = B * (T - pad_from + 2)                        # padded positions, [CLS], [SEP]
+    reserved = -(-laid_out // 8) if spread else 0
+    ids = rng.integers(5, V - reserved, size=(B, T))
+    if spread:
+        block = (V - reserved + np.arange(laid_out) % reserved).reshape(B, T - pad_from + 2)
+        ids[:, 0], ids[:, pad_from - 1], ids[:, pad_from:] = block[:, 0], block[:, 1], block[:, 2:]
+    else:
+        ids[:, 0], ids[:, pad_from - 1], ids[:, pad_from:] = 2, 3, 0
     body = [(i, j) for i in range(B) for j in range(1, pad_from - 1)]
-    for i, j in (body[::2][:10] if len(body) >= 20 else body[2:]):      # (21 tokens hold no ten free words: all but two of them)
+    for i, j in (body[::2][:8 if spread else 10] if len(body) >= 20 else body[2:]):      # (21 tokens hold no ten free words: all but two of them)
         ids[i, j] = 7
     attn = np.ones((B, T), dtype=np.int64)
     attn[:, pad_from:] = 0
@@ -92,8 +121,17 @@ def make_case(B, T, H, V, seed, p_noise=0.05):
               "Tt": (rng.standard_normal((2, H)) * scale).astype(np.float32), "gamma": (1 + 0.2 * rng.standard_normal(H)).astype(np.float32),
               "beta": (0.1 * rng.standard_normal(H)).astype(np.float32)}
     keep = (rng.random((B, T, H)) >= 0.1).astype(np.uint8)
-    return {"ids": ids, "types": types, "attn": attn, "special": special, "draws": draws, "keep": keep, "p_noise": p_noise, "mask_id": 4,
+    case = {"ids": ids, "types": types, "attn": attn, "special": special, "draws": draws, "keep": keep, "p_noise": p_noise, "mask_id": 4,
             "len_tok": V - 2, "eps": 1e-12, "p_drop": 0.1, **tables}
+    if len(plant_ids):
+        assert len(plant_ids) <= len(body) and all(0 <= v < V for v in plant_ids)
+        spots = sorted(reversed(body), key=lambda ij: draws[0][ij] < P)[:len(plant_ids)]      # (stable: never selected first)
+        for (i, j), v in zip(spots, plant_ids):
+            ids[i, j] = v
+        case["plant_pos"] = np.array(spots, dtype=np.int64)
+    for name in misalign:
+        case[name] = offset_view(case[name], 1 if name == "keep" else 4)
+    return case
 
 
 def boundary_draws():
