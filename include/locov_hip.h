@@ -38,7 +38,8 @@ extern "C" {
  *    locov_grounding_triplet_fwd / _bwd, locov_mha_fwd / _bwd, locov_rpn_proposals (+ _workspace_bytes),
  *    locov_rpn_label_anchors (+ _workspace_bytes), locov_rpn_sample_anchors, locov_rpn_loss (+ _workspace_bytes),
  *    locov_resnet_stem_fwd, locov_resnet_stem_fwd_sel, locov_resnet_stem_wgrad (+ _workspace_bytes),
- *    locov_preprocess_images, locov_detector_rescale, locov_sgd_step (+ _workspace_bytes) */
+ *    locov_preprocess_images, locov_detector_rescale, locov_sgd_step (+ _workspace_bytes),
+ *    locov_coco_match (+ _workspace_bytes), locov_coco_accumulate */
 #define LOCOV_ABI_VERSION 8
 
 #define LOCOV_OK 0
@@ -1422,6 +1423,68 @@ int64_t locov_sgd_workspace_bytes(int n_tensors, int64_t total_chunks);
 int locov_sgd_step(const void *table, int n_tensors, int64_t total_chunks, const float *lr_host, const float *wd_host, int n_classes,
                    float momentum, double dampening, int nesterov, int clip_type, float clip_value, void *workspace,
                    int64_t workspace_bytes, locov_stream_t stream);
+
+/* ---- COCO-protocol box evaluation (csrc/coco_eval.hip): the public COCOeval, iouType "bbox", useCats 1 --------------------------
+ * (what ovr/evaluation/custom_coco_eval.py:29 sits on).  Added under ABI version 8.  fp64 and integers only, each step rounded on
+ * its own: the outputs equal the numpy definition in locov_amd/evaluation.py bit for bit, and two calls give the same bits.
+ *
+ * A CELL is one (image, category) pair; cells are numbered category-major (cell = category * n_images + image rank), so a
+ * category's cells and dets are contiguous.  Both entry points only enqueue work; nothing is read by the host.
+ *
+ * locov_coco_match: greedy matching of every cell's dets to its gts, for every area range and IoU threshold.
+ *   det_offsets, gt_offsets : int32 [n_cells + 1], CSR.  The entry cannot read them: the kernel clamps every offset into
+ *                 [0, n_det] / [0, n_gt] and takes a descending pair as an empty cell, so no content can send it out of bounds.
+ *   det_boxes   : fp32 [n_det, 4] XYXY in cell order, a cell's dets in descending score (ties in input order).  Only the first
+ *                 max_det dets of a cell take part; the bits of the others are written as 0 (the accumulation never counts them:
+ *                 their in-cell rank is above every cap).  XYWH is formed in fp32 (w = x2 - x1), then widened; area = w * h.
+ *   gt_boxes    : fp64 [n_gt, 4] XYWH, gt_area fp64 [n_gt] (the annotation's own field), gt_crowd uint8 [n_gt], in cell order.
+ *   area_ranges_host : n_areas (1 .. LOCOV_COCO_MAX_AREAS) pairs lo, hi;  iou_thresholds_host : n_thresholds (1 ..
+ *                 LOCOV_COCO_MAX_THRESHOLDS) doubles.  They travel as kernel arguments.
+ *   IoU (double): w = min(dx + dw, gx + gw) - max(dx, gx), h likewise; 0 if w <= 0 or h <= 0; else i = w * h,
+ *                 u = crowd ? dw * dh : dw * dh + gw * gh - i;  IoU = i / u.
+ *   Per (range a, threshold t), the dets in order: best = min(t, 1 - 1e-10); over the gts not ignored in a (ignored = crowd or
+ *                 area outside [lo, hi]) and not yet matched at (a, t), in order, a gt with IoU >= best is taken and raises best
+ *                 (equal IoU moves to the later gt); if none was taken, the same over the ignored gts, where a matched crowd gt can
+ *                 be taken again.  The det takes the gt's ignore flag; an unmatched det with its area outside [lo, hi] is ignored.
+ *   det_bits    : out uint8 [n_det, n_areas * n_thresholds]: bit 0 matched, bit 1 ignored.
+ *   gt_ignore   : out uint8 [n_areas, n_gt].
+ *   workspace   : locov_coco_match_workspace_bytes(n_gt, max_det) bytes, 8-byte aligned (needed when n_det > 0 and n_gt > 0): a
+ *                 cell whose IoU matrix and matched flags exceed its 8 KiB of LDS keeps them there, at a slot given by its gt offset.
+ *   max_det > LOCOV_COCO_MAX_DET or n_cells > 4 * LOCOV_COCO_MAX_BLOCKS: LOCOV_ERR_UNSUPPORTED.  n_cells == 0 or no det and no gt:
+ *   LOCOV_OK, nothing launched.  A null pointer, a negative count, max_det < 1, a range with lo > hi, list lengths outside their
+ *   limits, a small workspace: LOCOV_ERR_INVALID_ARG before any HIP call.
+ *
+ * locov_coco_accumulate: precision / recall / scores per (threshold, category, range, cap).
+ *   cat_offsets : int32 [n_categories + 1] into the three acc_* arrays (clamped like the offsets above).
+ *   acc_index, acc_rank, acc_score : per det, in (category, descending score, image rank, in-cell rank) order: its row of det_bits,
+ *                 its in-cell rank, its score (fp64).  A det counts under cap m when acc_rank < max_dets_host[m].
+ *   npig        : int32 [n_categories, n_areas]: the category's gts not ignored in the range.
+ *   max_dets_host : 1 .. LOCOV_COCO_MAX_CAPS positive ascending caps;  recall_thresholds_host : 1 ..
+ *                 LOCOV_COCO_MAX_RECALL_THRESHOLDS ascending doubles.
+ *   Over the counted dets: tp / fp = running counts of the not-ignored matched / unmatched dets; rc = tp / npig;
+ *                 pr = tp / (fp + tp + 2^-52), made non-increasing from the right; for recall threshold r the first det with
+ *                 rc >= r gives precision and score, 0 once none does.  recall = the last rc, 0 with no det.
+ *   precision, scores : out fp64 [T, R, K, A, M] (scores may be null);  recall : out fp64 [T, K, A, M].  Every element is written;
+ *                 -1 where npig == 0.
+ *   One workgroup per (category, range, cap, threshold) walks the category's dets in chunks with integer carries and a running
+ *   maximum: no atomics.  More than LOCOV_COCO_MAX_BLOCKS workgroups: LOCOV_ERR_UNSUPPORTED.  n_categories == 0: LOCOV_OK.
+ *   A null pointer, a negative count, more than LOCOV_COCO_MAX_CAPS caps, caps or recall thresholds not ascending:
+ *   LOCOV_ERR_INVALID_ARG before any HIP call. */
+#define LOCOV_COCO_MAX_AREAS 4
+#define LOCOV_COCO_MAX_THRESHOLDS 16
+#define LOCOV_COCO_MAX_CAPS 3
+#define LOCOV_COCO_MAX_RECALL_THRESHOLDS 256
+#define LOCOV_COCO_MAX_DET 4096
+#define LOCOV_COCO_MAX_BLOCKS 8388608
+int64_t locov_coco_match_workspace_bytes(int n_gt, int max_det);
+int locov_coco_match(const int *det_offsets, const int *gt_offsets, int64_t n_cells, int n_det, int n_gt, int max_det,
+                     const float *det_boxes, const double *gt_boxes, const double *gt_area, const uint8_t *gt_crowd,
+                     const double *area_ranges_host, int n_areas, const double *iou_thresholds_host, int n_thresholds,
+                     uint8_t *det_bits, uint8_t *gt_ignore, void *workspace, int64_t workspace_bytes, locov_stream_t stream);
+int locov_coco_accumulate(const int *cat_offsets, int n_categories, const int *acc_index, const int *acc_rank,
+                          const double *acc_score, int n_det, const uint8_t *det_bits, const int *npig, int n_areas,
+                          int n_thresholds, const int *max_dets_host, int n_max_dets, const double *recall_thresholds_host,
+                          int n_recall_thresholds, double *precision, double *recall, double *scores, locov_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -43,6 +43,8 @@ MHA_MAX_S, MHA_MAX_GRID, MHA_HEAD_DIMS = 4096, 65535, (32, 64, 96, 128)
 CAPTION_MAX_TOKENS, CAPTION_MAX_HIDDEN = 8192, 4096
 SGD_MAX_CLASSES, SGD_CHUNK, SGD_RECORD_BYTES = 8, 4096, 48
 SGD_CLIP_NONE, SGD_CLIP_VALUE, SGD_CLIP_NORM = 0, 1, 2
+COCO_MAX_AREAS, COCO_MAX_THRESHOLDS, COCO_MAX_CAPS, COCO_MAX_RECALL_THRESHOLDS = 4, 16, 3, 256
+COCO_MAX_DET, COCO_MAX_BLOCKS = 4096, 8388608
 
 _p = c_void_p  # device pointer
 
@@ -234,6 +236,11 @@ SIGNATURES = {
     "locov_sgd_workspace_bytes": (c_int64, [c_int, c_int64]),
     "locov_sgd_step": (c_int, [_p, c_int, c_int64, POINTER(c_float), POINTER(c_float), c_int, c_float, c_double, c_int, c_int, c_float,
                                _p, c_int64, _p]),
+    "locov_coco_match_workspace_bytes": (c_int64, [c_int, c_int]),
+    "locov_coco_match": (c_int, [_p, _p, c_int64, c_int, c_int, c_int, _p, _p, _p, _p, POINTER(c_double), c_int, POINTER(c_double), c_int,
+                                 _p, _p, _p, c_int64, _p]),
+    "locov_coco_accumulate": (c_int, [_p, c_int, _p, _p, _p, c_int, _p, _p, c_int, c_int, POINTER(c_int), c_int, POINTER(c_double), c_int,
+                                      _p, _p, _p, _p]),
 }
 
 _lib = None

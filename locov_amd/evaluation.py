@@ -1,0 +1,382 @@
+"""COCO-protocol bounding-box AP with seen / unseen AP50 (the reference's CustomCOCOEvaluator, ovr/evaluation/custom_coco_eval.py,
+and the public COCOeval with iouType="bbox", useCats=1 it sits on), without pycocotools.
+
+The protocol, as every path below computes it (float64 and integers only, so the paths agree bit for bit):
+
+  * Parameters: iouThrs = linspace(.5, .95, 10), recThrs = linspace(0, 1, 101), maxDets = (1, 10, 100) (any ascending tuple of
+    1-3 caps), areaRng = [0, 1e10], [0, 32^2], [32^2, 96^2], [96^2, 1e10].  Images in ascending image id, categories in ascending
+    category id; contiguous class c is the c-th smallest category id.
+  * Ground truth: bbox XYWH as float64, area = the annotation's own field, ignore = iscrowd.
+  * Detections: fp32 XYXY boxes; XYWH is formed in fp32 (w = x2 - x1, as BoxMode.convert does on the fp32 array), then widened;
+    area = w * h in double; scores widened to double.
+  * Per (image, category) cell with a gt or a det: the dets stable-sorted by descending score, the first maxDets[-1] kept; IoU in
+    double, each step rounded on its own: w = min(dx + dw, gx + gw) - max(dx, gx), h likewise, 0 if w <= 0 or h <= 0, else
+    i = w * h, u = crowd ? dw * dh : dw * dh + gw * gh - i, IoU = i / u.
+  * Per area range a gt is ignored if it is crowd or its area is outside [lo, hi]; gts are visited non-ignored first (stable).
+  * Per threshold t, the dets in order: best = min(t, 1 - 1e-10), m = none; a gt already matched at t and not crowd is skipped; the
+    walk stops when m is a non-ignored gt and the next is ignored; a gt with iou >= best becomes m and raises best (equal IoU moves
+    to the later gt).  A matched det takes m's ignore flag and marks m; an unmatched det whose own area is outside the range is
+    ignored.  (Done here as two passes: the non-ignored gts, then the ignored ones only if the first pass found nothing.)
+  * Per (category, range, cap m): each cell's first m dets, concatenated in image order and stable-sorted by descending score;
+    npig = the category's non-ignored gts in the range (0: precision, recall and scores stay -1); tp / fp = cumulative counts of
+    the non-ignored matched / unmatched dets; rc = tp / npig; pr = tp / (fp + tp + spacing(1)); recall = the last rc (0 with no
+    det); pr made non-increasing from the right; for each recThrs[r] the first index with rc >= recThrs[r] gives precision and
+    score, 0 for this and every later r once the index runs off the end.
+  * The twelve stats (means over the entries > -1, -1 with none, taken with numpy on the host): AP, AP at iouThrs[0] and [5], AP
+    small / medium / large, AR at each cap (-1 for a cap that is not configured), AR small / medium / large.
+  * Results: the six AP metrics x 100 (nan for -1), AP-<name> per category, and AP50-seen / AP50-unseen: plain means of the
+    per-category AP50 x 100 over `seen_names` / `unseen_names` (the reference imports those lists from a file it does not ship;
+    nan for an empty list).
+
+Paths: the numpy functions of this file are the definition; they serve CPU tensors, LOCOV_FUSED_COCOEVAL=0 (A/B runs, like
+LOCOV_FUSED_ATTENTION) and sizes beyond the kernels' limits.  Device tensors take ops.coco_order / coco_match / coco_accumulate
+(csrc/coco_eval.hip) with one device-to-host copy, of the result arrays.  The evaluator scores what its own process saw.
+"""
+from __future__ import annotations
+
+import json
+import os
+from collections import OrderedDict
+from typing import Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import _lib
+
+__all__ = ["COCOEvaluator", "inference_on_dataset", "IOU_THRS", "REC_THRS", "AREA_RNG"]
+
+IOU_THRS = np.linspace(.5, .95, 10)
+REC_THRS = np.linspace(0., 1., 101)
+AREA_RNG = np.array([[0., 1e10], [0., 32. ** 2], [32. ** 2, 96. ** 2], [96. ** 2, 1e10]], dtype=np.float64)
+METRICS = ("AP", "AP50", "AP75", "APs", "APm", "APl")
+
+
+def _fused() -> bool:
+    return os.environ.get("LOCOV_FUSED_COCOEVAL", "1") != "0"
+
+
+class _GroundTruth:
+    """The annotations in cell order (cell = category rank * n_images + image rank; inside a cell, dataset order)."""
+
+    def __init__(self, gt):
+        if isinstance(gt, (str, os.PathLike)):
+            with open(gt) as f:
+                gt = json.load(f)
+        cats = sorted(gt["categories"], key=lambda c: c["id"])
+        self.cat_ids = [c["id"] for c in cats]
+        self.cat_names = [c.get("name", str(c["id"])) for c in cats]
+        self.image_ids = sorted({im["id"] for im in gt["images"]})
+        self.image_rank = {iid: r for r, iid in enumerate(self.image_ids)}
+        cat_rank = {cid: r for r, cid in enumerate(self.cat_ids)}
+        I, K = len(self.image_ids), len(self.cat_ids)
+        anns = [a for a in gt.get("annotations", ()) if a["image_id"] in self.image_rank and a["category_id"] in cat_rank]
+        cell = np.array([cat_rank[a["category_id"]] * I + self.image_rank[a["image_id"]] for a in anns], dtype=np.int64)
+        order = np.argsort(cell, kind="stable")
+        self.n_images, self.n_categories, self.n_cells = I, K, I * K
+        self.box = np.array([anns[i]["bbox"] for i in order], dtype=np.float64).reshape(-1, 4)
+        self.area = np.array([anns[i]["area"] for i in order], dtype=np.float64)
+        self.crowd = np.array([1 if anns[i].get("iscrowd", 0) else 0 for i in order], dtype=np.uint8)
+        cell = cell[order]
+        self.offsets = np.searchsorted(cell, np.arange(I * K + 1, dtype=np.int64), side="left").astype(np.int32)
+        self.cat_offsets = self.offsets[::I].astype(np.int64) if I else np.zeros(K + 1, dtype=np.int64)   # [K + 1]
+        self._device = {}
+
+    def on(self, device):
+        """The device copies of the arrays, made once per device."""
+        d = self._device.get(device)
+        if d is None:
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
+            d = self._device[device] = dict(box=up(self.box), area=up(self.area), crowd=up(self.crowd), offsets=up(self.offsets),
+                                            cat_offsets=up(self.cat_offsets))
+        return d
+
+
+# ---- the host path: numpy, float64; the definition ------------------------------------------------------------------------------
+def order_host(img_rank, cls, score, n_images, n_categories):
+    """The two orderings of the dets.  Cell order: (cell, descending score, input order); accumulate order: (category, descending
+    score, image rank, in-cell rank).  A class outside [0, K) goes to a trailing cell nothing reads.
+    -> perm (input index per cell-order slot), det_offsets int32 [C + 1], rank (in-cell), acc_index (cell-order slot per
+    accumulate-order slot), cat_offsets int32 [K + 1]."""
+    I, K = n_images, n_categories
+    C = I * K
+    cell = np.where((cls >= 0) & (cls < K), cls * I + img_rank, C).astype(np.int64)
+    p1 = np.argsort(-score, kind="stable")
+    perm = p1[np.argsort(cell[p1], kind="stable")]
+    cell = cell[perm]
+    det_offsets = np.searchsorted(cell, np.arange(C + 1, dtype=np.int64), side="left").astype(np.int32)
+    rank = (np.arange(len(cell), dtype=np.int64) - det_offsets[cell]).astype(np.int32)
+    pa = np.argsort(-score[perm], kind="stable")
+    cat = np.minimum(cell // max(I, 1), K)
+    acc_index = pa[np.argsort(cat[pa], kind="stable")].astype(np.int32)
+    cat_offsets = np.searchsorted(cat[acc_index], np.arange(K + 1, dtype=np.int64), side="left").astype(np.int32)
+    return perm, det_offsets, rank, acc_index, cat_offsets
+
+
+def match_host(gt: _GroundTruth, det_offsets, boxes, max_det, area_rng=AREA_RNG, iou_thrs=IOU_THRS):
+    """boxes: fp32 XYXY in cell order.  -> det_bits uint8 [N, A * T] (bit 0 matched, bit 1 ignored), gt_ignore uint8 [A, G]."""
+    A, T = len(area_rng), len(iou_thrs)
+    lo, hi = area_rng[:, 0], area_rng[:, 1]
+    boxes = np.asarray(boxes, dtype=np.float32).reshape(-1, 4)
+    dw = (boxes[:, 2] - boxes[:, 0]).astype(np.float64)                       # fp32 differences, then widened
+    dh = (boxes[:, 3] - boxes[:, 1]).astype(np.float64)
+    dx, dy = boxes[:, 0].astype(np.float64), boxes[:, 1].astype(np.float64)
+    darea = dw * dh
+    gt_ignore = ((gt.crowd[None, :] != 0) | (gt.area[None, :] < lo[:, None]) | (gt.area[None, :] > hi[:, None]))
+    det_out = (darea[:, None] < lo[None, :]) | (darea[:, None] > hi[None, :])                 # [N, A]
+    bits = np.repeat(det_out.astype(np.uint8) * 2, T, axis=1)                                 # an unmatched det: ignored by its area
+    counts = np.diff(det_offsets.astype(np.int64))
+    n_listed = int(det_offsets[-1])                                                            # (the rest: classes outside the bank)
+    in_cell = np.arange(n_listed, dtype=np.int64) - np.repeat(det_offsets[:-1].astype(np.int64), counts)
+    bits[:n_listed][in_cell >= max_det] = 0                                                    # past the cap: no part, bits 0
+    start = np.minimum(iou_thrs, 1 - 1e-10)
+    gcount = np.diff(gt.offsets.astype(np.int64))
+    for c in np.nonzero((counts > 0) & (gcount > 0))[0]:
+        d0, g0, G = int(det_offsets[c]), int(gt.offsets[c]), int(gcount[c])
+        D = min(int(counts[c]), max_det)
+        gb, crowd = gt.box[g0:g0 + G], gt.crowd[g0:g0 + G] != 0
+        sl = slice(d0, d0 + D)
+        w = np.minimum((dx[sl] + dw[sl])[:, None], (gb[:, 0] + gb[:, 2])[None, :]) - np.maximum(dx[sl][:, None], gb[None, :, 0])
+        h = np.minimum((dy[sl] + dh[sl])[:, None], (gb[:, 1] + gb[:, 3])[None, :]) - np.maximum(dy[sl][:, None], gb[None, :, 1])
+        inter = w * h
+        da = np.broadcast_to(darea[sl][:, None], inter.shape)
+        union = np.where(crowd[None, :], da, da + (gb[:, 2] * gb[:, 3])[None, :] - inter)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            iou = np.where((w > 0) & (h > 0), inter / union, 0.0)
+        gig = gt_ignore[:, g0:g0 + G]                                                          # [A, G]
+        gtm = np.zeros((A, T, G), dtype=bool)
+        ai, ti = np.meshgrid(np.arange(A), np.arange(T), indexing="ij")
+        for d in range(D):
+            best = np.broadcast_to(start[None, :], (A, T)).copy()
+            m = np.full((A, T), -1, dtype=np.int64)
+            for g in range(G):                                                                 # the gts not ignored in the range
+                ok = ~gig[:, g, None] & ~gtm[:, :, g] & (iou[d, g] >= best)
+                best[ok] = iou[d, g]
+                m[ok] = g
+            second = m < 0
+            for g in range(G):                                                                 # nothing there: the ignored gts
+                ok = second & gig[:, g, None] & ~(gtm[:, :, g] & ~crowd[g]) & (iou[d, g] >= best)
+                best[ok] = iou[d, g]
+                m[ok] = g
+            matched = m >= 0
+            gtm[ai[matched], ti[matched], m[matched]] = True
+            ign = np.where(matched, second, det_out[d0 + d][:, None])
+            bits[d0 + d] = (matched.astype(np.uint8) | (ign.astype(np.uint8) << 1)).reshape(-1)
+    return bits, gt_ignore.astype(np.uint8)
+
+
+def npig_host(gt: _GroundTruth, gt_ignore):
+    """int32 [K, A]: the category's gts that are not ignored in the range."""
+    c = np.concatenate([np.zeros((gt_ignore.shape[0], 1), dtype=np.int64), np.cumsum(gt_ignore == 0, axis=1)], axis=1)
+    return (c[:, gt.cat_offsets[1:]] - c[:, gt.cat_offsets[:-1]]).T.astype(np.int32)
+
+
+def accumulate_host(cat_offsets, acc_index, acc_rank, acc_score, det_bits, npig, max_dets, n_thresholds, rec_thrs=REC_THRS):
+    """-> precision [T, R, K, A, M], recall [T, K, A, M], scores [T, R, K, A, M]; acc_rank / acc_score in accumulate order."""
+    K, A = npig.shape
+    T, R, M = n_thresholds, len(rec_thrs), len(max_dets)
+    precision = -np.ones((T, R, K, A, M))
+    recall = -np.ones((T, K, A, M))
+    scores = -np.ones((T, R, K, A, M))
+    for k in range(K):
+        n0, n1 = int(cat_offsets[k]), int(cat_offsets[k + 1])
+        if not npig[k].any():
+            continue
+        for m, cap in enumerate(max_dets):
+            sel = np.nonzero(acc_rank[n0:n1] < cap)[0] + n0
+            b = det_bits[acc_index[sel]].reshape(len(sel), A, T)
+            sc = acc_score[sel]
+            tps = np.cumsum(b == 1, axis=0).astype(np.float64)
+            fps = np.cumsum(b == 0, axis=0).astype(np.float64)
+            nd = len(sel)
+            for a in range(A):
+                if npig[k, a] == 0:
+                    continue
+                rc = tps[:, a] / int(npig[k, a])
+                pr = tps[:, a] / (fps[:, a] + tps[:, a] + np.spacing(1))
+                recall[:, k, a, m] = rc[-1] if nd else 0
+                pr = np.maximum.accumulate(pr[::-1], axis=0)[::-1]
+                for t in range(T):
+                    inds = np.searchsorted(rc[:, t], rec_thrs, side="left")
+                    ok = inds < nd
+                    q, ss = np.zeros(R), np.zeros(R)
+                    q[ok] = pr[inds[ok], t]
+                    ss[ok] = sc[inds[ok]]
+                    precision[t, :, k, a, m] = q
+                    scores[t, :, k, a, m] = ss
+    return precision, recall, scores
+
+
+def summarize(precision, recall):
+    """COCOeval.summarize's twelve numbers.  AP and the area ARs use the last cap; a cap that is not configured gives -1."""
+    M = precision.shape[-1]
+
+    def mean(s):
+        s = s[s > -1]
+        return -1.0 if s.size == 0 else float(np.mean(s))
+
+    stats = np.full(12, -1.0)
+    stats[0] = mean(precision[:, :, :, 0, M - 1])
+    stats[1] = mean(precision[0, :, :, 0, M - 1])
+    if precision.shape[0] > 5:
+        stats[2] = mean(precision[5, :, :, 0, M - 1])
+    for i in range(1, min(4, precision.shape[3])):
+        stats[2 + i] = mean(precision[:, :, :, i, M - 1])
+        stats[8 + i] = mean(recall[:, :, i, M - 1])
+    for m in range(M):
+        stats[6 + m] = mean(recall[:, :, 0, m])
+    return stats
+
+
+def derive_results(ev, class_names, seen_names=(), unseen_names=()):
+    """CustomCOCOEvaluator._derive_coco_results (custom_coco_eval.py:30-137) on {"precision", "stats"}; ev None: nothing was processed."""
+    if ev is None:
+        return {metric: float("nan") for metric in METRICS}
+    stats = ev["stats"]
+    results = {metric: float(stats[i] * 100 if stats[i] >= 0 else "nan") for i, metric in enumerate(METRICS)}
+    if class_names is None or len(class_names) <= 1:
+        return results
+    precisions = ev["precision"]
+    assert len(class_names) == precisions.shape[2], "one class name per category"
+    seen, unseen = set(seen_names), set(unseen_names)
+    per_cat, ap50_seen, ap50_unseen = [], [], []
+    for idx, name in enumerate(class_names):
+        p = precisions[:, :, idx, 0, -1]
+        p = p[p > -1]
+        per_cat.append((str(name), float(np.mean(p) * 100) if p.size else float("nan")))
+        p50 = precisions[0, :, idx, 0, -1]
+        p50 = p50[p50 > -1]
+        ap50 = float(np.mean(p50) * 100) if p50.size else float("nan")
+        if name in seen:
+            ap50_seen.append(ap50)
+        if name in unseen:
+            ap50_unseen.append(ap50)
+    results.update({"AP-" + name: ap for name, ap in per_cat})
+    results["AP50-seen"] = sum(ap50_seen) / len(ap50_seen) if ap50_seen else float("nan")
+    results["AP50-unseen"] = sum(ap50_unseen) / len(ap50_unseen) if ap50_unseen else float("nan")
+    return results
+
+
+def evaluate_host(gt: _GroundTruth, img_rank, cls, score, boxes, max_dets):
+    """The whole protocol on numpy arrays -> {"precision", "recall", "scores", "stats"}."""
+    img_rank, cls = np.asarray(img_rank, dtype=np.int64), np.asarray(cls, dtype=np.int64)
+    score = np.asarray(score).astype(np.float64)
+    boxes = np.asarray(boxes, dtype=np.float32).reshape(-1, 4)
+    perm, det_offsets, rank, acc_index, cat_offsets = order_host(img_rank, cls, score, gt.n_images, gt.n_categories)
+    bits, gt_ignore = match_host(gt, det_offsets, boxes[perm], max_dets[-1])
+    score_c = score[perm]
+    precision, recall, scores = accumulate_host(cat_offsets, acc_index, rank[acc_index], score_c[acc_index], bits,
+                                                npig_host(gt, gt_ignore), max_dets, len(IOU_THRS))
+    return dict(precision=precision, recall=recall, scores=scores, stats=summarize(precision, recall))
+
+
+# ---- the device path ------------------------------------------------------------------------------------------------------------
+def device_supported(gt: _GroundTruth, n_det: int, max_dets) -> bool:
+    """Sizes inside the kernels' stated limits (beyond them locov_coco_* answer LOCOV_ERR_UNSUPPORTED: the host path is taken)."""
+    blocks = gt.n_categories * len(AREA_RNG) * len(max_dets) * len(IOU_THRS)
+    return (max_dets[-1] <= _lib.COCO_MAX_DET and gt.n_cells <= 4 * _lib.COCO_MAX_BLOCKS and blocks <= _lib.COCO_MAX_BLOCKS
+            and n_det < 2 ** 31 - 1 and len(gt.area) < 2 ** 31 - 1 and gt.n_cells > 0)
+
+
+def evaluate_device(gt: _GroundTruth, img_rank, cls, score, boxes, max_dets):
+    """The same on device tensors: orderings by stable integer sorts, two kernel launches, one copy to the host."""
+    from . import ops
+    g = gt.on(boxes.device)
+    K, A, T, R, M = gt.n_categories, len(AREA_RNG), len(IOU_THRS), len(REC_THRS), len(max_dets)
+    o = ops.coco_order(img_rank, cls, score, boxes, gt.n_images, K)
+    bits, gt_ignore = ops.coco_match(o.det_offsets, g["offsets"], o.boxes, g["box"], g["area"], g["crowd"], AREA_RNG, IOU_THRS,
+                                     max_dets[-1])
+    c = torch.cat([torch.zeros((A, 1), dtype=torch.int64, device=boxes.device), torch.cumsum(gt_ignore == 0, dim=1)], dim=1)
+    npig = (c[:, g["cat_offsets"][1:]] - c[:, g["cat_offsets"][:-1]]).t().contiguous().to(torch.int32)
+    flat = ops.coco_accumulate(o.cat_offsets, o.acc_index, o.acc_rank, o.acc_score, bits, npig, T, max_dets, REC_THRS)
+    host = flat.cpu().numpy()                                                  # the one device-to-host copy
+    n = T * R * K * A * M
+    precision, scores = host[:n].reshape(T, R, K, A, M), host[n:2 * n].reshape(T, R, K, A, M)
+    recall = host[2 * n:].reshape(T, K, A, M)
+    return dict(precision=precision, recall=recall, scores=scores, stats=summarize(precision, recall))
+
+
+class COCOEvaluator:
+    """Box AP under the COCO protocol (module docstring), with the reference's AP50-seen / AP50-unseen.
+
+    gt: a COCO-format dict or the path of its JSON (images, annotations, categories).  class_names: one name per category in
+    ascending category id (default: the categories' own names).  seen_names / unseen_names: the two lists the reference imports
+    from its dataset file.  max_dets: an ascending tuple of 1-3 caps.  device: where evaluate() runs (default: where the
+    processed tensors are)."""
+
+    def __init__(self, gt, class_names: Optional[Sequence[str]] = None, seen_names: Sequence[str] = (), unseen_names: Sequence[str] = (),
+                 max_dets: Sequence[int] = (1, 10, 100), device=None):
+        max_dets = tuple(int(m) for m in max_dets)
+        if not 1 <= len(max_dets) <= 3 or max_dets[0] < 1 or any(b <= a for a, b in zip(max_dets, max_dets[1:])):
+            raise ValueError(f"max_dets must be an ascending tuple of 1-3 positive caps, got {max_dets}")
+        self._gt = gt if isinstance(gt, _GroundTruth) else _GroundTruth(gt)
+        self._class_names = list(class_names) if class_names is not None else list(self._gt.cat_names)
+        if len(self._class_names) != self._gt.n_categories:
+            raise ValueError(f"{len(self._class_names)} class names for {self._gt.n_categories} categories")
+        self._seen, self._unseen = tuple(seen_names), tuple(unseen_names)
+        self.max_dets = max_dets
+        self._device = torch.device(device) if device is not None else None
+        self.eval = None
+        self.reset()
+
+    def reset(self) -> None:
+        self._ranks, self._counts, self._boxes, self._scores, self._classes = [], [], [], [], []
+        self.eval = None
+
+    def process(self, inputs, outputs) -> None:
+        """inputs[i]["image_id"], outputs[i]["instances"] (pred_boxes XYXY, scores, pred_classes).  The tensors are kept where
+        they are; nothing is read to the host (the image id is host data)."""
+        for inp, out in zip(inputs, outputs):
+            if "instances" not in out:
+                continue
+            inst = out["instances"]
+            iid = inp["image_id"]
+            if iid not in self._gt.image_rank:
+                raise KeyError(f"image id {iid!r} is not in the ground truth")
+            boxes = inst.pred_boxes
+            boxes = boxes.tensor if hasattr(boxes, "tensor") else boxes
+            self._ranks.append(self._gt.image_rank[iid])
+            self._counts.append(int(boxes.shape[0]))
+            self._boxes.append(boxes.detach().reshape(-1, 4))
+            self._scores.append(inst.scores.detach().reshape(-1))
+            self._classes.append(inst.pred_classes.detach().reshape(-1))
+
+    def _gathered(self, device):
+        def cat(parts, dtype):
+            if len({(p.device, p.dtype) for p in parts}) == 1:             # one concatenation, then one move / conversion
+                return torch.cat(parts).to(device=device, dtype=dtype)
+            return torch.cat([p.to(device=device, dtype=dtype) for p in parts])
+
+        boxes, score, cls = cat(self._boxes, torch.float32), cat(self._scores, torch.float64), cat(self._classes, torch.int64)
+        img_rank = torch.from_numpy(np.repeat(np.asarray(self._ranks, dtype=np.int64), self._counts)).to(device)
+        return img_rank, cls, score, boxes
+
+    def evaluate(self):
+        n = sum(self._counts)
+        if n == 0:
+            self.eval = None
+            return OrderedDict(bbox=derive_results(None, self._class_names))
+        device = self._device or self._boxes[0].device
+        on_device = device.type == "cuda" and _fused() and device_supported(self._gt, n, self.max_dets)
+        img_rank, cls, score, boxes = self._gathered(device if on_device else torch.device("cpu"))
+        if on_device:
+            self.eval = evaluate_device(self._gt, img_rank, cls, score, boxes, self.max_dets)
+        else:
+            self.eval = evaluate_host(self._gt, img_rank.numpy(), cls.numpy(), score.numpy(), boxes.numpy(), self.max_dets)
+        return OrderedDict(bbox=derive_results(self.eval, self._class_names, self._seen, self._unseen))
+
+
+def inference_on_dataset(model, data_loader, evaluator):
+    """model.eval() under no_grad over the loader, evaluator.process per batch, then evaluator.evaluate(); the model's training
+    mode is restored on exit."""
+    was_training = model.training
+    evaluator.reset()
+    model.eval()
+    try:
+        with torch.no_grad():
+            for inputs in data_loader:
+                evaluator.process(inputs, model(inputs))
+    finally:
+        model.train(was_training)
+    results = evaluator.evaluate()
+    return results if results is not None else {}

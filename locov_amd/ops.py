@@ -2963,3 +2963,106 @@ def sgd_step(table: SgdTable, params: Sequence[torch.Tensor], grads: Sequence[to
         check(lib.locov_sgd_step(_ptr(table._device), n, chunks, (ctypes.c_float * c)(*lr), (ctypes.c_float * c)(*wd), c, float(momentum),
                                  float(dampening), int(bool(nesterov)), _SGD_CLIP[clip_type], float(clip_value), _ptr(ws), ws_bytes,
                                  _stream(params[0])), "locov_sgd_step")
+
+
+# --------------------------------------------------------------------------------------
+# COCO-protocol box evaluation (csrc/coco_eval.hip); composed by locov_amd/evaluation.py, whose docstring states the protocol.
+class CocoOrder(NamedTuple):
+    det_offsets: torch.Tensor   # int32 [C + 1]: each cell's dets in `boxes`
+    boxes: torch.Tensor         # fp32 [N, 4] XYXY in cell order (cell, descending score, input order)
+    cat_offsets: torch.Tensor   # int32 [K + 1] into the acc_* arrays
+    acc_index: torch.Tensor     # int32 [N]: the cell-order slot of each det in (category, descending score, image, in-cell rank) order
+    acc_rank: torch.Tensor      # int32 [N]: its in-cell rank
+    acc_score: torch.Tensor     # fp64 [N]: its score
+
+
+def _descending_key(score: torch.Tensor) -> torch.Tensor:
+    """int64 keys whose ascending order is the descending order of the fp64 scores, equal scores (0.0 and -0.0 too) on equal keys."""
+    b = (score + 0.0).view(torch.int64)
+    return ~(b ^ ((b >> 63) & 0x7FFFFFFFFFFFFFFF))
+
+
+def coco_order(img_rank: torch.Tensor, cls: torch.Tensor, score: torch.Tensor, boxes: torch.Tensor, n_images: int,
+               n_categories: int) -> CocoOrder:
+    """The two orderings locov_coco_match / locov_coco_accumulate take, by stable sorts on integer keys (no host read).
+    img_rank, cls: int64 [N]; score: fp64 [N]; boxes: fp32 [N, 4].  A class outside [0, K) goes to a trailing cell nothing reads."""
+    boxes = _dev(boxes, "boxes")
+    score = _dev(score, "score", torch.float64)
+    img_rank, cls = _dev(img_rank, "img_rank", torch.int64), _dev(cls, "cls", torch.int64)
+    I, K, N = int(n_images), int(n_categories), score.shape[0]
+    C = I * K
+    dev = boxes.device
+    cell = torch.where((cls >= 0) & (cls < K), cls * I + img_rank, torch.full_like(cls, C))
+    key = _descending_key(score)
+    p1 = torch.sort(key, stable=True).indices
+    cell, p2 = torch.sort(cell[p1], stable=True)
+    perm = p1[p2]
+    det_offsets = torch.searchsorted(cell, torch.arange(C + 1, dtype=torch.int64, device=dev)).to(torch.int32)
+    rank = (torch.arange(N, dtype=torch.int64, device=dev) - det_offsets[cell]).to(torch.int32)
+    pa = torch.sort(key[perm], stable=True).indices
+    cat, pb = torch.sort(torch.clamp(torch.div(cell, max(I, 1), rounding_mode="floor"), max=K)[pa], stable=True)
+    acc = pa[pb]
+    cat_offsets = torch.searchsorted(cat, torch.arange(K + 1, dtype=torch.int64, device=dev)).to(torch.int32)
+    return CocoOrder(det_offsets, boxes[perm].contiguous(), cat_offsets, acc.to(torch.int32), rank[acc].contiguous(),
+                     score[perm][acc].contiguous())
+
+
+def coco_match(det_offsets: torch.Tensor, gt_offsets: torch.Tensor, det_boxes: torch.Tensor, gt_boxes: torch.Tensor,
+               gt_area: torch.Tensor, gt_crowd: torch.Tensor, area_ranges, iou_thresholds, max_det: int):
+    """locov_coco_match: -> det_bits uint8 [N, A * T] (bit 0 matched, bit 1 ignored), gt_ignore uint8 [A, G].  One launch, no host
+    read.  det_offsets / gt_offsets: int32 [C + 1]; det_boxes fp32 [N, 4] XYXY in cell order; gt_boxes fp64 [G, 4] XYWH, gt_area
+    fp64 [G], gt_crowd uint8 [G]; area_ranges [A][2] and iou_thresholds [T]: host doubles."""
+    import numpy as np
+    det_offsets, gt_offsets = _dev(det_offsets, "det_offsets", torch.int32), _dev(gt_offsets, "gt_offsets", torch.int32)
+    det_boxes = _dev(det_boxes, "det_boxes")
+    gt_boxes, gt_area = _dev(gt_boxes, "gt_boxes", torch.float64), _dev(gt_area, "gt_area", torch.float64)
+    gt_crowd = _dev(gt_crowd, "gt_crowd", torch.uint8)
+    C, N, G = det_offsets.shape[0] - 1, det_boxes.shape[0], gt_area.shape[0]
+    if gt_offsets.shape[0] != C + 1 or det_boxes.shape != (N, 4) or gt_boxes.shape != (G, 4) or gt_crowd.shape[0] != G:
+        raise ValueError("coco_match: offsets of C + 1 entries each, det_boxes [N,4], gt_boxes [G,4], gt_area [G], gt_crowd [G]")
+    ar = np.ascontiguousarray(area_ranges, dtype=np.float64).reshape(-1, 2)
+    th = np.ascontiguousarray(iou_thresholds, dtype=np.float64).reshape(-1)
+    A, T = len(ar), len(th)
+    dev = det_boxes.device
+    bits = torch.empty((N, A * T), dtype=torch.uint8, device=dev)
+    gt_ignore = torch.empty((A, G), dtype=torch.uint8, device=dev)
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        ws_bytes = int(lib.locov_coco_match_workspace_bytes(G, int(max_det))) if N and G else 0
+        ws = _workspace("coco_match", det_boxes, ws_bytes) if ws_bytes else None
+        dp = ctypes.POINTER(ctypes.c_double)
+        check(lib.locov_coco_match(_ptr(det_offsets), _ptr(gt_offsets), C, N, G, int(max_det), _ptr(det_boxes), _ptr(gt_boxes), _ptr(gt_area),
+                                   _ptr(gt_crowd), ar.ctypes.data_as(dp), A, th.ctypes.data_as(dp), T, _ptr(bits), _ptr(gt_ignore), _ptr(ws),
+                                   ws_bytes, _stream(det_boxes)), "locov_coco_match")
+    return bits, gt_ignore
+
+
+def coco_accumulate(cat_offsets: torch.Tensor, acc_index: torch.Tensor, acc_rank: torch.Tensor, acc_score: torch.Tensor,
+                    det_bits: torch.Tensor, npig: torch.Tensor, n_thresholds: int, max_dets: Sequence[int], recall_thresholds,
+                    with_scores: bool = True) -> torch.Tensor:
+    """locov_coco_accumulate: -> ONE fp64 vector holding precision [T,R,K,A,M], then scores [T,R,K,A,M] (with_scores), then
+    recall [T,K,A,M], every element written (-1 where npig == 0), so the caller downloads it in one copy.  One launch, no host read.
+    cat_offsets int32 [K + 1]; acc_index / acc_rank int32 [N] and acc_score fp64 [N] in (category, descending score, image rank,
+    in-cell rank) order; det_bits as coco_match leaves it; npig int32 [K, A]."""
+    import numpy as np
+    cat_offsets = _dev(cat_offsets, "cat_offsets", torch.int32)
+    acc_index, acc_rank = _dev(acc_index, "acc_index", torch.int32), _dev(acc_rank, "acc_rank", torch.int32)
+    acc_score, det_bits, npig = _dev(acc_score, "acc_score", torch.float64), _dev(det_bits, "det_bits", torch.uint8), _dev(npig, "npig", torch.int32)
+    K, N, T = cat_offsets.shape[0] - 1, acc_index.shape[0], int(n_thresholds)
+    if npig.dim() != 2 or npig.shape[0] != K:
+        raise ValueError("coco_accumulate: npig must be [K, A]")
+    A = npig.shape[1]
+    if acc_rank.shape[0] != N or acc_score.shape[0] != N or det_bits.shape != (N, A * T):
+        raise ValueError("coco_accumulate: acc_index, acc_rank, acc_score of N entries each and det_bits [N, A * T]")
+    caps = np.ascontiguousarray(max_dets, dtype=np.int32).reshape(-1)
+    rec = np.ascontiguousarray(recall_thresholds, dtype=np.float64).reshape(-1)
+    M, R = len(caps), len(rec)
+    n = T * R * K * A * M
+    flat = torch.empty(((2 if with_scores else 1) * n + T * K * A * M,), dtype=torch.float64, device=det_bits.device)
+    precision, scores, recall = flat[:n], (flat[n:2 * n] if with_scores else None), flat[-T * K * A * M:] if K else flat[:0]
+    with torch.cuda.device(det_bits.device):
+        check(_lib.load().locov_coco_accumulate(_ptr(cat_offsets), K, _ptr(acc_index), _ptr(acc_rank), _ptr(acc_score), N, _ptr(det_bits),
+                                                _ptr(npig), A, T, caps.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), M,
+                                                rec.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), R, _ptr(precision), _ptr(recall),
+                                                _ptr(scores), _stream(det_bits)), "locov_coco_accumulate")
+    return flat

@@ -1,0 +1,162 @@
+"""COCOEvaluator.evaluate() on the device (csrc/coco_eval.hip) against the package's host path, on synthetic sets of COCO-val size.
+
+    timeout -k 10 900 python tools/time_evaluation.py [--images 5000] [--categories 80 1203] [--repeats 7] [--warmup 2]
+                                                      [--host-repeats 2] [--out records.json]
+
+A set: `images` images, `categories` categories, 7 gts and 100 dets per image from a seed (60 dets are jittered copies of the
+image's gts with their class, 40 are random boxes of random classes; 5 % of the gts are crowd; fp32 scores).  The dets are fed as
+one Instances per image, on the device for the device path and on the CPU for the host path; only evaluate() is timed.
+
+Per set: the wall time of evaluate() on the device (it ends in its one device-to-host copy, which synchronises) over `repeats`
+runs after `warmup`, median and 10th / 90th percentile; the same steps once more with a device synchronisation after each, to
+state the share of the gathering of the per-image tensors, the orderings (four stable sorts and two searches), the match launch,
+the accumulate launch, and the copy with the host's means; the host path's evaluate() `host-repeats` times; and whether the two
+paths' arrays are equal bit for bit.  Needs a ROCm GPU."""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+
+def spread(v, unit="ms"):
+    return {f"median_{unit}": float(np.median(v)), f"p10_{unit}": float(np.percentile(v, 10)), f"p90_{unit}": float(np.percentile(v, 90)),
+            "n": len(v)}
+
+
+def synthetic(n_images, n_categories, seed=0, gts_per_image=7, dets_per_image=100, matched=60):
+    """-> the COCO-format gt dict and per image (image_id, boxes fp32 [100, 4] XYXY, scores fp32, classes int64)."""
+    rng = np.random.default_rng(seed)
+    anns, per_image = [], []
+    for img in range(1, n_images + 1):
+        wh = rng.choice([12.0, 24.0, 48.0, 80.0, 140.0, 260.0], size=(gts_per_image, 2)) * rng.uniform(0.7, 1.3, size=(gts_per_image, 2))
+        xy = rng.uniform(0, 400, size=(gts_per_image, 2))
+        cat = rng.integers(0, n_categories, size=gts_per_image)
+        for g in range(gts_per_image):
+            anns.append(dict(id=len(anns) + 1, image_id=img, category_id=int(cat[g]) + 1, iscrowd=int(rng.random() < 0.05),
+                             bbox=[float(xy[g, 0]), float(xy[g, 1]), float(wh[g, 0]), float(wh[g, 1])], area=float(wh[g, 0] * wh[g, 1])))
+        pick = rng.integers(0, gts_per_image, size=matched)
+        bxy = xy[pick] + rng.normal(0, 4, size=(matched, 2))
+        bwh = wh[pick] * rng.uniform(0.8, 1.25, size=(matched, 2))
+        rxy, rwh = rng.uniform(0, 400, size=(dets_per_image - matched, 2)), rng.uniform(8, 200, size=(dets_per_image - matched, 2))
+        x1y1 = np.concatenate([bxy, rxy])
+        boxes = np.concatenate([x1y1, x1y1 + np.concatenate([bwh, rwh])], axis=1).astype(np.float32)
+        classes = np.concatenate([cat[pick], rng.integers(0, n_categories, size=dets_per_image - matched)]).astype(np.int64)
+        per_image.append((img, boxes, rng.random(dets_per_image).astype(np.float32), classes))
+    gt = dict(images=[dict(id=i) for i in range(1, n_images + 1)], annotations=anns,
+              categories=[dict(id=c + 1, name=f"c{c}") for c in range(n_categories)])
+    return gt, per_image
+
+
+def feed(evaluator, per_image, device):
+    from locov_amd.structures import Boxes, Instances
+    evaluator.reset()
+    for img, boxes, scores, classes in per_image:
+        inst = Instances((480, 640))
+        inst.pred_boxes = Boxes(torch.from_numpy(boxes).to(device))
+        inst.scores = torch.from_numpy(scores).to(device)
+        inst.pred_classes = torch.from_numpy(classes).to(device)
+        evaluator.process([dict(image_id=img)], [dict(instances=inst)])
+
+
+def staged(ev, dev):
+    """evaluate_device's steps with a synchronisation after each -> milliseconds per step."""
+    from locov_amd import evaluation as E, ops
+    t, marks = {}, [time.perf_counter()]
+
+    def mark(name):
+        torch.cuda.synchronize(dev)
+        marks.append(time.perf_counter())
+        t[name] = (marks[-1] - marks[-2]) * 1e3
+
+    gt, max_dets = ev._gt, ev.max_dets
+    img_rank, cls, score, boxes = ev._gathered(dev)
+    mark("gather")
+    g = gt.on(dev)
+    o = ops.coco_order(img_rank, cls, score, boxes, gt.n_images, gt.n_categories)
+    mark("orderings")
+    bits, gt_ignore = ops.coco_match(o.det_offsets, g["offsets"], o.boxes, g["box"], g["area"], g["crowd"], E.AREA_RNG, E.IOU_THRS, max_dets[-1])
+    mark("match")
+    c = torch.cat([torch.zeros((len(E.AREA_RNG), 1), dtype=torch.int64, device=dev), torch.cumsum(gt_ignore == 0, dim=1)], dim=1)
+    npig = (c[:, g["cat_offsets"][1:]] - c[:, g["cat_offsets"][:-1]]).t().contiguous().to(torch.int32)
+    mark("npig")
+    flat = ops.coco_accumulate(o.cat_offsets, o.acc_index, o.acc_rank, o.acc_score, bits, npig, len(E.IOU_THRS), max_dets, E.REC_THRS)
+    mark("accumulate")
+    host = flat.cpu().numpy()
+    K, A, T, R, M = gt.n_categories, len(E.AREA_RNG), len(E.IOU_THRS), len(E.REC_THRS), len(max_dets)
+    n = T * R * K * A * M
+    E.summarize(host[:n].reshape(T, R, K, A, M), host[2 * n:].reshape(T, K, A, M))
+    mark("copy_and_means")
+    return t
+
+
+def measure(n_images, n_categories, args, dev):
+    from locov_amd.evaluation import COCOEvaluator
+    t0 = time.perf_counter()
+    gt, per_image = synthetic(n_images, n_categories)
+    on_dev, on_host = COCOEvaluator(gt), COCOEvaluator(gt)
+    rec = {"images": n_images, "categories": n_categories, "dets": sum(len(p[2]) for p in per_image), "gts": len(gt["annotations"]),
+           "build_s": time.perf_counter() - t0}
+    feed(on_dev, per_image, dev)
+    wall = []
+    for it in range(args.warmup + args.repeats):
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        res = on_dev.evaluate()
+        torch.cuda.synchronize(dev)
+        if it >= args.warmup:
+            wall.append((time.perf_counter() - t0) * 1e3)
+    rec["device_evaluate"] = spread(wall)
+    stages = [staged(on_dev, dev) for _ in range(args.warmup + args.repeats)][args.warmup:]
+    rec["device_stages_ms"] = {k: float(np.median([s[k] for s in stages])) for k in stages[0]}
+    total = sum(rec["device_stages_ms"].values())
+    rec["device_stage_share"] = {k: v / total for k, v in rec["device_stages_ms"].items()}
+    print(json.dumps({f"{n_categories} categories, device": rec}), flush=True)
+    feed(on_host, per_image, "cpu")
+    host = []
+    for _ in range(args.host_repeats):
+        t0 = time.perf_counter()
+        res_host = on_host.evaluate()
+        host.append((time.perf_counter() - t0) * 1e3)
+        print(json.dumps({f"{n_categories} categories, host evaluate ms": host[-1]}), flush=True)
+    rec["host_evaluate"] = spread(host)
+    rec["equal_bits"] = all(on_dev.eval[k].tobytes() == on_host.eval[k].tobytes() for k in ("precision", "recall", "scores", "stats"))
+    rec["AP"], rec["AP50"] = res["bbox"]["AP"], res_host["bbox"]["AP50"]
+    rec["speedup_median"] = rec["host_evaluate"]["median_ms"] / rec["device_evaluate"]["median_ms"]
+    return rec
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--images", type=int, default=5000)
+    ap.add_argument("--categories", type=int, nargs="+", default=[80, 1203])
+    ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--host-repeats", type=int, default=2)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args(argv)
+    if not torch.cuda.is_available():
+        raise SystemExit("time_evaluation: needs a ROCm GPU")
+    dev = torch.device("cuda:0")
+    torch.cuda.set_device(dev)
+    rec = {"device": torch.cuda.get_device_name(dev), "torch": torch.__version__, "sets": []}
+    for k in args.categories:
+        rec["sets"].append(measure(args.images, k, args, dev))
+        print(json.dumps(rec["sets"][-1]), flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(rec, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
