@@ -39,7 +39,7 @@ extern "C" {
  *    locov_rpn_label_anchors (+ _workspace_bytes), locov_rpn_sample_anchors, locov_rpn_loss (+ _workspace_bytes),
  *    locov_resnet_stem_fwd, locov_resnet_stem_fwd_sel, locov_resnet_stem_wgrad (+ _workspace_bytes),
  *    locov_preprocess_images, locov_detector_rescale, locov_sgd_step (+ _workspace_bytes),
- *    locov_coco_match (+ _workspace_bytes), locov_coco_accumulate */
+ *    locov_coco_match (+ _workspace_bytes), locov_coco_accumulate, locov_lvis_match */
 #define LOCOV_ABI_VERSION 8
 
 #define LOCOV_OK 0
@@ -1485,6 +1485,30 @@ int locov_coco_accumulate(const int *cat_offsets, int n_categories, const int *a
                           const double *acc_score, int n_det, const uint8_t *det_bits, const int *npig, int n_areas,
                           int n_thresholds, const int *max_dets_host, int n_max_dets, const double *recall_thresholds_host,
                           int n_recall_thresholds, double *precision, double *recall, double *scores, locov_stream_t stream);
+
+/* ---- LVIS-protocol box evaluation (csrc/coco_eval.hip): the public LVISEval, which Detectron2's LVISEvaluator sits on ------------
+ * (what ovr/evaluation/evaluator.py:39-50 returns for every dataset whose name contains "lvis").  Added under ABI version 8.
+ *
+ * locov_lvis_match: locov_coco_match's kernel under the federated protocol; every argument it shares with locov_coco_match means
+ * the same, its frame, limits, workspace (locov_coco_match_workspace_bytes) and error codes are the same.  The differences:
+ *   gt_ignore_in : uint8 [n_gt], the annotation's own `ignore` field.  It stands where gt_crowd stood in the ignore test (a gt is
+ *                 ignored in range a if gt_ignore_in or its area is outside [lo, hi]) and nowhere else: the IoU is always
+ *                 i / (dw * dh + gw * gh - i), and a gt matched at (a, t) is never taken again, ignored or not.
+ *   cell_flags  : uint8 [n_cells], bits LOCOV_LVIS_CELL_*: the image's neg_category_ids / not_exhaustive_category_ids.
+ *                 An unmatched det is ignored if its area is outside [lo, hi] OR its cell is NOT_EXHAUSTIVE.
+ *                 A cell with no gt and no NEG bit is UNLISTED: its dets are neither true nor false positives.  The first max_det
+ *                 of them get bits 2 (unmatched, ignored) in every column; locov_coco_accumulate repeats its running counts
+ *                 over such a det, so precision and recall are those of the dets without them (the `scores` output is not:
+ *                 pass scores = NULL to locov_coco_accumulate).
+ *   max_det     : the caller's cap; LVIS caps per image over all categories, which the caller applies before the cell order, so
+ *                 no cell holds more.  The precision / recall arrays come from locov_coco_accumulate with the one cap max_det.
+ *   A null cell_flags (with cells and a det or gt) or gt_ignore_in (with n_gt > 0): LOCOV_ERR_INVALID_ARG before any HIP call. */
+#define LOCOV_LVIS_CELL_NEG 1            /* the category is in the image's neg_category_ids */
+#define LOCOV_LVIS_CELL_NOT_EXHAUSTIVE 2 /* ... in its not_exhaustive_category_ids */
+int locov_lvis_match(const int *det_offsets, const int *gt_offsets, const uint8_t *cell_flags, int64_t n_cells, int n_det, int n_gt,
+                     int max_det, const float *det_boxes, const double *gt_boxes, const double *gt_area, const uint8_t *gt_ignore_in,
+                     const double *area_ranges_host, int n_areas, const double *iou_thresholds_host, int n_thresholds,
+                     uint8_t *det_bits, uint8_t *gt_ignore, void *workspace, int64_t workspace_bytes, locov_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -25,4 +25,4 @@ from .engine import SimpleTrainerMMSS  # noqa: F401,E402
 from .solver import (FusedSGD, WarmupCosineLR, WarmupMultiStepLR, build_lr_scheduler, build_optimizer,  # noqa: F401,E402
                      get_default_optimizer_params)
 from . import evaluation  # noqa: F401,E402
-from .evaluation import COCOEvaluator, inference_on_dataset  # noqa: F401,E402
+from .evaluation import COCOEvaluator, LVISEvaluator, build_evaluator, inference_on_dataset  # noqa: F401,E402

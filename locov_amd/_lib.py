@@ -45,6 +45,7 @@ SGD_MAX_CLASSES, SGD_CHUNK, SGD_RECORD_BYTES = 8, 4096, 48
 SGD_CLIP_NONE, SGD_CLIP_VALUE, SGD_CLIP_NORM = 0, 1, 2
 COCO_MAX_AREAS, COCO_MAX_THRESHOLDS, COCO_MAX_CAPS, COCO_MAX_RECALL_THRESHOLDS = 4, 16, 3, 256
 COCO_MAX_DET, COCO_MAX_BLOCKS = 4096, 8388608
+LVIS_CELL_NEG, LVIS_CELL_NOT_EXHAUSTIVE = 1, 2
 
 _p = c_void_p  # device pointer
 
@@ -241,6 +242,8 @@ SIGNATURES = {
                                  _p, _p, _p, c_int64, _p]),
     "locov_coco_accumulate": (c_int, [_p, c_int, _p, _p, _p, c_int, _p, _p, c_int, c_int, POINTER(c_int), c_int, POINTER(c_double), c_int,
                                       _p, _p, _p, _p]),
+    "locov_lvis_match": (c_int, [_p, _p, _p, c_int64, c_int, c_int, c_int, _p, _p, _p, _p, POINTER(c_double), c_int, POINTER(c_double), c_int,
+                                 _p, _p, _p, c_int64, _p]),
 }
 
 _lib = None

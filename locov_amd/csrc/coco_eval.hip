@@ -15,6 +15,12 @@
 //   gts, where a matched crowd gt may be taken again.  This is COCOeval's single loop over the gts sorted non-ignored first.  A
 //   matched det takes its gt's ignore flag; an unmatched det whose own area (dw * dh) is outside the range is ignored.
 //
+// locov_lvis_match: the same kernel under the LVIS protocol (the public LVISEval, which Detectron2's LVISEvaluator sits on).
+//   The gt's own `ignore` flag stands where crowd stood in the ignore test and nowhere else: the IoU is always the non-crowd one
+//   and a matched gt is never taken again.  A byte per cell carries the image's federated lists: an unmatched det of a cell
+//   marked NOT_EXHAUSTIVE is ignored whatever its area, and a cell with no gt and no NEG mark is UNLISTED -- its dets are neither
+//   true nor false positives, and are written as unmatched and ignored (2), which the accumulation passes over.
+//
 // locov_coco_accumulate: one workgroup per (category, range, cap, threshold), walking the category's dets (descending score, ties
 //   in image then in-cell order) in chunks of kAccChunk, in ascending order, with integer carries -- no atomics, no float carry
 //   but a running maximum, so two runs give equal bits.  Over the dets whose in-cell rank is below the cap:  tp / fp are the
@@ -44,12 +50,15 @@ __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? l
 // bytes of workspace one gt owns: its column of the largest IoU matrix and its matched flags
 __host__ __device__ inline int64_t gt_slot_bytes(int max_det) { return (int64_t)max_det * 8 + kGtmStride; }
 
-__global__ __launch_bounds__(kThreads) void coco_match_kernel(const int *__restrict__ det_off, const int *__restrict__ gt_off,
-                                                              int64_t n_cells, int n_det, int n_gt, int max_det,
-                                                              const float *__restrict__ det_box, const double *__restrict__ gt_box,
-                                                              const double *__restrict__ gt_area, const uint8_t *__restrict__ gt_crowd,
-                                                              MatchArgs args, uint8_t *__restrict__ det_bits,
-                                                              uint8_t *__restrict__ gt_ignore, char *__restrict__ ws)
+// kLvis false: gt_flag is iscrowd and cell_flags is not read.  kLvis true: gt_flag is the gt's own ignore field.
+template <bool kLvis>
+__global__ __launch_bounds__(kThreads) void match_kernel(const int *__restrict__ det_off, const int *__restrict__ gt_off,
+                                                         const uint8_t *__restrict__ cell_flags, int64_t n_cells, int n_det, int n_gt,
+                                                         int max_det, const float *__restrict__ det_box,
+                                                         const double *__restrict__ gt_box, const double *__restrict__ gt_area,
+                                                         const uint8_t *__restrict__ gt_flag, MatchArgs args,
+                                                         uint8_t *__restrict__ det_bits, uint8_t *__restrict__ gt_ignore,
+                                                         char *__restrict__ ws)
 {
     __shared__ double lds[kCellsPerBlock][kCellLds / 8];
     __shared__ double s_lo[LOCOV_COCO_MAX_AREAS], s_hi[LOCOV_COCO_MAX_AREAS], s_thr[LOCOV_COCO_MAX_THRESHOLDS];
@@ -63,7 +72,7 @@ __global__ __launch_bounds__(kThreads) void coco_match_kernel(const int *__restr
     __syncthreads();
 
     const int64_t cell = (int64_t)blockIdx.x * kCellsPerBlock + wave;
-    int d0 = 0, D = 0, g0 = 0, G = 0;
+    int d0 = 0, D = 0, g0 = 0, G = 0, flags = 0;
     double *iou = nullptr;
     uint8_t *gtm = nullptr;
     if (cell < n_cells) {
@@ -73,6 +82,7 @@ __global__ __launch_bounds__(kThreads) void coco_match_kernel(const int *__restr
         g0 = clampi(gt_off[cell], 0, n_gt);
         G = clampi(gt_off[cell + 1], g0, n_gt) - g0;
         D = d1 - d0 < max_det ? d1 - d0 : max_det;
+        if constexpr (kLvis) flags = cell_flags[cell];
         // the dets past the cap take no part: their bits are written as zero
         const int64_t extra = (int64_t)(d1 - d0 - D) * AT;
         uint8_t *tail = det_bits + (int64_t)(d0 + D) * AT;
@@ -80,7 +90,7 @@ __global__ __launch_bounds__(kThreads) void coco_match_kernel(const int *__restr
         for (int64_t i = lane; i < (int64_t)A * G; i += kWave) {
             const int a = (int)(i / G), g = g0 + (int)(i % G);
             const double ar = gt_area[g];
-            gt_ignore[(int64_t)a * n_gt + g] = (gt_crowd[g] != 0 || ar < s_lo[a] || ar > s_hi[a]) ? 1 : 0;
+            gt_ignore[(int64_t)a * n_gt + g] = (gt_flag[g] != 0 || ar < s_lo[a] || ar > s_hi[a]) ? 1 : 0;
         }
         if (D > 0 && G > 0) {
             if ((int64_t)D * G * 8 + (int64_t)G * kGtmStride <= kCellLds) {
@@ -105,7 +115,7 @@ __global__ __launch_bounds__(kThreads) void coco_match_kernel(const int *__restr
                     if (h > 0.0) {
                         const double i = w * h;
                         const double da = dw * dh;
-                        const double u = gt_crowd[g0 + g] ? da : da + gw * gh - i;
+                        const double u = (!kLvis && gt_flag[g0 + g]) ? da : da + gw * gh - i;
                         v = i / u;
                     }
                 }
@@ -116,6 +126,12 @@ __global__ __launch_bounds__(kThreads) void coco_match_kernel(const int *__restr
     }
     __syncthreads();                                                                           // the matrix is complete
     if (lane >= AT || D == 0) return;
+    if constexpr (kLvis) {
+        if (G == 0 && !(flags & LOCOV_LVIS_CELL_NEG)) {                                        // an unlisted cell: no part
+            for (int d = 0; d < D; d++) det_bits[(int64_t)(d0 + d) * AT + lane] = 2;
+            return;
+        }
+    }
 
     const int a = lane / T;
     const double lo = s_lo[a], hi = s_hi[a];
@@ -126,7 +142,7 @@ __global__ __launch_bounds__(kThreads) void coco_match_kernel(const int *__restr
         int m = -1, m_ignored = 0;
         for (int g = 0; g < G; g++) {                                                          // the gts not ignored in this range
             const double ar = gt_area[g0 + g];
-            if (gt_crowd[g0 + g] || ar < lo || ar > hi) continue;
+            if (gt_flag[g0 + g] || ar < lo || ar > hi) continue;
             if (gtm[(int64_t)g * kGtmStride + lane]) continue;
             const double v = iou[(int64_t)d * G + g];
             if (v < best) continue;
@@ -136,9 +152,9 @@ __global__ __launch_bounds__(kThreads) void coco_match_kernel(const int *__restr
         if (m < 0) {
             for (int g = 0; g < G; g++) {                                                      // nothing there: the ignored ones
                 const double ar = gt_area[g0 + g];
-                const bool crowd = gt_crowd[g0 + g] != 0;
-                if (!(crowd || ar < lo || ar > hi)) continue;
-                if (gtm[(int64_t)g * kGtmStride + lane] && !crowd) continue;
+                const bool flag = gt_flag[g0 + g] != 0;
+                if (!(flag || ar < lo || ar > hi)) continue;
+                if (gtm[(int64_t)g * kGtmStride + lane] && (kLvis || !flag)) continue;              // (only a crowd gt is taken again)
                 const double v = iou[(int64_t)d * G + g];
                 if (v < best) continue;
                 best = v;
@@ -153,7 +169,7 @@ __global__ __launch_bounds__(kThreads) void coco_match_kernel(const int *__restr
         } else {
             const float *b = det_box + (int64_t)(d0 + d) * 4;
             const double da = (double)(b[2] - b[0]) * (double)(b[3] - b[1]);
-            bits = (da < lo || da > hi) ? 2 : 0;
+            bits = (da < lo || da > hi || (kLvis && (flags & LOCOV_LVIS_CELL_NOT_EXHAUSTIVE))) ? 2 : 0;
         }
         det_bits[(int64_t)(d0 + d) * AT + lane] = (uint8_t)bits;
     }
@@ -331,33 +347,37 @@ extern "C" int64_t locov_coco_match_workspace_bytes(int n_gt, int max_det)
     return (int64_t)n_gt * gt_slot_bytes(max_det);
 }
 
-extern "C" int locov_coco_match(const int *det_offsets, const int *gt_offsets, int64_t n_cells, int n_det, int n_gt, int max_det,
-                                const float *det_boxes, const double *gt_boxes, const double *gt_area, const uint8_t *gt_crowd,
-                                const double *area_ranges_host, int n_areas, const double *iou_thresholds_host, int n_thresholds,
-                                uint8_t *det_bits, uint8_t *gt_ignore, void *workspace, int64_t workspace_bytes,
-                                locov_stream_t stream)
+namespace {
+
+// The one body of locov_coco_match (cell_flags unused, gt_flag = iscrowd) and locov_lvis_match (gt_flag = the gt's ignore field).
+template <bool kLvis>
+int match_entry(const char *who, const int *det_offsets, const int *gt_offsets, const uint8_t *cell_flags, int64_t n_cells, int n_det,
+                int n_gt, int max_det, const float *det_boxes, const double *gt_boxes, const double *gt_area, const uint8_t *gt_flag,
+                const double *area_ranges_host, int n_areas, const double *iou_thresholds_host, int n_thresholds, uint8_t *det_bits,
+                uint8_t *gt_ignore, void *workspace, int64_t workspace_bytes, locov_stream_t stream)
 {
-    LOCOV_REQUIRE(n_cells >= 0 && n_det >= 0 && n_gt >= 0 && workspace_bytes >= 0, "locov_coco_match: negative count or size");
-    LOCOV_REQUIRE(max_det >= 1, "locov_coco_match: max_det must be at least 1");
-    LOCOV_REQUIRE(n_areas >= 1 && n_areas <= LOCOV_COCO_MAX_AREAS, "locov_coco_match: 1..%d area ranges", LOCOV_COCO_MAX_AREAS);
-    LOCOV_REQUIRE(n_thresholds >= 1 && n_thresholds <= LOCOV_COCO_MAX_THRESHOLDS, "locov_coco_match: 1..%d IoU thresholds",
+    LOCOV_REQUIRE(n_cells >= 0 && n_det >= 0 && n_gt >= 0 && workspace_bytes >= 0, "%s: negative count or size", who);
+    LOCOV_REQUIRE(max_det >= 1, "%s: max_det must be at least 1", who);
+    LOCOV_REQUIRE(n_areas >= 1 && n_areas <= LOCOV_COCO_MAX_AREAS, "%s: 1..%d area ranges", who, LOCOV_COCO_MAX_AREAS);
+    LOCOV_REQUIRE(n_thresholds >= 1 && n_thresholds <= LOCOV_COCO_MAX_THRESHOLDS, "%s: 1..%d IoU thresholds", who,
                   LOCOV_COCO_MAX_THRESHOLDS);
-    LOCOV_REQUIRE(area_ranges_host && iou_thresholds_host, "locov_coco_match: null area range or threshold list");
+    LOCOV_REQUIRE(area_ranges_host && iou_thresholds_host, "%s: null area range or threshold list", who);
     for (int a = 0; a < n_areas; a++)
-        LOCOV_REQUIRE(area_ranges_host[2 * a] <= area_ranges_host[2 * a + 1], "locov_coco_match: area range %d is not ascending", a);
+        LOCOV_REQUIRE(area_ranges_host[2 * a] <= area_ranges_host[2 * a + 1], "%s: area range %d is not ascending", who, a);
     if (n_cells == 0 || (n_det == 0 && n_gt == 0)) return LOCOV_OK;
     if (max_det > LOCOV_COCO_MAX_DET || n_cells > (int64_t)LOCOV_COCO_MAX_BLOCKS * kCellsPerBlock)
-        return set_error(LOCOV_ERR_UNSUPPORTED, "locov_coco_match: at most %d dets per cell and %lld cells", LOCOV_COCO_MAX_DET,
+        return set_error(LOCOV_ERR_UNSUPPORTED, "%s: at most %d dets per cell and %lld cells", who, LOCOV_COCO_MAX_DET,
                          (long long)LOCOV_COCO_MAX_BLOCKS * kCellsPerBlock);
-    LOCOV_REQUIRE(det_offsets && gt_offsets, "locov_coco_match: null offsets");
-    LOCOV_REQUIRE(n_det == 0 || (det_boxes && det_bits), "locov_coco_match: null det pointer");
-    LOCOV_REQUIRE(n_gt == 0 || (gt_boxes && gt_area && gt_crowd && gt_ignore), "locov_coco_match: null gt pointer");
+    LOCOV_REQUIRE(det_offsets && gt_offsets, "%s: null offsets", who);
+    if (kLvis) LOCOV_REQUIRE(cell_flags, "%s: null cell flags", who);
+    LOCOV_REQUIRE(n_det == 0 || (det_boxes && det_bits), "%s: null det pointer", who);
+    LOCOV_REQUIRE(n_gt == 0 || (gt_boxes && gt_area && gt_flag && gt_ignore), "%s: null gt pointer", who);
     LOCOV_REQUIRE((uintptr_t)gt_boxes % 8 == 0 && (uintptr_t)gt_area % 8 == 0 && (uintptr_t)det_boxes % 4 == 0 &&
                       (uintptr_t)det_offsets % 4 == 0 && (uintptr_t)gt_offsets % 4 == 0,
-                  "locov_coco_match: misaligned pointer");
+                  "%s: misaligned pointer", who);
     if (n_det > 0 && n_gt > 0) {
-        LOCOV_REQUIRE(workspace && (uintptr_t)workspace % 8 == 0, "locov_coco_match: null or misaligned workspace");
-        LOCOV_REQUIRE(workspace_bytes >= locov_coco_match_workspace_bytes(n_gt, max_det), "locov_coco_match: workspace too small");
+        LOCOV_REQUIRE(workspace && (uintptr_t)workspace % 8 == 0, "%s: null or misaligned workspace", who);
+        LOCOV_REQUIRE(workspace_bytes >= locov_coco_match_workspace_bytes(n_gt, max_det), "%s: workspace too small", who);
     }
     MatchArgs args{};
     for (int a = 0; a < n_areas; a++) {
@@ -368,10 +388,34 @@ extern "C" int locov_coco_match(const int *det_offsets, const int *gt_offsets, i
     args.A = n_areas;
     args.T = n_thresholds;
     const int64_t grid = ceil_div(n_cells, kCellsPerBlock);
-    hipLaunchKernelGGL(coco_match_kernel, dim3((unsigned)grid), dim3(kThreads), 0, as_stream(stream), det_offsets, gt_offsets, n_cells,
-                       n_det, n_gt, max_det, det_boxes, gt_boxes, gt_area, gt_crowd, args, det_bits, gt_ignore,
+    hipLaunchKernelGGL(match_kernel<kLvis>, dim3((unsigned)grid), dim3(kThreads), 0, as_stream(stream), det_offsets, gt_offsets,
+                       cell_flags, n_cells, n_det, n_gt, max_det, det_boxes, gt_boxes, gt_area, gt_flag, args, det_bits, gt_ignore,
                        static_cast<char *>(workspace));
-    return check_launch("locov_coco_match");
+    return check_launch(who);
+}
+
+}  // namespace
+
+extern "C" int locov_coco_match(const int *det_offsets, const int *gt_offsets, int64_t n_cells, int n_det, int n_gt, int max_det,
+                                const float *det_boxes, const double *gt_boxes, const double *gt_area, const uint8_t *gt_crowd,
+                                const double *area_ranges_host, int n_areas, const double *iou_thresholds_host, int n_thresholds,
+                                uint8_t *det_bits, uint8_t *gt_ignore, void *workspace, int64_t workspace_bytes,
+                                locov_stream_t stream)
+{
+    return match_entry<false>("locov_coco_match", det_offsets, gt_offsets, nullptr, n_cells, n_det, n_gt, max_det, det_boxes, gt_boxes,
+                              gt_area, gt_crowd, area_ranges_host, n_areas, iou_thresholds_host, n_thresholds, det_bits, gt_ignore,
+                              workspace, workspace_bytes, stream);
+}
+
+extern "C" int locov_lvis_match(const int *det_offsets, const int *gt_offsets, const uint8_t *cell_flags, int64_t n_cells, int n_det,
+                                int n_gt, int max_det, const float *det_boxes, const double *gt_boxes, const double *gt_area,
+                                const uint8_t *gt_ignore_in, const double *area_ranges_host, int n_areas,
+                                const double *iou_thresholds_host, int n_thresholds, uint8_t *det_bits, uint8_t *gt_ignore,
+                                void *workspace, int64_t workspace_bytes, locov_stream_t stream)
+{
+    return match_entry<true>("locov_lvis_match", det_offsets, gt_offsets, cell_flags, n_cells, n_det, n_gt, max_det, det_boxes, gt_boxes,
+                             gt_area, gt_ignore_in, area_ranges_host, n_areas, iou_thresholds_host, n_thresholds, det_bits, gt_ignore,
+                             workspace, workspace_bytes, stream);
 }
 
 extern "C" int locov_coco_accumulate(const int *cat_offsets, int n_categories, const int *acc_index, const int *acc_rank,

@@ -31,6 +31,41 @@ The protocol, as every path below computes it (float64 and integers only, so the
 Paths: the numpy functions of this file are the definition; they serve CPU tensors, LOCOV_FUSED_COCOEVAL=0 (A/B runs, like
 LOCOV_FUSED_ATTENTION) and sizes beyond the kernels' limits.  Device tensors take ops.coco_order / coco_match / coco_accumulate
 (csrc/coco_eval.hip) with one device-to-host copy, of the result arrays.  The evaluator scores what its own process saw.
+
+LVIS-protocol box AP with APr / APc / APf (the public lvis-api's LVISEval and LVISResults, and Detectron2's LVISEvaluator, which
+the reference's select_and_build_evaluator returns for every dataset whose name contains "lvis": ovr/evaluation/evaluator.py:39-50),
+without lvis-api.  LVIS is federated: an image is annotated exhaustively for a few categories only.  The protocol, float64 and
+integers again:
+
+  * Parameters: iou_thrs, rec_thrs and the four area ranges as above; one cap, max_dets_per_image = 300.  Images and categories in
+    ascending id; contiguous class c is the c-th smallest category id.
+  * Ground truth: bbox XYWH as float64, area = the annotation's own field, ignore = its `ignore` field (0 when absent); there is
+    no crowd notion and iscrowd is not read.  Per image neg_category_ids and not_exhaustive_category_ids (empty when absent); per
+    category frequency "r" / "c" / "f" (a category without the field belongs to no group).
+  * Detections: as above.  A det whose class is outside [0, K) is left out before anything else.
+  * The cap (LVISResults.limit_dets_per_image): an image with more than max_dets_per_image dets keeps the first max_dets_per_image
+    of a stable sort by descending score (ties in input order), over all its categories together.
+  * The federated filter: a det of (image i, category k) takes part only if k has a gt in i or k is in i's neg_category_ids; any
+    other det is dropped, neither a true nor a false positive.
+  * Per cell and area range: a gt is ignored if its ignore is set or its area is outside [lo, hi]; gts are visited non-ignored
+    first (stable); IoU is the non-crowd formula for every gt.  Per threshold t, the dets in descending score (ties in the order the
+    cap left, which is input order): best = min(t, 1 - 1e-10); a gt already matched at t is skipped, so an ignored gt is taken once
+    only; the walk stops when the match is a non-ignored gt and the next is ignored; a gt with iou >= best becomes the match and
+    raises best (equal IoU moves to the later gt).  A matched det takes its gt's ignore flag; an unmatched det is ignored if its
+    own area is outside the range or its category is in the image's not_exhaustive_category_ids.
+  * Accumulate: the COCO one above with the one cap and no scores; num_gt = the category's non-ignored gts over all images.
+    -> precision [T, R, K, A], recall [T, K, A], -1 where num_gt == 0.
+  * The thirteen stats: AP, AP50 (iou_thrs[0]), AP75 (iou_thrs[5]), APs, APm, APl; APr, APc, APf = precision[:, :, group, 0] over
+    the category ranks of each frequency group; AR@cap, ARs, ARm, ARl.  Each the mean over the entries > -1, -1 with none.
+  * Results: the nine AP metrics x 100 with no special case, as Detectron2 does (-1 becomes -100.0); all nan when nothing was
+    processed.
+  * Stated differences (COCO's too): a gt with id 0 counts as a match like any other (LVISEval reads a stored id 0 as
+    "unmatched"); an image id absent from the ground truth raises in process().
+
+Paths: the *_lvis numpy functions are the definition and drop the unlisted dets literally.  Device tensors take ops.lvis_limit
+(the cap: two stable integer-key sorts and the in-image position; a det past the cap goes to the trailing cell), ops.coco_order,
+ops.lvis_match (the COCO match kernel's other instantiation, which writes the dets of an unlisted cell as ignored: the accumulation
+passes over an ignored det, so precision and recall do not move) and ops.coco_accumulate without scores, then the one copy.
 """
 from __future__ import annotations
 
@@ -44,7 +79,7 @@ import torch
 
 from . import _lib
 
-__all__ = ["COCOEvaluator", "inference_on_dataset", "IOU_THRS", "REC_THRS", "AREA_RNG"]
+__all__ = ["COCOEvaluator", "LVISEvaluator", "build_evaluator", "inference_on_dataset", "IOU_THRS", "REC_THRS", "AREA_RNG"]
 
 IOU_THRS = np.linspace(.5, .95, 10)
 REC_THRS = np.linspace(0., 1., 101)
@@ -380,3 +415,217 @@ def inference_on_dataset(model, data_loader, evaluator):
         model.train(was_training)
     results = evaluator.evaluate()
     return results if results is not None else {}
+
+
+# ---- the LVIS protocol (module docstring) ------------------------------------------------------------------------------------------
+LVIS_METRICS = ("AP", "AP50", "AP75", "APs", "APm", "APl", "APr", "APc", "APf")
+LVIS_FREQUENCIES = ("r", "c", "f")
+
+
+class _LVISGroundTruth(_GroundTruth):
+    """_GroundTruth plus what the federated protocol reads: each gt's `ignore` field (cell order), a byte per cell with the image's
+    neg / not-exhaustive lists, and the frequency groups as arrays of category ranks.  `crowd` is kept but never read."""
+
+    def __init__(self, gt):
+        if isinstance(gt, (str, os.PathLike)):
+            with open(gt) as f:
+                gt = json.load(f)
+        super().__init__(gt)
+        I, K = self.n_images, self.n_categories
+        cat_rank = {cid: r for r, cid in enumerate(self.cat_ids)}
+        anns = [a for a in gt.get("annotations", ()) if a["image_id"] in self.image_rank and a["category_id"] in cat_rank]
+        cell = np.array([cat_rank[a["category_id"]] * I + self.image_rank[a["image_id"]] for a in anns], dtype=np.int64)
+        order = np.argsort(cell, kind="stable")                                               # (the parent's order)
+        self.ignore = np.array([1 if anns[i].get("ignore", 0) else 0 for i in order], dtype=np.uint8)
+        self.cell_flags = np.zeros(I * K, dtype=np.uint8)
+        for field, bit in (("neg_category_ids", _lib.LVIS_CELL_NEG), ("not_exhaustive_category_ids", _lib.LVIS_CELL_NOT_EXHAUSTIVE)):
+            cells = np.array([cat_rank[c] * I + self.image_rank[im["id"]] for im in gt["images"] for c in im.get(field, ())
+                              if c in cat_rank], dtype=np.int64)
+            self.cell_flags[cells] |= np.uint8(bit)                                            # (a scatter of one constant)
+        freq = [c.get("frequency") for c in sorted(gt["categories"], key=lambda c: c["id"])]
+        self.freq_groups = [np.array([r for r, f in enumerate(freq) if f == name], dtype=np.int64) for name in LVIS_FREQUENCIES]
+
+    def on(self, device):
+        d = self._device.get(device)
+        if d is None:
+            d = super().on(device)
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
+            d.update(ignore=up(self.ignore), cell_flags=up(self.cell_flags))
+        return d
+
+
+def limit_host(img_rank, cls, score, n_categories, max_dets_per_image):
+    """LVISResults.limit_dets_per_image -> bool [N]: the dets that stay.  A class outside [0, K) is left out first; of the others
+    each image keeps the first max_dets_per_image of a stable sort by descending score, over all categories together."""
+    keep = (cls >= 0) & (cls < n_categories)
+    idx = np.nonzero(keep)[0]
+    p = idx[np.argsort(-score[idx], kind="stable")]
+    p = p[np.argsort(img_rank[p], kind="stable")]
+    image = img_rank[p]
+    first = np.searchsorted(image, image, side="left")
+    keep[p[np.arange(len(p)) - first >= max_dets_per_image]] = False
+    return keep
+
+
+def listed_host(gt: _LVISGroundTruth, img_rank, cls):
+    """bool [N] for dets with a class in [0, K): the category has a gt in the image or is in its neg_category_ids."""
+    cell = cls * gt.n_images + img_rank
+    return (np.diff(gt.offsets.astype(np.int64))[cell] > 0) | ((gt.cell_flags[cell] & _lib.LVIS_CELL_NEG) != 0)
+
+
+def match_host_lvis(gt: _LVISGroundTruth, det_offsets, boxes, max_det, area_rng=AREA_RNG, iou_thrs=IOU_THRS):
+    """match_host under the LVIS rules.  boxes: fp32 XYXY in cell order.  -> det_bits uint8 [N, A * T], gt_ignore uint8 [A, G],
+    listed bool [N]: False for the dets of unlisted cells (and of the trailing cell), which take no part; their bits are 0."""
+    A, T = len(area_rng), len(iou_thrs)
+    lo, hi = area_rng[:, 0], area_rng[:, 1]
+    boxes = np.asarray(boxes, dtype=np.float32).reshape(-1, 4)
+    dw = (boxes[:, 2] - boxes[:, 0]).astype(np.float64)
+    dh = (boxes[:, 3] - boxes[:, 1]).astype(np.float64)
+    dx, dy = boxes[:, 0].astype(np.float64), boxes[:, 1].astype(np.float64)
+    darea = dw * dh
+    gt_ignore = ((gt.ignore[None, :] != 0) | (gt.area[None, :] < lo[:, None]) | (gt.area[None, :] > hi[:, None]))
+    counts = np.diff(det_offsets.astype(np.int64))
+    gcount = np.diff(gt.offsets.astype(np.int64))
+    n_listed = int(det_offsets[-1])
+    cell_of = np.repeat(np.arange(len(counts), dtype=np.int64), counts)
+    in_cell = np.arange(n_listed, dtype=np.int64) - np.repeat(det_offsets[:-1].astype(np.int64), counts)
+    listed = np.zeros(len(boxes), dtype=bool)
+    listed[:n_listed] = (gcount[cell_of] > 0) | ((gt.cell_flags[cell_of] & _lib.LVIS_CELL_NEG) != 0)
+    nel = np.zeros(len(boxes), dtype=bool)
+    nel[:n_listed] = (gt.cell_flags[cell_of] & _lib.LVIS_CELL_NOT_EXHAUSTIVE) != 0
+    det_out = (darea[:, None] < lo[None, :]) | (darea[:, None] > hi[None, :]) | nel[:, None]   # an unmatched det: ignored by these
+    bits = np.repeat(det_out.astype(np.uint8) * 2, T, axis=1)
+    bits[~listed] = 0
+    bits[:n_listed][in_cell >= max_det] = 0
+    start = np.minimum(iou_thrs, 1 - 1e-10)
+    for c in np.nonzero((counts > 0) & (gcount > 0))[0]:
+        d0, g0, G = int(det_offsets[c]), int(gt.offsets[c]), int(gcount[c])
+        D = min(int(counts[c]), max_det)
+        gb = gt.box[g0:g0 + G]
+        sl = slice(d0, d0 + D)
+        w = np.minimum((dx[sl] + dw[sl])[:, None], (gb[:, 0] + gb[:, 2])[None, :]) - np.maximum(dx[sl][:, None], gb[None, :, 0])
+        h = np.minimum((dy[sl] + dh[sl])[:, None], (gb[:, 1] + gb[:, 3])[None, :]) - np.maximum(dy[sl][:, None], gb[None, :, 1])
+        inter = w * h
+        union = darea[sl][:, None] + (gb[:, 2] * gb[:, 3])[None, :] - inter
+        with np.errstate(divide="ignore", invalid="ignore"):
+            iou = np.where((w > 0) & (h > 0), inter / union, 0.0)
+        gig = gt_ignore[:, g0:g0 + G]
+        gtm = np.zeros((A, T, G), dtype=bool)
+        ai, ti = np.meshgrid(np.arange(A), np.arange(T), indexing="ij")
+        for d in range(D):
+            best = np.broadcast_to(start[None, :], (A, T)).copy()
+            m = np.full((A, T), -1, dtype=np.int64)
+            for g in range(G):                                                                 # the gts not ignored in the range
+                ok = ~gig[:, g, None] & ~gtm[:, :, g] & (iou[d, g] >= best)
+                best[ok] = iou[d, g]
+                m[ok] = g
+            second = m < 0
+            for g in range(G):                                                                 # nothing there: the ignored, once each
+                ok = second & gig[:, g, None] & ~gtm[:, :, g] & (iou[d, g] >= best)
+                best[ok] = iou[d, g]
+                m[ok] = g
+            matched = m >= 0
+            gtm[ai[matched], ti[matched], m[matched]] = True
+            ign = np.where(matched, second, det_out[d0 + d][:, None])
+            bits[d0 + d] = (matched.astype(np.uint8) | (ign.astype(np.uint8) << 1)).reshape(-1)
+    return bits, gt_ignore.astype(np.uint8), listed
+
+
+def summarize_lvis(precision, recall, freq_groups):
+    """LVISEval._summarize's thirteen numbers on precision [T, R, K, A] and recall [T, K, A]: AP, AP50, AP75, APs, APm, APl, APr,
+    APc, APf, AR@cap, ARs, ARm, ARl."""
+    def mean(s):
+        s = s[s > -1]
+        return -1.0 if s.size == 0 else float(np.mean(s))
+
+    stats = np.full(13, -1.0)
+    stats[0] = mean(precision[:, :, :, 0])
+    stats[1] = mean(precision[0, :, :, 0])
+    stats[2] = mean(precision[5, :, :, 0])
+    for i in range(1, 4):
+        stats[2 + i] = mean(precision[:, :, :, i])
+        stats[9 + i] = mean(recall[:, :, i])
+    for i, group in enumerate(freq_groups):
+        stats[6 + i] = mean(precision[:, :, group, 0])
+    stats[9] = mean(recall[:, :, 0])
+    return stats
+
+
+def derive_results_lvis(ev):
+    """Detectron2's LVISEvaluator: the nine AP metrics x 100 with no special case (-1 becomes -100.0); ev None: all nan."""
+    if ev is None:
+        return {metric: float("nan") for metric in LVIS_METRICS}
+    return {metric: float(ev["stats"][i] * 100) for i, metric in enumerate(LVIS_METRICS)}
+
+
+def evaluate_host_lvis(gt: _LVISGroundTruth, img_rank, cls, score, boxes, max_dets_per_image):
+    """The whole LVIS protocol on numpy arrays -> {"precision" [T, R, K, A], "recall" [T, K, A], "stats" [13]}."""
+    img_rank, cls = np.asarray(img_rank, dtype=np.int64), np.asarray(cls, dtype=np.int64)
+    score = np.asarray(score).astype(np.float64)
+    boxes = np.asarray(boxes, dtype=np.float32).reshape(-1, 4)
+    keep = np.nonzero(limit_host(img_rank, cls, score, gt.n_categories, max_dets_per_image))[0]
+    keep = keep[listed_host(gt, img_rank[keep], cls[keep])]                                    # the federated filter
+    img_rank, cls, score, boxes = img_rank[keep], cls[keep], score[keep], boxes[keep]
+    perm, det_offsets, rank, acc_index, cat_offsets = order_host(img_rank, cls, score, gt.n_images, gt.n_categories)
+    bits, gt_ignore, _ = match_host_lvis(gt, det_offsets, boxes[perm], max_dets_per_image)
+    precision, recall, _ = accumulate_host(cat_offsets, acc_index, rank[acc_index], score[perm][acc_index], bits,
+                                           npig_host(gt, gt_ignore), (max_dets_per_image,), len(IOU_THRS))
+    precision, recall = np.ascontiguousarray(precision[..., 0]), np.ascontiguousarray(recall[..., 0])
+    return dict(precision=precision, recall=recall, stats=summarize_lvis(precision, recall, gt.freq_groups))
+
+
+def evaluate_device_lvis(gt: _LVISGroundTruth, img_rank, cls, score, boxes, max_dets_per_image):
+    """The same on device tensors: the cap and the orderings by stable integer sorts, two launches, one copy to the host.  The
+    unlisted dets stay in their cells; locov_lvis_match marks them ignored, which leaves precision and recall unchanged."""
+    from . import ops
+    g = gt.on(boxes.device)
+    K, A, T, R = gt.n_categories, len(AREA_RNG), len(IOU_THRS), len(REC_THRS)
+    cls = ops.lvis_limit(img_rank, cls, score, gt.n_images, K, max_dets_per_image)
+    o = ops.coco_order(img_rank, cls, score, boxes, gt.n_images, K)
+    bits, gt_ignore = ops.lvis_match(o.det_offsets, g["offsets"], g["cell_flags"], o.boxes, g["box"], g["area"], g["ignore"], AREA_RNG,
+                                     IOU_THRS, max_dets_per_image)
+    c = torch.cat([torch.zeros((A, 1), dtype=torch.int64, device=boxes.device), torch.cumsum(gt_ignore == 0, dim=1)], dim=1)
+    npig = (c[:, g["cat_offsets"][1:]] - c[:, g["cat_offsets"][:-1]]).t().contiguous().to(torch.int32)
+    flat = ops.coco_accumulate(o.cat_offsets, o.acc_index, o.acc_rank, o.acc_score, bits, npig, T, (max_dets_per_image,), REC_THRS,
+                               with_scores=False)
+    host = flat.cpu().numpy()                                                  # the one device-to-host copy
+    n = T * R * K * A
+    precision, recall = host[:n].reshape(T, R, K, A), host[n:].reshape(T, K, A)
+    return dict(precision=precision, recall=recall, stats=summarize_lvis(precision, recall, gt.freq_groups))
+
+
+class LVISEvaluator(COCOEvaluator):
+    """Box AP under the LVIS protocol (module docstring), as Detectron2's LVISEvaluator reports it: AP, AP50, AP75, APs, APm, APl
+    and APr / APc / APf over the rare / common / frequent categories.
+
+    gt: an LVIS-format dict or the path of its JSON (images with neg_category_ids / not_exhaustive_category_ids, annotations,
+    categories with frequency).  class_names: one name per category in ascending category id (checked for length; LVIS reports no
+    per-category rows).  max_dets_per_image: the cap over all categories of an image.  device: where evaluate() runs.
+    process() and reset() are COCOEvaluator's; .eval holds {"precision" [T, R, K, A], "recall" [T, K, A], "stats" [13]}."""
+
+    def __init__(self, gt, class_names: Optional[Sequence[str]] = None, max_dets_per_image: int = 300, device=None):
+        if int(max_dets_per_image) != max_dets_per_image or max_dets_per_image < 1:
+            raise ValueError(f"max_dets_per_image must be a positive integer, got {max_dets_per_image!r}")
+        super().__init__(gt if isinstance(gt, _LVISGroundTruth) else _LVISGroundTruth(gt), class_names=class_names,
+                         max_dets=(int(max_dets_per_image),), device=device)
+        self.max_dets_per_image = int(max_dets_per_image)
+
+    def evaluate(self):
+        n = sum(self._counts)
+        if n == 0:
+            self.eval = None
+            return OrderedDict(bbox=derive_results_lvis(None))
+        device = self._device or self._boxes[0].device
+        on_device = device.type == "cuda" and _fused() and device_supported(self._gt, n, self.max_dets)
+        img_rank, cls, score, boxes = self._gathered(device if on_device else torch.device("cpu"))
+        if on_device:
+            self.eval = evaluate_device_lvis(self._gt, img_rank, cls, score, boxes, self.max_dets_per_image)
+        else:
+            self.eval = evaluate_host_lvis(self._gt, img_rank.numpy(), cls.numpy(), score.numpy(), boxes.numpy(), self.max_dets_per_image)
+        return OrderedDict(bbox=derive_results_lvis(self.eval))
+
+
+def build_evaluator(dataset_name: str, gt, **kwargs):
+    """The box branch of the reference's select_and_build_evaluator (ovr/evaluation/evaluator.py:39-50): a dataset whose name
+    contains "lvis" is scored under the LVIS protocol, any other under COCO's."""
+    return LVISEvaluator(gt, **kwargs) if "lvis" in dataset_name else COCOEvaluator(gt, **kwargs)

@@ -3066,3 +3066,57 @@ def coco_accumulate(cat_offsets: torch.Tensor, acc_index: torch.Tensor, acc_rank
                                                 rec.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), R, _ptr(precision), _ptr(recall),
                                                 _ptr(scores), _stream(det_bits)), "locov_coco_accumulate")
     return flat
+
+
+# --------------------------------------------------------------------------------------
+# LVIS-protocol box evaluation: the same kernels under the federated rules (evaluation.py's docstring states them).
+def lvis_limit(img_rank: torch.Tensor, cls: torch.Tensor, score: torch.Tensor, n_images: int, n_categories: int,
+               max_dets_per_image: int) -> torch.Tensor:
+    """LVISResults.limit_dets_per_image without a host read: -> cls with every det past its image's first max_dets_per_image (of a
+    stable sort by descending score, over all categories together) sent to class K, the trailing cell coco_order leaves unread.
+    Two stable sorts on integer keys (descending score, then image rank) and the position inside the image.  A class outside
+    [0, K) is left out before the cap: it takes no place among its image's dets."""
+    score = _dev(score, "score", torch.float64)
+    img_rank, cls = _dev(img_rank, "img_rank", torch.int64), _dev(cls, "cls", torch.int64)
+    I, K, N = int(n_images), int(n_categories), score.shape[0]
+    dev = score.device
+    image = torch.where((cls >= 0) & (cls < K), img_rank, torch.full_like(img_rank, I))
+    p1 = torch.sort(_descending_key(score), stable=True).indices
+    image, p2 = torch.sort(image[p1], stable=True)
+    perm = p1[p2]
+    first = torch.searchsorted(image, torch.arange(I + 1, dtype=torch.int64, device=dev))
+    pos = torch.arange(N, dtype=torch.int64, device=dev) - first[image]
+    return cls.scatter(0, perm, torch.where(pos >= int(max_dets_per_image), torch.full_like(cls, K), cls[perm]))
+
+
+def lvis_match(det_offsets: torch.Tensor, gt_offsets: torch.Tensor, cell_flags: torch.Tensor, det_boxes: torch.Tensor,
+               gt_boxes: torch.Tensor, gt_area: torch.Tensor, gt_ignore_in: torch.Tensor, area_ranges, iou_thresholds, max_det: int):
+    """locov_lvis_match: -> det_bits uint8 [N, A * T] (bit 0 matched, bit 1 ignored; 2 for every det of an unlisted cell),
+    gt_ignore uint8 [A, G].  One launch, no host read.  As coco_match, with cell_flags uint8 [C] (_lib.LVIS_CELL_NEG |
+    _lib.LVIS_CELL_NOT_EXHAUSTIVE) and gt_ignore_in uint8 [G] (the annotation's ignore field) in place of gt_crowd."""
+    import numpy as np
+    det_offsets, gt_offsets = _dev(det_offsets, "det_offsets", torch.int32), _dev(gt_offsets, "gt_offsets", torch.int32)
+    cell_flags = _dev(cell_flags, "cell_flags", torch.uint8)
+    det_boxes = _dev(det_boxes, "det_boxes")
+    gt_boxes, gt_area = _dev(gt_boxes, "gt_boxes", torch.float64), _dev(gt_area, "gt_area", torch.float64)
+    gt_ignore_in = _dev(gt_ignore_in, "gt_ignore_in", torch.uint8)
+    C, N, G = det_offsets.shape[0] - 1, det_boxes.shape[0], gt_area.shape[0]
+    if (gt_offsets.shape[0] != C + 1 or cell_flags.shape[0] != C or det_boxes.shape != (N, 4) or gt_boxes.shape != (G, 4)
+            or gt_ignore_in.shape[0] != G):
+        raise ValueError("lvis_match: offsets of C + 1 entries each, cell_flags [C], det_boxes [N,4], gt_boxes [G,4], gt_area [G], "
+                         "gt_ignore_in [G]")
+    ar = np.ascontiguousarray(area_ranges, dtype=np.float64).reshape(-1, 2)
+    th = np.ascontiguousarray(iou_thresholds, dtype=np.float64).reshape(-1)
+    A, T = len(ar), len(th)
+    dev = det_boxes.device
+    bits = torch.empty((N, A * T), dtype=torch.uint8, device=dev)
+    gt_ignore = torch.empty((A, G), dtype=torch.uint8, device=dev)
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        ws_bytes = int(lib.locov_coco_match_workspace_bytes(G, int(max_det))) if N and G else 0
+        ws = _workspace("coco_match", det_boxes, ws_bytes) if ws_bytes else None
+        dp = ctypes.POINTER(ctypes.c_double)
+        check(lib.locov_lvis_match(_ptr(det_offsets), _ptr(gt_offsets), _ptr(cell_flags), C, N, G, int(max_det), _ptr(det_boxes),
+                                   _ptr(gt_boxes), _ptr(gt_area), _ptr(gt_ignore_in), ar.ctypes.data_as(dp), A, th.ctypes.data_as(dp), T,
+                                   _ptr(bits), _ptr(gt_ignore), _ptr(ws), ws_bytes, _stream(det_boxes)), "locov_lvis_match")
+    return bits, gt_ignore

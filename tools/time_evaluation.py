@@ -1,7 +1,8 @@
-"""COCOEvaluator.evaluate() on the device (csrc/coco_eval.hip) against the package's host path, on synthetic sets of COCO-val size.
+"""COCOEvaluator.evaluate() / LVISEvaluator.evaluate() on the device (csrc/coco_eval.hip) against the package's host path, on
+synthetic sets of COCO-val / LVIS-val size.
 
-    timeout -k 10 900 python tools/time_evaluation.py [--images 5000] [--categories 80 1203] [--repeats 7] [--warmup 2]
-                                                      [--host-repeats 2] [--out records.json]
+    timeout -k 10 900 python tools/time_evaluation.py [--protocol coco|lvis] [--images 5000] [--categories 80 1203] [--repeats 7]
+                                                      [--warmup 2] [--host-repeats 2] [--out records.json]
 
 A set: `images` images, `categories` categories, 7 gts and 100 dets per image from a seed (60 dets are jittered copies of the
 image's gts with their class, 40 are random boxes of random classes; 5 % of the gts are crowd; fp32 scores).  The dets are fed as
@@ -11,7 +12,13 @@ Per set: the wall time of evaluate() on the device (it ends in its one device-to
 runs after `warmup`, median and 10th / 90th percentile; the same steps once more with a device synchronisation after each, to
 state the share of the gathering of the per-image tensors, the orderings (four stable sorts and two searches), the match launch,
 the accumulate launch, and the copy with the host's means; the host path's evaluate() `host-repeats` times; and whether the two
-paths' arrays are equal bit for bit.  Needs a ROCm GPU."""
+paths' arrays are equal bit for bit.  Needs a ROCm GPU.
+
+--protocol lvis (categories default to 1203): a federated set from a seed -- per image 11 gts over 4 of its categories (3 % with
+ignore = 1), 6 neg_category_ids and 1 not_exhaustive_category_id (drawn from all categories, so now and then a positive one), and
+300 dets (120 jittered copies of the image's gts with their class, 60 random boxes of its negative categories, 120 random boxes of
+random classes, nearly all of them unlisted); 320 dets are fed for every tenth image, so the cap of 300 acts; the categories are
+rare / common / frequent 337 : 461 : 405, as in LVIS v1.  The steps then start with the cap (ops.lvis_limit)."""
 from __future__ import annotations
 
 import argparse
@@ -57,6 +64,38 @@ def synthetic(n_images, n_categories, seed=0, gts_per_image=7, dets_per_image=10
     return gt, per_image
 
 
+def synthetic_lvis(n_images, n_categories, seed=0, gts_per_image=11, pos_cats=4, n_neg=6, n_nel=1, dets_per_image=300, matched=120,
+                   on_neg=60):
+    """-> the LVIS-format gt dict and per image (image_id, boxes fp32 [300 or 320, 4] XYXY, scores fp32, classes int64)."""
+    rng = np.random.default_rng(seed)
+    K = n_categories
+    freq = np.array(["r"] * (337 * K // 1203) + ["c"] * (461 * K // 1203) + ["f"] * K)[:K][rng.permutation(K)]
+    anns, images, per_image = [], [], []
+    for img in range(1, n_images + 1):
+        wh = rng.choice([12.0, 24.0, 48.0, 80.0, 140.0, 260.0], size=(gts_per_image, 2)) * rng.uniform(0.7, 1.3, size=(gts_per_image, 2))
+        xy = rng.uniform(0, 400, size=(gts_per_image, 2))
+        pos = rng.choice(K, size=min(pos_cats, K), replace=False)
+        cat = pos[rng.integers(0, len(pos), size=gts_per_image)]
+        for g in range(gts_per_image):
+            anns.append(dict(id=len(anns) + 1, image_id=img, category_id=int(cat[g]) + 1, ignore=int(rng.random() < 0.03),
+                             bbox=[float(xy[g, 0]), float(xy[g, 1]), float(wh[g, 0]), float(wh[g, 1])], area=float(wh[g, 0] * wh[g, 1])))
+        neg = np.setdiff1d(rng.choice(K, size=min(n_neg, K), replace=False), cat)
+        nel = rng.choice(K, size=min(n_nel, K), replace=False)
+        images.append(dict(id=img, neg_category_ids=[int(c) + 1 for c in neg], not_exhaustive_category_ids=[int(c) + 1 for c in nel]))
+        n = dets_per_image + (20 if img % 10 == 0 else 0)
+        pick = rng.integers(0, gts_per_image, size=matched)
+        bxy = xy[pick] + rng.normal(0, 4, size=(matched, 2))
+        bwh = wh[pick] * rng.uniform(0.8, 1.25, size=(matched, 2))
+        rxy, rwh = rng.uniform(0, 400, size=(n - matched, 2)), rng.uniform(8, 200, size=(n - matched, 2))
+        x1y1 = np.concatenate([bxy, rxy])
+        boxes = np.concatenate([x1y1, x1y1 + np.concatenate([bwh, rwh])], axis=1).astype(np.float32)
+        neg_cls = neg[rng.integers(0, len(neg), size=on_neg)] if len(neg) else rng.integers(0, K, size=on_neg)
+        classes = np.concatenate([cat[pick], neg_cls, rng.integers(0, K, size=n - matched - on_neg)]).astype(np.int64)
+        per_image.append((img, boxes, rng.random(n).astype(np.float32), classes))
+    gt = dict(images=images, annotations=anns, categories=[dict(id=c + 1, name=f"c{c}", frequency=str(freq[c])) for c in range(K)])
+    return gt, per_image
+
+
 def feed(evaluator, per_image, device):
     from locov_amd.structures import Boxes, Instances
     evaluator.reset()
@@ -99,11 +138,54 @@ def staged(ev, dev):
     return t
 
 
+def staged_lvis(ev, dev):
+    """evaluate_device_lvis's steps with a synchronisation after each -> milliseconds per step."""
+    from locov_amd import evaluation as E, ops
+    t, marks = {}, [time.perf_counter()]
+
+    def mark(name):
+        torch.cuda.synchronize(dev)
+        marks.append(time.perf_counter())
+        t[name] = (marks[-1] - marks[-2]) * 1e3
+
+    gt, cap = ev._gt, ev.max_dets_per_image
+    img_rank, cls, score, boxes = ev._gathered(dev)
+    mark("gather")
+    g = gt.on(dev)
+    cls = ops.lvis_limit(img_rank, cls, score, gt.n_images, gt.n_categories, cap)
+    mark("cap")
+    o = ops.coco_order(img_rank, cls, score, boxes, gt.n_images, gt.n_categories)
+    mark("orderings")
+    bits, gt_ignore = ops.lvis_match(o.det_offsets, g["offsets"], g["cell_flags"], o.boxes, g["box"], g["area"], g["ignore"], E.AREA_RNG,
+                                     E.IOU_THRS, cap)
+    mark("match")
+    c = torch.cat([torch.zeros((len(E.AREA_RNG), 1), dtype=torch.int64, device=dev), torch.cumsum(gt_ignore == 0, dim=1)], dim=1)
+    npig = (c[:, g["cat_offsets"][1:]] - c[:, g["cat_offsets"][:-1]]).t().contiguous().to(torch.int32)
+    mark("npig")
+    flat = ops.coco_accumulate(o.cat_offsets, o.acc_index, o.acc_rank, o.acc_score, bits, npig, len(E.IOU_THRS), (cap,), E.REC_THRS,
+                               with_scores=False)
+    mark("accumulate")
+    host = flat.cpu().numpy()
+    mark("copy")
+    K, A, T, R = gt.n_categories, len(E.AREA_RNG), len(E.IOU_THRS), len(E.REC_THRS)
+    n = T * R * K * A
+    E.summarize_lvis(host[:n].reshape(T, R, K, A), host[n:].reshape(T, K, A), gt.freq_groups)
+    mark("means")
+    return t
+
+
 def measure(n_images, n_categories, args, dev):
-    from locov_amd.evaluation import COCOEvaluator
+    from locov_amd.evaluation import COCOEvaluator, LVISEvaluator
+    stage = staged
     t0 = time.perf_counter()
-    gt, per_image = synthetic(n_images, n_categories)
-    on_dev, on_host = COCOEvaluator(gt), COCOEvaluator(gt)
+    if args.protocol == "lvis":
+        gt, per_image = synthetic_lvis(n_images, n_categories)
+        on_dev, on_host = LVISEvaluator(gt), LVISEvaluator(gt)
+        stage, keys = staged_lvis, ("precision", "recall", "stats")
+    else:
+        gt, per_image = synthetic(n_images, n_categories)
+        on_dev, on_host = COCOEvaluator(gt), COCOEvaluator(gt)
+        keys = ("precision", "recall", "scores", "stats")
     rec = {"images": n_images, "categories": n_categories, "dets": sum(len(p[2]) for p in per_image), "gts": len(gt["annotations"]),
            "build_s": time.perf_counter() - t0}
     feed(on_dev, per_image, dev)
@@ -116,7 +198,7 @@ def measure(n_images, n_categories, args, dev):
         if it >= args.warmup:
             wall.append((time.perf_counter() - t0) * 1e3)
     rec["device_evaluate"] = spread(wall)
-    stages = [staged(on_dev, dev) for _ in range(args.warmup + args.repeats)][args.warmup:]
+    stages = [stage(on_dev, dev) for _ in range(args.warmup + args.repeats)][args.warmup:]
     rec["device_stages_ms"] = {k: float(np.median([s[k] for s in stages])) for k in stages[0]}
     total = sum(rec["device_stages_ms"].values())
     rec["device_stage_share"] = {k: v / total for k, v in rec["device_stages_ms"].items()}
@@ -129,21 +211,28 @@ def measure(n_images, n_categories, args, dev):
         host.append((time.perf_counter() - t0) * 1e3)
         print(json.dumps({f"{n_categories} categories, host evaluate ms": host[-1]}), flush=True)
     rec["host_evaluate"] = spread(host)
-    rec["equal_bits"] = all(on_dev.eval[k].tobytes() == on_host.eval[k].tobytes() for k in ("precision", "recall", "scores", "stats"))
+    rec["equal_bits"] = all(on_dev.eval[k].tobytes() == on_host.eval[k].tobytes() for k in keys)
     rec["AP"], rec["AP50"] = res["bbox"]["AP"], res_host["bbox"]["AP50"]
+    if args.protocol == "lvis":
+        rec["protocol"] = "lvis"
+        rec["APr"], rec["APc"], rec["APf"] = (res["bbox"][k] for k in ("APr", "APc", "APf"))
+        assert rec["equal_bits"], "the device path and the host path differ"
     rec["speedup_median"] = rec["host_evaluate"]["median_ms"] / rec["device_evaluate"]["median_ms"]
     return rec
 
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--protocol", choices=("coco", "lvis"), default="coco")
     ap.add_argument("--images", type=int, default=5000)
-    ap.add_argument("--categories", type=int, nargs="+", default=[80, 1203])
+    ap.add_argument("--categories", type=int, nargs="+", default=None)
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--host-repeats", type=int, default=2)
     ap.add_argument("--out", default=None)
     args = ap.parse_args(argv)
+    if args.categories is None:
+        args.categories = [1203] if args.protocol == "lvis" else [80, 1203]
     if not torch.cuda.is_available():
         raise SystemExit("time_evaluation: needs a ROCm GPU")
     dev = torch.device("cuda:0")
