@@ -39,7 +39,8 @@ extern "C" {
  *    locov_rpn_label_anchors (+ _workspace_bytes), locov_rpn_sample_anchors, locov_rpn_loss (+ _workspace_bytes),
  *    locov_resnet_stem_fwd, locov_resnet_stem_fwd_sel, locov_resnet_stem_wgrad (+ _workspace_bytes),
  *    locov_preprocess_images, locov_detector_rescale, locov_sgd_step (+ _workspace_bytes),
- *    locov_coco_match (+ _workspace_bytes), locov_coco_accumulate, locov_lvis_match */
+ *    locov_coco_match (+ _workspace_bytes), locov_coco_accumulate, locov_lvis_match,
+ *    locov_resize_flip_images, locov_resize_supported */
 #define LOCOV_ABI_VERSION 8
 
 #define LOCOV_OK 0
@@ -1335,6 +1336,41 @@ int locov_preprocess_images(const void *const *images_host, const int *heights_h
 int locov_detector_rescale(const float *boxes, const int *roff_host, const float *scale_x_host, const float *scale_y_host,
                            const int *out_h_host, const int *out_w_host, int n_images, float *out_boxes, int64_t *src, int *counts,
                            locov_stream_t stream);
+
+/* ---- the image side of the dataset mapper in one launch for the whole batch (csrc/image_resize.hip) ---------------------------
+ * Added under ABI version 8.  What BasicTextImageDatasetMapper.__call__ (ovr/data/mappers/basic_mappers.py:116-124) does to the
+ * decoded image under every shipped config: [D2-upstream] ResizeShortestEdge -> ResizeTransform.apply_image (Pillow's
+ * Image.resize(..., BILINEAR) on uint8), RandomFlip -> HFlipTransform / VFlipTransform, then image.transpose(2, 0, 1).
+ *
+ * locov_resize_flip_images: out_n[c, y', x'] = resized_n[y, x, c], with (y', x') = (y, x), (y, ow - 1 - x) or (oh - 1 - y, x).
+ *   images_host : host array of n_images DEVICE pointers; image n is uint8 [heights_host[n], widths_host[n], channels],
+ *                 contiguous, aligned to one byte only.  One channel count (1 .. LOCOV_IMAGE_MAX_CHANNELS) per call.
+ *   outs_host   : host array of n_images DEVICE pointers; output n is uint8 [channels, out_heights_host[n], out_widths_host[n]],
+ *                 contiguous, aligned to one byte only, not overlapping any input.  EVERY byte of it is written, nothing else.
+ *   flips_host  : per image LOCOV_FLIP_NONE, LOCOV_FLIP_HORIZONTAL or LOCOV_FLIP_VERTICAL, applied AFTER the resize.
+ *   `resized` is Pillow's ImagingResample for 8-bit channels with the bilinear filter, bit for bit.  Per axis, in fp64 with every
+ *   operation rounded on its own (scale = in / out, fs = max(scale, 1), support = fs):
+ *     center = (xx + 0.5) * scale;  xmin = max((int)(center - support + 0.5), 0);  xmax = min((int)(center + support + 0.5), in) - xmin
+ *     w[x] = f((x + xmin - center + 0.5) * (1 / fs)), f(t) = 1 - |t| below 1 and 0 from there;  w[x] /= sum of the w[x] (if != 0)
+ *     k[x] = (int)(w[x] * 2^22 + 0.5)   (- 0.5 for a negative weight; the conversion truncates)
+ *   and each pass is clamp((2^21 + sum k[x] * pixel[xmin + x]) >> 22, 0, 255) in int32.  The horizontal pass comes first and its
+ *   ROUNDED bytes are what the vertical pass reads; a pass between equal sizes is the identity by these formulas.
+ *   The taps are formed on the device from the sizes: no coefficient upload, no workspace, nothing read by the host.  One launch:
+ *   a workgroup owns 16 x 64 output pixels of one image and keeps the horizontal pass of the source rows its band needs in LDS.
+ *   No atomics; vector stores only; two calls give the same bits.
+ *   Supported: every upscale, and every downscale of at most LOCOV_RESIZE_MAX_TAPS taps per axis, i.e. ceil(in / out) <= 8 (a
+ *   factor of 8 per axis); locov_resize_supported answers for one image without a launch (1 / 0).
+ *   n_images == 0: LOCOV_OK, nothing is touched.  More than LOCOV_LABEL_MAX_IMAGES images, a null pointer, a size < 1, channels
+ *   outside 1 .. 4, an unknown flip, more taps than the limit, h * w * channels or oh * ow * channels above 2^31 - 1 (the kernel's
+ *   offsets within an image are int32 quantities): LOCOV_ERR_INVALID_ARG before any HIP call. */
+#define LOCOV_RESIZE_MAX_TAPS 17
+#define LOCOV_FLIP_NONE 0
+#define LOCOV_FLIP_HORIZONTAL 1
+#define LOCOV_FLIP_VERTICAL 2
+int locov_resize_supported(int in_h, int in_w, int out_h, int out_w, int channels);
+int locov_resize_flip_images(const void *const *images_host, const int *heights_host, const int *widths_host, void *const *outs_host,
+                             const int *out_heights_host, const int *out_widths_host, const int *flips_host, int n_images, int channels,
+                             locov_stream_t stream);
 
 /* ---- the caption path of the LSM step in one launch (csrc/caption.hip): BertEmbedding after the tokenizer --------------------
  * (ovr/modeling/language/transf_models.py:105-154).  Added under ABI version 8.

@@ -26,3 +26,5 @@ from .solver import (FusedSGD, WarmupCosineLR, WarmupMultiStepLR, build_lr_sched
                      get_default_optimizer_params)
 from . import evaluation  # noqa: F401,E402
 from .evaluation import COCOEvaluator, LVISEvaluator, build_evaluator, inference_on_dataset  # noqa: F401,E402
+from . import data  # noqa: F401,E402
+from .data import DatasetMapper, build_augmentation, iterate_batches, resize_bilinear_host  # noqa: F401,E402

@@ -46,6 +46,7 @@ SGD_CLIP_NONE, SGD_CLIP_VALUE, SGD_CLIP_NORM = 0, 1, 2
 COCO_MAX_AREAS, COCO_MAX_THRESHOLDS, COCO_MAX_CAPS, COCO_MAX_RECALL_THRESHOLDS = 4, 16, 3, 256
 COCO_MAX_DET, COCO_MAX_BLOCKS = 4096, 8388608
 LVIS_CELL_NEG, LVIS_CELL_NOT_EXHAUSTIVE = 1, 2
+RESIZE_MAX_TAPS, FLIP_NONE, FLIP_HORIZONTAL, FLIP_VERTICAL = 17, 0, 1, 2
 
 _p = c_void_p  # device pointer
 
@@ -244,6 +245,9 @@ SIGNATURES = {
                                       _p, _p, _p, _p]),
     "locov_lvis_match": (c_int, [_p, _p, _p, c_int64, c_int, c_int, c_int, _p, _p, _p, _p, POINTER(c_double), c_int, POINTER(c_double), c_int,
                                  _p, _p, _p, c_int64, _p]),
+    "locov_resize_supported": (c_int, [c_int, c_int, c_int, c_int, c_int]),
+    "locov_resize_flip_images": (c_int, [POINTER(c_void_p), POINTER(c_int), POINTER(c_int), POINTER(c_void_p), POINTER(c_int),
+                                         POINTER(c_int), POINTER(c_int), c_int, c_int, _p]),
 }
 
 _lib = None

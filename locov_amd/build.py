@@ -43,6 +43,7 @@ FILE_FLAGS = {
     "image_batch.hip": ["-ffp-contract=off"],    # ((x - mean) / std and box * scale as the torch ops round them: the bit-identity tests)
     "nms.hip": ["-ffp-contract=off"],          # (select_common.h's box_iou_gt, rounded as in detect.hip / rpn.hip: the bit-identity tests)
     "coco_eval.hip": ["-ffp-contract=off"],    # (fp64 IoU and precision, each step rounded on its own: bit-equal to numpy)
+    "image_resize.hip": ["-ffp-contract=off"],   # (Pillow's fp64 resampling weights, each step rounded on its own: bit-equal taps)
 }
 
 

@@ -203,7 +203,15 @@ def get_cfg() -> CfgNode:
                 "DEPTH": 50, "OUT_FEATURES": ["res4"], "STEM_OUT_CHANNELS": 64, "RES5_DILATION": 1,     # [D2-upstream] (backbone.py)
             },
         },
-        "INPUT": {"FORMAT": "BGR"},                                # [D2-upstream]
+        "INPUT": {                                                 # [D2-upstream] (data.py: build_augmentation, DatasetMapper)
+            "FORMAT": "BGR",
+            "MIN_SIZE_TRAIN": (800,), "MIN_SIZE_TRAIN_SAMPLING": "choice", "MAX_SIZE_TRAIN": 1333,
+            "MIN_SIZE_TEST": 800, "MAX_SIZE_TEST": 1333,
+            "RANDOM_FLIP": "horizontal",                           # "horizontal", "vertical" or "none" (config.py:166)
+            "CROP": {"ENABLED": False},                            # True is refused: RandomCrop is not built
+            # config.py:168-174, the strong augmentations: off in both yaml files; anything else is refused (not built)
+            "COLOR_JITTER": 0.0, "RANDOM_GRAY_SCALE": False, "GAUSSIAN_BLUR": False, "RANDOM_ERASE": False,
+        },
         "VIS_PERIOD": 0,                                           # [D2-upstream]; > 0 is refused (meta_arch.py)
         "TEST": {"DETECTIONS_PER_IMAGE": 100},                     # [D2-upstream]
         "DATASETS": {"TRAIN": ()},                                 # [D2-upstream] (USE_FED_LOSS: whose class_image_count to read)

@@ -1,0 +1,469 @@
+"""From a decoded image to the dict the models take: the reference's dataset mapper, its image side on the device.
+
+The reference's BasicTextImageDatasetMapper.__call__ (ovr/data/mappers/basic_mappers.py:90-192) reduces, for every shipped config, to
+Detectron2's build_augmentation -- ResizeShortestEdge plus, in training, RandomFlip -- because the strong augmentations of
+ovr/data/detection_utils.py:60-100 are off by default and in coco_lsm.yaml / coco_stt.yaml.  ResizeTransform.apply_image resizes
+uint8 images with Pillow: Image.fromarray(img).resize((new_w, new_h), Image.BILINEAR).
+
+As in evaluation.py the numpy path of this module is the DEFINITION:
+
+  * resize_bilinear_host restates Pillow's ImagingResample (public Resample.c) for 8-bit channels and the bilinear filter, byte for
+    byte.  Per axis, in float64: scale = in / out, fs = max(scale, 1), support = fs, and for output index xx
+        center = (xx + 0.5) * scale;  xmin = max(int(center - support + 0.5), 0);  xmax = min(int(center + support + 0.5), in) - xmin
+        w[x] = f((x + xmin - center + 0.5) * (1 / fs)), f(t) = 1 - |t| below 1, else 0;  w /= sum(w) (summed in order, if != 0)
+        k[x] = int(w[x] * 2^22 + 0.5)     (- 0.5 for a negative weight; int() truncates)
+    and a pass is clamp((2^21 + sum k[x] * pixel[xmin + x]) >> 22, 0, 255) in int32.  The horizontal pass comes first and writes
+    uint8; the vertical pass reads those rounded bytes.  A pass between equal sizes is skipped (it is the identity anyway).
+  * the device path (ops.resize_flip_images: csrc/image_resize.hip) does resize, flip and the HWC -> CHW transposition of a whole
+    batch in one launch and gives the same bytes.  The host path serves CPU tensors, LOCOV_FUSED_RESIZE=0 and the sizes outside
+    ops.resize_supported.
+
+[D2-upstream] (restated from Detectron2's public sources, unverified here: Detectron2 is not installed): ResizeShortestEdge,
+RandomFlip, build_augmentation, the transforms' apply_coords / apply_box, BoxMode.convert, transform_instance_annotations,
+filter_empty_instances.  annotations_to_instances and check_image_size are the reference's own (ovr/data/detection_utils.py:21-58,
+272-352).  The box side stays on the host, in float64 numpy as upstream: a handful of boxes per image.
+
+Not built: INPUT.CROP, the strong augmentations (COLOR_JITTER, RANDOM_GRAY_SCALE, GAUSSIAN_BLUR, RANDOM_ERASE), masks, keypoints,
+precomputed proposals, the NOISE_* options -- the first two groups are refused with an error, never ignored.
+"""
+from __future__ import annotations
+
+import copy
+import math
+import os
+import random
+from typing import Dict, Iterable, Iterator, List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from .structures import Boxes, Instances
+
+PRECISION_BITS = 22                      # Pillow's PRECISION_BITS for 8-bit channels: 32 - 8 - 2
+XYXY_ABS, XYWH_ABS = 0, 1                # [D2-upstream] BoxMode
+FLIP_NONE, FLIP_HORIZONTAL, FLIP_VERTICAL = 0, 1, 2
+
+
+# ---- Pillow's resampling -------------------------------------------------------------------------------------------------------
+
+def bilinear_coefficients(in_size: int, out_size: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """precompute_coeffs + normalize_coeffs_8bpc for the bilinear filter: (xmin [out], count [out], k [out, ksize] int32), the
+    row of k behind count zero."""
+    scale = float(in_size) / float(out_size)
+    fs = max(scale, 1.0)
+    support = 1.0 * fs
+    ksize = int(math.ceil(support)) * 2 + 1
+    ss = 1.0 / fs
+    center = (np.arange(out_size, dtype=np.float64) + 0.5) * scale
+    xmin = np.maximum((center - support + 0.5).astype(np.int64), 0)                  # (astype truncates, as C's (int))
+    count = np.minimum((center + support + 0.5).astype(np.int64), in_size) - xmin
+    w = np.zeros((out_size, ksize), dtype=np.float64)
+    ww = np.zeros(out_size, dtype=np.float64)
+    for x in range(ksize):
+        t = np.abs(((x + xmin).astype(np.float64) - center + 0.5) * ss)
+        w[:, x] = np.where((x < count) & (t < 1.0), 1.0 - t, 0.0)
+        ww = ww + w[:, x]                                                            # in order; the zeros behind count change nothing
+    nz = ww != 0.0
+    w[nz] = w[nz] / ww[nz, None]
+    k = np.where(w < 0.0, -0.5 + w * float(1 << PRECISION_BITS), 0.5 + w * float(1 << PRECISION_BITS)).astype(np.int32)
+    return xmin, count, k
+
+
+def _resample_axis0(img: np.ndarray, out_size: int) -> np.ndarray:
+    """One pass along axis 0 of a uint8 array [in, ...]."""
+    xmin, _, k = bilinear_coefficients(img.shape[0], out_size)
+    acc = np.full((out_size,) + img.shape[1:], 1 << (PRECISION_BITS - 1), dtype=np.int32)
+    tail = (slice(None),) + (None,) * (img.ndim - 1)
+    for x in range(k.shape[1]):
+        rows = np.minimum(xmin + x, img.shape[0] - 1)                                # (behind count the tap is 0)
+        acc += k[:, x][tail] * img[rows].astype(np.int32)
+    return np.clip(acc >> PRECISION_BITS, 0, 255).astype(np.uint8)
+
+
+def resize_bilinear_host(img, new_h: int, new_w: int) -> np.ndarray:
+    """np.asarray(Image.fromarray(img).resize((new_w, new_h), Image.BILINEAR)) for uint8 [H, W, C] (or [H, W]), without Pillow."""
+    img = np.asarray(img)
+    if img.dtype != np.uint8 or img.ndim not in (2, 3):
+        raise TypeError(f"resize_bilinear_host: a uint8 [H, W, C] image, got {img.dtype} {img.shape}")
+    new_h, new_w = int(new_h), int(new_w)
+    if min(img.shape[:2]) < 1 or new_h < 1 or new_w < 1:
+        raise ValueError(f"resize_bilinear_host: sizes must be positive, got {img.shape[:2]} -> {(new_h, new_w)}")
+    if new_w != img.shape[1]:
+        img = np.swapaxes(_resample_axis0(np.swapaxes(img, 0, 1), new_w), 0, 1)
+    if new_h != img.shape[0]:
+        img = _resample_axis0(img, new_h)
+    return np.ascontiguousarray(img)
+
+
+# ---- [D2-upstream] transforms: what they do to an image and to coordinates -----------------------------------------------------
+
+class NoOpTransform:
+    flip = FLIP_NONE
+
+    def output_shape(self, h: int, w: int) -> Tuple[int, int]:
+        return h, w
+
+    def apply_image(self, img: np.ndarray) -> np.ndarray:
+        return img
+
+    def apply_coords(self, coords: np.ndarray) -> np.ndarray:
+        return coords
+
+    def apply_box(self, box: np.ndarray) -> np.ndarray:
+        """Transform.apply_box: the four corners through apply_coords, then their min / max."""
+        idxs = np.array([(0, 1), (2, 1), (0, 3), (2, 3)]).flatten()
+        coords = np.asarray(box).reshape(-1, 4)[:, idxs].reshape(-1, 2)
+        coords = self.apply_coords(coords).reshape((-1, 4, 2))
+        return np.concatenate((coords.min(axis=1), coords.max(axis=1)), axis=1)
+
+
+class ResizeTransform(NoOpTransform):
+    def __init__(self, h: int, w: int, new_h: int, new_w: int):
+        self.h, self.w, self.new_h, self.new_w = int(h), int(w), int(new_h), int(new_w)
+
+    def output_shape(self, h, w):
+        return self.new_h, self.new_w
+
+    def apply_image(self, img):
+        assert img.shape[:2] == (self.h, self.w)
+        return resize_bilinear_host(img, self.new_h, self.new_w)
+
+    def apply_coords(self, coords):
+        coords[:, 0] = coords[:, 0] * (self.new_w * 1.0 / self.w)
+        coords[:, 1] = coords[:, 1] * (self.new_h * 1.0 / self.h)
+        return coords
+
+
+class HFlipTransform(NoOpTransform):
+    flip = FLIP_HORIZONTAL
+
+    def __init__(self, width: int):
+        self.width = int(width)
+
+    def apply_image(self, img):
+        return np.flip(img, axis=1)
+
+    def apply_coords(self, coords):
+        coords[:, 0] = self.width - coords[:, 0]
+        return coords
+
+
+class VFlipTransform(NoOpTransform):
+    flip = FLIP_VERTICAL
+
+    def __init__(self, height: int):
+        self.height = int(height)
+
+    def apply_image(self, img):
+        return np.flip(img, axis=0)
+
+    def apply_coords(self, coords):
+        coords[:, 1] = self.height - coords[:, 1]
+        return coords
+
+
+class TransformList:
+    def __init__(self, transforms: Sequence[NoOpTransform]):
+        self.transforms = list(transforms)
+
+    def apply_image(self, img):
+        for t in self.transforms:
+            img = t.apply_image(img)
+        return img
+
+    def apply_coords(self, coords):
+        for t in self.transforms:
+            coords = t.apply_coords(coords)
+        return coords
+
+    def apply_box(self, box):
+        for t in self.transforms:
+            box = t.apply_box(box)
+        return box
+
+
+class ResizeShortestEdge:
+    """short_edge_length: the choices ("choice") or the [min, max] range ("range"); a drawn size of 0 is a no-op."""
+
+    def __init__(self, short_edge_length, max_size: int = 2 ** 31 - 1, sample_style: str = "range"):
+        assert sample_style in ("range", "choice"), sample_style
+        self.is_range = sample_style == "range"
+        if isinstance(short_edge_length, int):
+            short_edge_length = (short_edge_length, short_edge_length)
+        if self.is_range:
+            assert len(short_edge_length) == 2, f"short_edge_length must be two values using 'range' sample style. Got {short_edge_length}!"
+        self.short_edge_length, self.max_size = tuple(int(v) for v in short_edge_length), int(max_size)
+
+    def draw(self, rng: random.Random) -> int:
+        if self.is_range:
+            return rng.randint(self.short_edge_length[0], self.short_edge_length[1])
+        return rng.choice(self.short_edge_length)
+
+    @staticmethod
+    def get_output_shape(oldh: int, oldw: int, short_edge_length: int, max_size: int) -> Tuple[int, int]:
+        h, w = oldh, oldw
+        size = short_edge_length * 1.0
+        scale = size / min(h, w)
+        if h < w:
+            newh, neww = size, scale * w
+        else:
+            newh, neww = scale * h, size
+        if max(newh, neww) > max_size:
+            scale = max_size * 1.0 / max(newh, neww)
+            newh = newh * scale
+            neww = neww * scale
+        return int(newh + 0.5), int(neww + 0.5)
+
+    def get_transform(self, h: int, w: int, size: int) -> NoOpTransform:
+        if size == 0:
+            return NoOpTransform()
+        newh, neww = self.get_output_shape(h, w, size, self.max_size)
+        return ResizeTransform(h, w, newh, neww)
+
+
+class RandomFlip:
+    def __init__(self, prob: float = 0.5, *, horizontal: bool = True, vertical: bool = False):
+        if horizontal and vertical:
+            raise ValueError("Cannot do both horiz and vert. Please use two Flip instead.")
+        if not horizontal and not vertical:
+            raise ValueError("At least one of horiz or vert has to be True!")
+        self.prob, self.horizontal, self.vertical = float(prob), bool(horizontal), bool(vertical)
+
+    def draw(self, rng: random.Random) -> bool:
+        return rng.random() < self.prob
+
+    def get_transform(self, h: int, w: int, do: bool) -> NoOpTransform:
+        if not do:
+            return NoOpTransform()
+        return HFlipTransform(w) if self.horizontal else VFlipTransform(h)
+
+
+def _refuse_unbuilt(cfg) -> None:
+    inp = cfg.INPUT
+    crop = getattr(inp, "CROP", None)
+    if crop is not None and getattr(crop, "ENABLED", False):
+        raise NotImplementedError("INPUT.CROP.ENABLED: RandomCrop is not built (locov_amd.data)")
+    for key, off in (("COLOR_JITTER", 0.0), ("RANDOM_GRAY_SCALE", False), ("GAUSSIAN_BLUR", False), ("RANDOM_ERASE", False)):
+        v = getattr(inp, key, off)
+        if (v > 0) if key == "COLOR_JITTER" else bool(v):
+            raise NotImplementedError(f"INPUT.{key}: the strong augmentations are not built (locov_amd.data)")
+
+
+def build_augmentation(cfg, is_train: bool) -> list:
+    """[ResizeShortestEdge] plus, in training and unless INPUT.RANDOM_FLIP is "none", [RandomFlip]."""
+    _refuse_unbuilt(cfg)
+    if is_train:
+        min_size, max_size, sample_style = cfg.INPUT.MIN_SIZE_TRAIN, cfg.INPUT.MAX_SIZE_TRAIN, cfg.INPUT.MIN_SIZE_TRAIN_SAMPLING
+    else:
+        min_size, max_size, sample_style = cfg.INPUT.MIN_SIZE_TEST, cfg.INPUT.MAX_SIZE_TEST, "choice"
+    if isinstance(min_size, (list, tuple)):
+        min_size = tuple(min_size)
+    augmentation = [ResizeShortestEdge(min_size, max_size, sample_style)]
+    if is_train and cfg.INPUT.RANDOM_FLIP != "none":
+        augmentation.append(RandomFlip(horizontal=cfg.INPUT.RANDOM_FLIP == "horizontal", vertical=cfg.INPUT.RANDOM_FLIP == "vertical"))
+    return augmentation
+
+
+# ---- the box side --------------------------------------------------------------------------------------------------------------
+
+def convert_to_xyxy(box, from_mode: int) -> list:
+    """BoxMode.convert(box, from_mode, XYXY_ABS) of one box given as a list.  Upstream forms torch.tensor(box) -- fp32 for Python
+    floats, int64 for ints -- adds x + w, y + h in that type and returns a list of Python numbers; so does this."""
+    if int(from_mode) == XYXY_ABS:
+        return list(box)
+    if int(from_mode) != XYWH_ABS:
+        raise NotImplementedError(f"bbox_mode {from_mode}: only XYXY_ABS (0) and XYWH_ABS (1) are built")
+    assert len(box) == 4, "BoxMode.convert takes either a k-tuple/list or an Nxk array/tensor, where k == 4 or 5"
+    arr = torch.tensor(list(box))[None, :]
+    arr[:, 2] += arr[:, 0]
+    arr[:, 3] += arr[:, 1]
+    return arr.flatten().tolist()
+
+
+def transform_instance_annotations(annotation: dict, transforms: TransformList, image_size: Tuple[int, int]) -> dict:
+    """The box part: XYXY, the corners through the transforms, clipped at 0 and at the image, in float64."""
+    bbox = convert_to_xyxy(annotation["bbox"], annotation["bbox_mode"])
+    bbox = transforms.apply_box(np.array([bbox]))[0].clip(min=0)
+    annotation["bbox"] = np.minimum(bbox, list(image_size + image_size)[::-1])
+    annotation["bbox_mode"] = XYXY_ABS
+    return annotation
+
+
+def annotations_to_instances(annos: List[dict], image_size: Tuple[int, int]) -> Instances:
+    """ovr/data/detection_utils.py:272-352 without masks and keypoints: gt_boxes (fp32), gt_classes (int64) and, as there, every
+    other annotation field whose values are ints or arrays."""
+    boxes = [convert_to_xyxy(obj["bbox"], obj["bbox_mode"]) for obj in annos]
+    target = Instances(tuple(image_size))
+    target.gt_boxes = Boxes(torch.as_tensor(np.asarray(boxes, dtype=np.float64).reshape(-1, 4), dtype=torch.float32))
+    target.gt_classes = torch.tensor([int(obj["category_id"]) for obj in annos], dtype=torch.int64)
+    if len(annos):
+        for name in set(annos[0].keys()).difference({"iscrowd", "bbox", "category_id", "area", "bbox_mode"}):
+            v = [ann[name] for ann in annos]
+            if isinstance(v[0], int):
+                v = torch.tensor(v, dtype=torch.int64)
+            elif isinstance(v[0], np.ndarray):
+                v = torch.stack([torch.from_numpy(np.ascontiguousarray(x)) for x in v])
+            if torch.is_tensor(v):
+                target.set(name, v)
+    return target
+
+
+def filter_empty_instances(instances: Instances, box_threshold: float = 1e-5) -> Instances:
+    return instances[instances.gt_boxes.nonempty(threshold=box_threshold)]
+
+
+def check_image_size(dataset_dict: dict, image_hw: Tuple[int, int]) -> None:
+    """ovr/data/detection_utils.py:21-58: a transposed size in the dict is swapped, any other mismatch is overwritten with the
+    image's size (with a message), and a missing entry is filled in."""
+    h, w = int(image_hw[0]), int(image_hw[1])
+    if "width" in dataset_dict or "height" in dataset_dict:
+        image_wh, expected_wh = (w, h), (dataset_dict["width"], dataset_dict["height"])
+        if image_wh != expected_wh:
+            if image_wh == (expected_wh[1], expected_wh[0]):
+                dataset_dict["width"], dataset_dict["height"] = expected_wh[1], expected_wh[0]
+            else:
+                print("Mismatched image shape{}, got {}, expect {}.".format(
+                    " for image " + dataset_dict["file_name"] if "file_name" in dataset_dict else "", image_wh, expected_wh)
+                    + " Please check the width/height in your annotation.")
+                dataset_dict["width"], dataset_dict["height"] = w, h
+    dataset_dict.setdefault("width", w)
+    dataset_dict.setdefault("height", h)
+
+
+# ---- the mapper ----------------------------------------------------------------------------------------------------------------
+
+def _fused_enabled() -> bool:
+    return os.environ.get("LOCOV_FUSED_RESIZE", "1") != "0"
+
+
+def _read_file(path: str, fmt: str) -> np.ndarray:
+    """[D2-upstream] detection_utils.read_image for the formats "RGB", "BGR" and "L" (EXIF orientation is not applied)."""
+    from PIL import Image
+    with open(path, "rb") as f:
+        image = Image.open(f)
+        image = np.asarray(image.convert("L" if fmt == "L" else "RGB"))
+    if fmt == "L":
+        return image[:, :, None]
+    return np.ascontiguousarray(image[:, :, ::-1]) if fmt == "BGR" else image
+
+
+class DatasetMapper:
+    """The reference's BasicTextImageDatasetMapper for the shipped configs.  __call__(dataset_dict) maps one image, map_batch a
+    list; both return the dicts the models take: "image" uint8 [C, new_h, new_w], "height" / "width" of the original
+    (check_image_size's rules), "instances" (when the dict has "annotations"), "caption" (one string when the dict has a list).
+
+    The raw image is dataset_dict["image_raw"], HWC uint8 (numpy or tensor) already in INPUT.FORMAT order; without it "file_name"
+    is read with Pillow, and when that fails the reference's fallback applies: a black image and the caption "A black image.".
+
+    device: where "image" is produced.  A cuda device resizes, flips and transposes the whole batch in one launch
+    (ops.resize_flip_images); "cpu" -- and LOCOV_FUSED_RESIZE=0, and any image outside ops.resize_supported -- takes the numpy
+    definition (and is then moved to `device`).  None: cfg.MODEL.DEVICE when a GPU is present, else the CPU.
+
+    Every random draw comes from draw_sample(dataset_dicts) (the edge length, the flip and the caption index per image, from
+    self.rng); map_batch(dataset_dicts, sample=...) replays one."""
+
+    def __init__(self, cfg, is_train: bool = True, device=None, seed: Optional[int] = None):
+        self.is_train = bool(is_train)
+        self.augmentations = build_augmentation(cfg, is_train)
+        if getattr(cfg.MODEL, "MASK_ON", False) or getattr(cfg.MODEL, "KEYPOINT_ON", False) or getattr(cfg.MODEL, "LOAD_OBJ_PROPOSALS", False):
+            raise NotImplementedError("MODEL.MASK_ON / KEYPOINT_ON / LOAD_OBJ_PROPOSALS: only the box side of the mapper is built")
+        self.image_format = cfg.INPUT.FORMAT
+        if device is None:
+            device = cfg.MODEL.DEVICE if torch.cuda.is_available() else "cpu"
+        self.device = torch.device(device)
+        self.rng = random.Random(seed)
+
+    # -- the draws
+    def draw_sample(self, dataset_dicts: Sequence[dict]) -> Dict[str, list]:
+        resize = self.augmentations[0]
+        flip = self.augmentations[1] if len(self.augmentations) > 1 else None
+        sample = {"short_edge": [], "flip": [], "caption": []}
+        for d in dataset_dicts:
+            sample["short_edge"].append(int(resize.draw(self.rng)))
+            sample["flip"].append(bool(flip.draw(self.rng)) if flip is not None else False)
+            cap = d.get("caption")
+            sample["caption"].append(self.rng.randrange(len(cap)) if self.is_train and isinstance(cap, list) and len(cap) else 0)
+        return sample
+
+    # -- one image's host-side part: the raw image, the transforms, the boxes, the caption
+    def _raw(self, d: dict):
+        raw = d.pop("image_raw", None)
+        if raw is not None:
+            if not isinstance(raw, torch.Tensor):
+                raw = np.asarray(raw)
+            if raw.dtype not in (np.uint8, torch.uint8) or raw.ndim != 3:
+                raise TypeError(f"image_raw must be uint8 [H, W, C], got {raw.dtype} {tuple(raw.shape)}")
+            return raw, True
+        try:
+            return _read_file(d["file_name"], self.image_format), True
+        except Exception:
+            print("Image not loaded {}, replaced by black image".format(d.get("file_name")))
+            return np.zeros((d["height"], d["width"], 3), dtype=np.uint8), False
+
+    def _prepare(self, dataset_dict: dict, i: int, sample: Dict[str, list]):
+        d = copy.copy(dataset_dict)                                # (the raw image is not copied; the annotations are, below)
+        raw, loaded = self._raw(d)
+        h, w = int(raw.shape[0]), int(raw.shape[1])
+        check_image_size(d, (h, w))
+        tfms = [self.augmentations[0].get_transform(h, w, int(sample["short_edge"][i]))]
+        nh, nw = tfms[0].output_shape(h, w)
+        if len(self.augmentations) > 1:
+            tfms.append(self.augmentations[1].get_transform(nh, nw, bool(sample["flip"][i])))
+        transforms = TransformList(tfms)
+        if "annotations" in d:
+            annos = [transform_instance_annotations(copy.deepcopy(obj), transforms, (nh, nw))
+                     for obj in d.pop("annotations") if obj.get("iscrowd", 0) == 0]
+            for obj in annos:
+                obj.pop("segmentation", None)
+                obj.pop("keypoints", None)
+            d["instances"] = filter_empty_instances(annotations_to_instances(annos, (nh, nw)))
+        if isinstance(d.get("caption"), list):
+            d["caption"] = d["caption"][int(sample["caption"][i])] if self.is_train else d["caption"][0]
+            if not loaded:
+                d["caption"] = "A black image."
+        return d, raw, transforms, (nh, nw)
+
+    def _host_image(self, raw, transforms: TransformList) -> torch.Tensor:
+        img = raw.cpu().numpy() if isinstance(raw, torch.Tensor) else raw
+        img = transforms.apply_image(img)
+        return torch.as_tensor(np.ascontiguousarray(img.transpose(2, 0, 1))).to(self.device)
+
+    def map_batch(self, dataset_dicts: Sequence[dict], sample: Optional[Dict[str, list]] = None) -> List[dict]:
+        dataset_dicts = list(dataset_dicts)
+        sample = self.draw_sample(dataset_dicts) if sample is None else sample
+        prepared = [self._prepare(d, i, sample) for i, d in enumerate(dataset_dicts)]
+        on_device = self.device.type == "cuda" and _fused_enabled()
+        fused: Dict[int, List[int]] = {}                           # channel count -> the images the kernel takes
+        images: List[Optional[torch.Tensor]] = [None] * len(prepared)
+        if on_device:
+            from . import ops
+            for i, (_, raw, _, size) in enumerate(prepared):
+                C = int(raw.shape[2])
+                if 1 <= C <= ops.IMAGE_BATCH_MAX_CHANNELS and ops.resize_supported(raw.shape[:2], size, C):
+                    fused.setdefault(C, []).append(i)
+            for idx in fused.values():
+                for lo in range(0, len(idx), ops.IMAGE_BATCH_MAX_IMAGES):
+                    part = idx[lo:lo + ops.IMAGE_BATCH_MAX_IMAGES]
+                    raws = [torch.as_tensor(prepared[i][1]).to(self.device, non_blocking=True) for i in part]
+                    flips = [max((t.flip for t in prepared[i][2].transforms), default=FLIP_NONE) for i in part]
+                    for i, image in zip(part, ops.resize_flip_images(raws, [prepared[i][3] for i in part], flips)):
+                        images[i] = image
+        for image, (d, raw, transforms, _) in zip(images, prepared):
+            d["image"] = image if image is not None else self._host_image(raw, transforms)
+        return [p[0] for p in prepared]
+
+    def __call__(self, dataset_dict: dict, sample: Optional[Dict[str, list]] = None) -> dict:
+        return self.map_batch([dataset_dict], sample)[0]
+
+
+def iterate_batches(dataset_dicts: Iterable[dict], mapper: DatasetMapper, batch_size: int) -> Iterator[List[dict]]:
+    """The mapped batches of a dataset, in order: inference_on_dataset(model, iterate_batches(dicts, mapper, n), evaluator) runs from
+    raw images."""
+    batch: List[dict] = []
+    for d in dataset_dicts:
+        batch.append(d)
+        if len(batch) == int(batch_size):
+            yield mapper.map_batch(batch)
+            batch = []
+    if batch:
+        yield mapper.map_batch(batch)

@@ -11,7 +11,7 @@ import ctypes
 import itertools
 import math
 import threading
-from typing import NamedTuple, Optional, Sequence, Tuple
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 from torch.autograd.function import once_differentiable
@@ -2732,6 +2732,58 @@ def detector_rescale(boxes: torch.Tensor, sizes: Sequence[int], image_sizes, out
         check(_lib.load().locov_detector_rescale(_ptr(boxes), roff, sx, sy, oh, ow, n, _ptr(out), _ptr(src), _ptr(counts), _stream(boxes)),
               "locov_detector_rescale")
     return out, src, counts.tolist()
+
+
+# --------------------------------------------------------------------------------------
+# The image side of the dataset mapper (csrc/image_resize.hip; data.py: DatasetMapper.map_batch)
+RESIZE_MAX_TAPS = _lib.RESIZE_MAX_TAPS            # LOCOV_RESIZE_MAX_TAPS
+FLIP_NONE, FLIP_HORIZONTAL, FLIP_VERTICAL = _lib.FLIP_NONE, _lib.FLIP_HORIZONTAL, _lib.FLIP_VERTICAL
+
+
+def resize_supported(in_size, out_size, channels: int = 3) -> bool:
+    """Whether locov_resize_flip_images takes an (h, w) -> (new_h, new_w) image of `channels` channels: every upscale, and a
+    downscale of at most RESIZE_MAX_TAPS taps per axis (ceil(in / out) <= 8).  No launch; the library's own rule."""
+    return bool(_lib.load().locov_resize_supported(int(in_size[0]), int(in_size[1]), int(out_size[0]), int(out_size[1]), int(channels)))
+
+
+def resize_flip_images(images: Sequence[torch.Tensor], out_sizes, flips: Optional[Sequence[int]] = None,
+                       out: Optional[Sequence[torch.Tensor]] = None) -> List[torch.Tensor]:
+    """Pillow's 8-bit bilinear resize, a flip and the HWC -> CHW transposition of N uint8 [h_i, w_i, C] device images, each to its own
+    out_sizes[i] = (new_h, new_w), in one launch (locov_resize_flip_images): the bytes of
+    np.asarray(Image.fromarray(img).resize((new_w, new_h), Image.BILINEAR)), flipped (FLIP_NONE / FLIP_HORIZONTAL / FLIP_VERTICAL
+    per image, default none), transposed.  Returns N uint8 [C, new_h, new_w] tensors; out: the caller's tensors instead of fresh ones,
+    every byte of which is written.  Sizes outside resize_supported raise: the caller takes data.resize_bilinear_host for those."""
+    images = list(images)
+    n = len(images)
+    if n == 0:
+        return []
+    ims = [_dev(t, f"images[{i}]", dtype=torch.uint8) for i, t in enumerate(images)]
+    C = ims[0].shape[2] if ims[0].dim() == 3 else -1
+    if any(t.dim() != 3 or t.shape[2] != C or t.device != ims[0].device for t in ims):
+        raise ValueError("resize_flip_images: the images must be [H, W, C] with one channel count, on one device")
+    flips = [FLIP_NONE] * n if flips is None else [int(f) for f in flips]
+    out_sizes = [(int(s[0]), int(s[1])) for s in out_sizes]
+    if len(out_sizes) != n or len(flips) != n or n > IMAGE_BATCH_MAX_IMAGES or not (1 <= C <= IMAGE_BATCH_MAX_CHANNELS):
+        raise ValueError(f"resize_flip_images: one size and one flip per image, at most {IMAGE_BATCH_MAX_IMAGES} images of "
+                         f"1..{IMAGE_BATCH_MAX_CHANNELS} channels")
+    for t, s in zip(ims, out_sizes):
+        if min(t.shape[0], t.shape[1]) < 1 or min(s) < 1 or not resize_supported(t.shape[:2], s, C):
+            raise ValueError(f"resize_flip_images: {tuple(t.shape[:2])} -> {s} is outside the kernel's limits (positive sizes, at most "
+                             f"{RESIZE_MAX_TAPS} taps per axis)")
+    if out is None:
+        outs = [torch.empty((C, s[0], s[1]), dtype=torch.uint8, device=ims[0].device) for s in out_sizes]
+    else:
+        outs = list(out)
+        if len(outs) != n or any(o.dtype != torch.uint8 or tuple(o.shape) != (C, s[0], s[1]) or o.device != ims[0].device
+                                 or not o.is_contiguous() for o, s in zip(outs, out_sizes)):
+            raise ValueError("resize_flip_images: out must hold one contiguous uint8 [C, new_h, new_w] tensor per image, on the images' device")
+    ints = lambda vals: (ctypes.c_int * n)(*vals)
+    with torch.cuda.device(ims[0].device):
+        check(_lib.load().locov_resize_flip_images(
+            (ctypes.c_void_p * n)(*[t.data_ptr() for t in ims]), ints([t.shape[0] for t in ims]), ints([t.shape[1] for t in ims]),
+            (ctypes.c_void_p * n)(*[o.data_ptr() for o in outs]), ints([s[0] for s in out_sizes]), ints([s[1] for s in out_sizes]),
+            ints(flips), n, C, _stream(ims[0])), "locov_resize_flip_images")
+    return outs
 
 
 # --------------------------------------------------------------------------------------
