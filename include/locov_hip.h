@@ -40,7 +40,7 @@ extern "C" {
  *    locov_resnet_stem_fwd, locov_resnet_stem_fwd_sel, locov_resnet_stem_wgrad (+ _workspace_bytes),
  *    locov_preprocess_images, locov_detector_rescale, locov_sgd_step (+ _workspace_bytes),
  *    locov_coco_match (+ _workspace_bytes), locov_coco_accumulate, locov_lvis_match,
- *    locov_resize_flip_images, locov_resize_supported */
+ *    locov_resize_flip_images, locov_resize_supported, locov_map_proposals */
 #define LOCOV_ABI_VERSION 8
 
 #define LOCOV_OK 0
@@ -1371,6 +1371,40 @@ int locov_resize_supported(int in_h, int in_w, int out_h, int out_w, int channel
 int locov_resize_flip_images(const void *const *images_host, const int *heights_host, const int *widths_host, void *const *outs_host,
                              const int *out_heights_host, const int *out_widths_host, const int *flips_host, int n_images, int channels,
                              locov_stream_t stream);
+
+/* ---- the proposal side of the dataset mapper in one launch for the whole batch (csrc/proposal_map.hip) ------------------------
+ * Added under ABI version 8.  What the mapper does with an image's precomputed proposals under MODEL.LOAD_OBJ_PROPOSALS
+ * (ovr/data/mappers/basic_mappers.py:130-133: [D2-upstream] transform_proposals; coco_mappers.py:82-106: change_proposals_as_gt).
+ *
+ * locov_map_proposals:
+ *   rows        : the STORE, device, [n_store_rows, 5] row-major, XYXY + objectness logit, fp32 (LOCOV_PROPOSAL_F32) or fp64
+ *                 (LOCOV_PROPOSAL_F64), aligned to its element size.  Image i of the call owns the store rows
+ *                 [row_start_host[i], row_start_host[i] + n_rows_host[i]); row_start_host (int64) may be in any order, with gaps.
+ *   fx_host, fy_host : per image, the DOUBLE factors new_w * 1.0 / w and new_h * 1.0 / h (1.0 for no resize).  The kernel rounds
+ *                 them once to the rows' dtype, as numpy does with a Python scalar beside an array.
+ *   flips_host  : per image LOCOV_FLIP_NONE, LOCOV_FLIP_HORIZONTAL or LOCOV_FLIP_VERTICAL.
+ *   new_h_host, new_w_host : per image, the size the boxes are flipped in and clipped to.
+ *   Per row and axis, in the rows' dtype with every operation rounded on its own: both ends times the factor, their min / max
+ *   (a NaN end makes both NaN, as ndarray.min does); on the flipped axis size - lo and size - hi and their min / max again; then
+ *   ONE rounding to fp32, clamped to [0, size] as torch.clamp does (NaN stays NaN).  A row is kept iff (x2 - x1 > 0) & (y2 - y1 > 0)
+ *   in fp32.  The proposal list of an image is its first `topk` kept rows in their original order; its pseudo-GT list is the subset
+ *   of THAT list with (float)logit > thr.
+ *   Outputs over T = sum of n_rows_host, image i's segment starting at the sum of the counts before it:
+ *     prop_boxes fp32 [T, 4], prop_logits fp32 [T], prop_src int64 [T]; gt_boxes fp32 [T, 4], gt_logits fp32 [T], gt_classes
+ *     int64 [T] (ones), gt_src int64 [T]; counts int32 [n_images, 2], device: (proposals, pseudo-GT) per image, the caller's one
+ *     host read.  The lists stand at the front of the segment; behind the count the segment holds zeros, src is -1 and gt_classes
+ *     is 0.  src is the row WITHIN the image.  EVERY output element is written.
+ *   One launch, one workgroup per image, any number of rows per image; no atomics, vector stores only.  Two calls give the same bits.
+ *   n_images == 0: LOCOV_OK, nothing is touched.  More than LOCOV_LABEL_MAX_IMAGES images, a null pointer, a negative count, size
+ *   or topk, an unknown dtype or flip, rows outside the store, misaligned pointers (boxes 16 bytes, int64 outputs 8, the rest their
+ *   element size), T above 2^31 - 1: LOCOV_ERR_INVALID_ARG before any HIP call.  (With T == 0 only `counts` is touched.) */
+#define LOCOV_PROPOSAL_F32 0
+#define LOCOV_PROPOSAL_F64 1
+int locov_map_proposals(const void *rows, int64_t n_store_rows, int dtype, const int64_t *row_start_host, const int *n_rows_host,
+                        const double *fx_host, const double *fy_host, const int *flips_host, const int *new_h_host,
+                        const int *new_w_host, int n_images, int topk, float thr, float *prop_boxes, float *prop_logits,
+                        int64_t *prop_src, float *gt_boxes, float *gt_logits, int64_t *gt_classes, int64_t *gt_src, int *counts,
+                        locov_stream_t stream);
 
 /* ---- the caption path of the LSM step in one launch (csrc/caption.hip): BertEmbedding after the tokenizer --------------------
  * (ovr/modeling/language/transf_models.py:105-154).  Added under ABI version 8.

@@ -47,6 +47,7 @@ COCO_MAX_AREAS, COCO_MAX_THRESHOLDS, COCO_MAX_CAPS, COCO_MAX_RECALL_THRESHOLDS =
 COCO_MAX_DET, COCO_MAX_BLOCKS = 4096, 8388608
 LVIS_CELL_NEG, LVIS_CELL_NOT_EXHAUSTIVE = 1, 2
 RESIZE_MAX_TAPS, FLIP_NONE, FLIP_HORIZONTAL, FLIP_VERTICAL = 17, 0, 1, 2
+PROPOSAL_F32, PROPOSAL_F64 = 0, 1
 
 _p = c_void_p  # device pointer
 
@@ -248,6 +249,9 @@ SIGNATURES = {
     "locov_resize_supported": (c_int, [c_int, c_int, c_int, c_int, c_int]),
     "locov_resize_flip_images": (c_int, [POINTER(c_void_p), POINTER(c_int), POINTER(c_int), POINTER(c_void_p), POINTER(c_int),
                                          POINTER(c_int), POINTER(c_int), c_int, c_int, _p]),
+    "locov_map_proposals": (c_int, [_p, c_int64, c_int, POINTER(c_int64), POINTER(c_int), POINTER(c_double), POINTER(c_double),
+                                    POINTER(c_int), POINTER(c_int), POINTER(c_int), c_int, c_int, c_float, _p, _p, _p, _p, _p, _p, _p,
+                                    _p, _p]),
 }
 
 _lib = None

@@ -81,6 +81,7 @@ def get_cfg() -> CfgNode:
             "MASK_ON": False,
             "KEYPOINT_ON": False,
             "LOAD_EMB_PRED_FROM_MMSS_HEAD": False,                # config.py:13
+            "LOAD_OBJ_PROPOSALS": False,                          # config.py:14; coco_lsm.yaml -> True (data.py: the OLN pseudo-GT)
             # NAME, FREEZE_AT: [D2-upstream]; coco_lsm.yaml -> FREEZE_AT 0.  TRAIN_ON_DEVICE (this port): a backbone with trainable
             # weights runs forward AND backward on the gfx950 kernels instead of the torch path (backbone.py; opt-in)
             "BACKBONE": {"NAME": "build_resnet_backbone", "FREEZE_AT": 2, "TRAIN_ON_DEVICE": False},
@@ -214,7 +215,8 @@ def get_cfg() -> CfgNode:
         },
         "VIS_PERIOD": 0,                                           # [D2-upstream]; > 0 is refused (meta_arch.py)
         "TEST": {"DETECTIONS_PER_IMAGE": 100},                     # [D2-upstream]
-        "DATASETS": {"TRAIN": ()},                                 # [D2-upstream] (USE_FED_LOSS: whose class_image_count to read)
+        # [D2-upstream] (TRAIN: USE_FED_LOSS reads its class_image_count; ..._TOPK_*: the mapper's cut under MODEL.LOAD_OBJ_PROPOSALS)
+        "DATASETS": {"TRAIN": (), "PRECOMPUTED_PROPOSAL_TOPK_TRAIN": 2000, "PRECOMPUTED_PROPOSAL_TOPK_TEST": 1000},
         "SOLVER": {                                                # [D2-upstream] (solver.py); the yaml files set BASE_LR, STEPS, MAX_ITER, ...
             "BASE_LR": 0.001, "MOMENTUM": 0.9, "NESTEROV": False,
             "WEIGHT_DECAY": 0.0001, "WEIGHT_DECAY_NORM": 0.0, "BIAS_LR_FACTOR": 1.0, "WEIGHT_DECAY_BIAS": 0.0001,

@@ -3,7 +3,7 @@
 //   locov_detector_rescale  : detector_postprocess' box part -- scale, clip, drop the empty boxes, kept rows compacted in order
 // Compiled with -ffp-contract=off: the subtraction, the division and the products round one by one, as the torch ops they stand for.
 // The per-image tables travel in a by-value argument struct (the idiom of detect_common.h's DetGeom): no H2D copy, no workspace.
-#include "common.h"
+#include "box_clip_common.h"
 
 namespace locov {
 namespace {
@@ -106,11 +106,6 @@ struct RescaleArgs {
     float sx[LOCOV_LABEL_MAX_IMAGES], sy[LOCOV_LABEL_MAX_IMAGES];
     float w[LOCOV_LABEL_MAX_IMAGES], h[LOCOV_LABEL_MAX_IMAGES];   // the output sizes, as the fp32 limits torch's clamp compares with
 };
-
-__device__ __forceinline__ float clamp_like_torch(float v, float hi)      // clamp(min=0, max=hi): NaN stays NaN
-{
-    return v != v ? v : fminf(fmaxf(v, 0.f), hi);
-}
 
 // One workgroup per image: 256 rows at a time, a ballot per wave and the four wave counts through LDS give each kept row its place.
 __global__ __launch_bounds__(256) void detector_rescale_kernel(const float4 *__restrict__ boxes, RescaleArgs a, float4 *__restrict__ out_boxes,

@@ -17,14 +17,25 @@ As in evaluation.py the numpy path of this module is the DEFINITION:
   * the device path (ops.resize_flip_images: csrc/image_resize.hip) does resize, flip and the HWC -> CHW transposition of a whole
     batch in one launch and gives the same bytes.  The host path serves CPU tensors, LOCOV_FUSED_RESIZE=0 and the sizes outside
     ops.resize_supported.
+  * transform_proposals and change_proposals_as_gt are the definition of the proposal side (MODEL.LOAD_OBJ_PROPOSALS, as in
+    coco_lsm.yaml: CocoImageDatasetMapper turns the image's precomputed OLN proposals with objectness > 0.7 into its "instances",
+    gt_classes 1, and moves the annotated boxes to "gt_obj").  The boxes go through apply_box in the ARRAY'S dtype -- numpy rounds
+    the Python factor new_w * 1.0 / w (formed in double) and the Python size to it, so fp32 rows are multiplied and mirrored in
+    fp32 --, are rounded once to fp32, clipped, the empty ones dropped, the first topk kept; the threshold is compared in fp32.
+    The device path (ops.map_proposals: csrc/proposal_map.hip) does both steps for a whole batch in one launch, on rows that
+    ProposalStore put on the device once, and gives the same values.  The host path serves CPU tensors, LOCOV_FUSED_PROPOSALS=0
+    and row dtypes outside ops.PROPOSAL_DTYPES.
 
 [D2-upstream] (restated from Detectron2's public sources, unverified here: Detectron2 is not installed): ResizeShortestEdge,
 RandomFlip, build_augmentation, the transforms' apply_coords / apply_box, BoxMode.convert, transform_instance_annotations,
-filter_empty_instances.  annotations_to_instances and check_image_size are the reference's own (ovr/data/detection_utils.py:21-58,
-272-352).  The box side stays on the host, in float64 numpy as upstream: a handful of boxes per image.
+filter_empty_instances, transform_proposals.  annotations_to_instances and check_image_size are the reference's own
+(ovr/data/detection_utils.py:21-58, 272-352), as are CocoImageDatasetMapper, change_proposals_as_gt and get_mapper
+(ovr/data/mappers/coco_mappers.py:24-106, __init__.py:11-35).  The annotated boxes stay on the host, in float64 numpy as upstream: a
+handful of boxes per image.
 
 Not built: INPUT.CROP, the strong augmentations (COLOR_JITTER, RANDOM_GRAY_SCALE, GAUSSIAN_BLUR, RANDOM_ERASE), masks, keypoints,
-precomputed proposals, the NOISE_* options -- the first two groups are refused with an error, never ignored.
+VawImageDatasetMapper, TextImageDatasetMapperNoise and its NOISE_* options, dataset registration and reading the proposal file --
+the first two groups and the two mappers are refused with an error, never ignored.
 """
 from __future__ import annotations
 
@@ -330,10 +341,101 @@ def check_image_size(dataset_dict: dict, image_hw: Tuple[int, int]) -> None:
     dataset_dict.setdefault("height", h)
 
 
+# ---- precomputed proposals and the pseudo ground truth ---------------------------------------------------------------------------
+
+OBJECTNESS_THR = 0.7                     # change_proposals_as_gt's default (ovr/data/mappers/coco_mappers.py:88)
+
+
+def transform_proposals(dataset_dict: dict, image_shape: Tuple[int, int], transforms: TransformList, proposal_topk: int,
+                        min_box_size: float = 0) -> None:
+    """[D2-upstream] detection_utils.transform_proposals, in place: a dict with "proposal_boxes" ([n, 4] array), "proposal_bbox_mode"
+    and "proposal_objectness_logits" loses the three and gains "proposals" = Instances(image_shape, proposal_boxes,
+    objectness_logits).  The boxes go through transforms.apply_box in the ARRAY'S OWN dtype (numpy rounds the Python factor and
+    the Python size to it), are rounded once to fp32 (Boxes), clipped, the empty ones dropped, the first proposal_topk kept."""
+    if "proposal_boxes" not in dataset_dict:
+        return
+    mode = dataset_dict.pop("proposal_bbox_mode")
+    if int(mode) != XYXY_ABS:
+        raise NotImplementedError(f"proposal_bbox_mode {mode}: only XYXY_ABS (0) is built")
+    boxes = Boxes(torch.as_tensor(transforms.apply_box(np.asarray(dataset_dict.pop("proposal_boxes"))).astype("float32")))
+    logits = torch.as_tensor(np.asarray(dataset_dict.pop("proposal_objectness_logits")).astype("float32"))
+    boxes.clip(image_shape)
+    keep = boxes.nonempty(threshold=min_box_size)
+    dataset_dict["proposals"] = Instances(tuple(image_shape), proposal_boxes=boxes[keep][:proposal_topk],
+                                          objectness_logits=logits[keep][:proposal_topk])
+
+
+def change_proposals_as_gt(dataset_dict: dict, objectness_thr: float = OBJECTNESS_THR) -> dict:
+    """ovr/data/mappers/coco_mappers.py:88-106: a new dict whose "instances" are the proposals with objectness_logits >
+    objectness_thr (compared in the logits' fp32, as torch compares a tensor with a Python number) under the fields
+    objectness_logits, gt_classes (ones: "an object") and gt_boxes; the former "instances" are "gt_obj"; "proposals" is gone.
+    Without "proposals" or "instances": KeyError, as there."""
+    out = dict(dataset_dict)
+    proposals, annotated = out.pop("proposals"), out.pop("instances")
+    picked = proposals[proposals.objectness_logits > objectness_thr]
+    out["gt_obj"] = annotated
+    out["instances"] = Instances(picked.image_size, objectness_logits=picked.objectness_logits,
+                                 gt_classes=torch.ones(len(picked), dtype=torch.int64, device=picked.objectness_logits.device),
+                                 gt_boxes=picked.proposal_boxes)
+    return out
+
+
+class ProposalStore:
+    """The precomputed proposals of a dataset, packed ONCE: proposals_by_image_id is the reference's metadata entry
+    "object_proposals", {image_id: array [n, >= 5] or a list whose element 0 is that array}, rows of XYXY + objectness logit; only
+    the first five columns are used.
+
+    All arrays of one dtype keep it.  MIXED dtypes across images are promoted to float64 -- on every device, so that an image's
+    boxes do not depend on where the store lives; the transform then runs in float64 for all of them.
+    On a cuda device the rows of all images stand in one [R, 5] tensor (`rows`) and `table` maps image_id -> (first row, n): a
+    step then uploads a descriptor, not rows.  `rows` is None on the CPU, and for a dtype outside ops.PROPOSAL_DTYPES, where the
+    store is a thin view over the arrays (store[image_id] -> [n, >= 5] array, KeyError for an unknown id) and the host
+    definition does the work."""
+
+    def __init__(self, proposals_by_image_id: dict, device="cpu"):
+        self.device = torch.device(device)
+        arrays = {}
+        for image_id, rows in proposals_by_image_id.items():
+            rows = np.asarray(rows[0] if isinstance(rows, list) else rows)
+            if rows.ndim != 2 or rows.shape[1] < 5:
+                raise ValueError(f"ProposalStore: image {image_id!r}: rows must be [n, >= 5] (XYXY + logit), got {rows.shape}")
+            arrays[image_id] = rows
+        dtypes = {a.dtype for a in arrays.values()}
+        self.dtype = next(iter(dtypes)) if len(dtypes) == 1 else np.dtype(np.float64)
+        if len(dtypes) > 1:                                        # (mixed: one dtype for the whole dataset)
+            arrays = {k: a.astype(np.float64) for k, a in arrays.items()}
+        self.arrays = arrays
+        self.table: Dict[object, Tuple[int, int]] = {}
+        self.rows: Optional[torch.Tensor] = None
+        if self.device.type == "cuda" and self.dtype in (np.float32, np.float64):
+            start = 0
+            for image_id, a in arrays.items():
+                self.table[image_id] = (start, a.shape[0])
+                start += a.shape[0]
+            packed = np.empty((start, 5), dtype=self.dtype)
+            for image_id, a in arrays.items():
+                s, n = self.table[image_id]
+                packed[s:s + n] = a[:, :5]
+            self.rows = torch.from_numpy(packed).to(self.device)
+
+    def __contains__(self, image_id) -> bool:
+        return image_id in self.arrays
+
+    def __len__(self) -> int:
+        return len(self.arrays)
+
+    def __getitem__(self, image_id) -> np.ndarray:
+        return self.arrays[image_id]
+
+
 # ---- the mapper ----------------------------------------------------------------------------------------------------------------
 
 def _fused_enabled() -> bool:
     return os.environ.get("LOCOV_FUSED_RESIZE", "1") != "0"
+
+
+def _fused_proposals_enabled() -> bool:
+    return os.environ.get("LOCOV_FUSED_PROPOSALS", "1") != "0"
 
 
 def _read_file(path: str, fmt: str) -> np.ndarray:
@@ -359,14 +461,22 @@ class DatasetMapper:
     (ops.resize_flip_images); "cpu" -- and LOCOV_FUSED_RESIZE=0, and any image outside ops.resize_supported -- takes the numpy
     definition (and is then moved to `device`).  None: cfg.MODEL.DEVICE when a GPU is present, else the CPU.
 
+    MODEL.LOAD_OBJ_PROPOSALS: a dict carrying "proposal_boxes" ([n, 4] array, XYXY_ABS), "proposal_bbox_mode" and
+    "proposal_objectness_logits" gets "proposals" (transform_proposals, cut at DATASETS.PRECOMPUTED_PROPOSAL_TOPK_TRAIN / _TEST), on
+    `device`.  On a cuda device the batch's rows are packed into one pinned buffer, uploaded once and mapped in one launch
+    (ops.map_proposals); LOCOV_FUSED_PROPOSALS=0, a CPU device and rows that are not fp32 / fp64 take the host definition.
+
     Every random draw comes from draw_sample(dataset_dicts) (the edge length, the flip and the caption index per image, from
     self.rng); map_batch(dataset_dicts, sample=...) replays one."""
 
     def __init__(self, cfg, is_train: bool = True, device=None, seed: Optional[int] = None):
         self.is_train = bool(is_train)
         self.augmentations = build_augmentation(cfg, is_train)
-        if getattr(cfg.MODEL, "MASK_ON", False) or getattr(cfg.MODEL, "KEYPOINT_ON", False) or getattr(cfg.MODEL, "LOAD_OBJ_PROPOSALS", False):
-            raise NotImplementedError("MODEL.MASK_ON / KEYPOINT_ON / LOAD_OBJ_PROPOSALS: only the box side of the mapper is built")
+        if getattr(cfg.MODEL, "MASK_ON", False) or getattr(cfg.MODEL, "KEYPOINT_ON", False):
+            raise NotImplementedError("MODEL.MASK_ON / KEYPOINT_ON: only the box side of the mapper is built")
+        self.proposal_topk: Optional[int] = None                   # (basic_mappers.py:82-87)
+        if getattr(cfg.MODEL, "LOAD_OBJ_PROPOSALS", False):
+            self.proposal_topk = int(cfg.DATASETS.PRECOMPUTED_PROPOSAL_TOPK_TRAIN if is_train else cfg.DATASETS.PRECOMPUTED_PROPOSAL_TOPK_TEST)
         self.image_format = cfg.INPUT.FORMAT
         if device is None:
             device = cfg.MODEL.DEVICE if torch.cuda.is_available() else "cpu"
@@ -374,6 +484,9 @@ class DatasetMapper:
         self.rng = random.Random(seed)
 
     # -- the draws
+    def _caption_choices(self, d: dict):
+        return d.get("caption")
+
     def draw_sample(self, dataset_dicts: Sequence[dict]) -> Dict[str, list]:
         resize = self.augmentations[0]
         flip = self.augmentations[1] if len(self.augmentations) > 1 else None
@@ -381,7 +494,7 @@ class DatasetMapper:
         for d in dataset_dicts:
             sample["short_edge"].append(int(resize.draw(self.rng)))
             sample["flip"].append(bool(flip.draw(self.rng)) if flip is not None else False)
-            cap = d.get("caption")
+            cap = self._caption_choices(d)
             sample["caption"].append(self.rng.randrange(len(cap)) if self.is_train and isinstance(cap, list) and len(cap) else 0)
         return sample
 
@@ -450,10 +563,136 @@ class DatasetMapper:
                         images[i] = image
         for image, (d, raw, transforms, _) in zip(images, prepared):
             d["image"] = image if image is not None else self._host_image(raw, transforms)
-        return [p[0] for p in prepared]
+        return self._finish(prepared)
 
     def __call__(self, dataset_dict: dict, sample: Optional[Dict[str, list]] = None) -> dict:
         return self.map_batch([dataset_dict], sample)[0]
+
+    # -- the proposal side (MODEL.LOAD_OBJ_PROPOSALS)
+    def _finish(self, prepared) -> List[dict]:
+        if self.proposal_topk is not None:
+            self._map_proposals(prepared, as_gt=False)
+        return [p[0] for p in prepared]
+
+    def _proposal_rows(self, dicts: List[dict]):
+        """(rows [R, 5] on the device, first row per image, rows per image) for the dicts, which all carry "proposal_boxes": their
+        rows packed into ONE pinned buffer and uploaded once.  None where only the host definition applies."""
+        from . import ops
+        boxes = [np.asarray(d["proposal_boxes"]) for d in dicts]
+        logits = [np.asarray(d["proposal_objectness_logits"]) for d in dicts]
+        dtypes = {a.dtype for a in boxes + logits}
+        if (any(int(d["proposal_bbox_mode"]) != XYXY_ABS for d in dicts) or len(dtypes) != 1
+                or getattr(torch, str(next(iter(dtypes))), None) not in ops.PROPOSAL_DTYPES
+                or any(b.ndim != 2 or b.shape[1] != 4 or l.shape != b.shape[:1] for b, l in zip(boxes, logits))):
+            return None
+        counts = [b.shape[0] for b in boxes]
+        starts = [0] + list(np.cumsum(counts)[:-1])
+        pinned = torch.empty((sum(counts), 5), dtype=getattr(torch, str(boxes[0].dtype)), pin_memory=True)
+        view = pinned.numpy()
+        for s, n, b, l in zip(starts, counts, boxes, logits):
+            view[s:s + n, :4], view[s:s + n, 4] = b, l
+        return pinned.to(self.device, non_blocking=True), starts, counts
+
+    def _map_proposals(self, prepared, as_gt: bool) -> bool:
+        """transform_proposals for the dicts that carry proposals.  On a cuda device, in one launch (ops.map_proposals), which with
+        as_gt also does change_proposals_as_gt; returns whether it did.  Otherwise -- LOCOV_FUSED_PROPOSALS=0, a CPU device, a
+        dtype or box mode the kernel does not take -- the host definition, its result moved to the device."""
+        idx = [i for i, p in enumerate(prepared) if "proposal_boxes" in p[0]]
+        if not idx:
+            return False
+        dicts = [prepared[i][0] for i in idx]
+        source = self._proposal_rows(dicts) if self.device.type == "cuda" and _fused_proposals_enabled() else None
+        if source is None:
+            for i in idx:
+                d, _, transforms, size = prepared[i]
+                transform_proposals(d, size, transforms, self.proposal_topk)
+                d["proposals"] = d["proposals"].to(self.device)
+            return False
+        from . import ops
+        factors, flips = [], []
+        for i in idx:
+            resize, (nh, nw) = prepared[i][2].transforms[0], prepared[i][3]
+            factors.append((nw * 1.0 / resize.w, nh * 1.0 / resize.h) if isinstance(resize, ResizeTransform) else (1.0, 1.0))
+            flips.append(max((t.flip for t in prepared[i][2].transforms), default=FLIP_NONE))
+        sizes = [prepared[i][3] for i in idx]
+        mapped = ops.map_proposals(*source, factors, flips, sizes, self.proposal_topk, OBJECTNESS_THR)
+        for d, m, size in zip(dicts, mapped, sizes):
+            for key in ("proposal_boxes", "proposal_bbox_mode", "proposal_objectness_logits"):
+                d.pop(key)
+            if as_gt:
+                d["gt_obj"] = d.pop("instances")
+                d["instances"] = Instances(tuple(size), objectness_logits=m.gt_logits, gt_classes=m.gt_classes, gt_boxes=Boxes(m.gt_boxes))
+            else:
+                d["proposals"] = Instances(tuple(size), proposal_boxes=Boxes(m.prop_boxes), objectness_logits=m.prop_logits)
+        return as_gt
+
+
+class CocoImageDatasetMapper(DatasetMapper):
+    """The reference's CocoImageDatasetMapper (ovr/data/mappers/coco_mappers.py:24-85).  metadata: anything with .get(name) and
+    .thing_classes; no catalog is involved.
+
+      * metadata.get("captions_dict"), {image_id: [caption, ...]}: "caption" is a drawn one in training (the draw is part of
+        draw_sample, so `sample` replays it) and the first one otherwise; every annotation gains "category" =
+        thing_classes[category_id], and "nouns" / "nouns_id" list them.  An image without an entry: "" and two empty lists.
+      * metadata.get("object_proposals"), the reference's dict or a ProposalStore built from it: the image's rows become its
+        proposals (KeyError for an image without an entry, as there), transform_proposals cuts them at the config's topk and
+        change_proposals_as_gt makes the ones above OBJECTNESS_THR the "instances" (gt_classes 1), the annotated boxes "gt_obj",
+        and removes "proposals".  With the store on a cuda device both steps are ops.map_proposals' one launch on rows that never
+        leave the device; "instances" is on the device, "gt_obj" on the host."""
+
+    def __init__(self, cfg, metadata, is_train: bool = True, device=None, seed: Optional[int] = None):
+        super().__init__(cfg, is_train, device, seed)
+        self.metadata = metadata
+        store = metadata.get("object_proposals")
+        if store is not None and not isinstance(store, ProposalStore):
+            store = ProposalStore(store, self.device) if len(store) else None
+        self.store: Optional[ProposalStore] = store
+
+    def _caption_choices(self, d: dict):
+        captions = self.metadata.get("captions_dict")
+        return captions.get(d["image_id"]) if captions else d.get("caption")
+
+    def _prepare(self, dataset_dict: dict, i: int, sample: Dict[str, list]):
+        d = copy.copy(dataset_dict)
+        captions = self.metadata.get("captions_dict")
+        if captions:
+            if d["image_id"] in captions:
+                choices = captions[d["image_id"]]
+                d["caption"] = choices[int(sample["caption"][i])] if self.is_train else choices[0]
+                d["annotations"] = [dict(ann, category=self.metadata.thing_classes[ann["category_id"]]) for ann in d["annotations"]]
+                d["nouns"] = [ann["category"] for ann in d["annotations"]]
+                d["nouns_id"] = [ann["category_id"] for ann in d["annotations"]]
+            else:
+                d["caption"], d["nouns"], d["nouns_id"] = "", [], []
+        if self.store is not None and d["image_id"] in self.store:
+            rows = self.store[d["image_id"]]
+            d["proposal_boxes"], d["proposal_objectness_logits"], d["proposal_bbox_mode"] = rows[:, :4], rows[:, 4], XYXY_ABS
+        return super()._prepare(d, i, sample)
+
+    def _proposal_rows(self, dicts: List[dict]):
+        store = self.store
+        if store is None or store.rows is None or store.rows.device.type != self.device.type or any(d["image_id"] not in store.table for d in dicts):
+            return super()._proposal_rows(dicts)
+        where = [store.table[d["image_id"]] for d in dicts]
+        return store.rows, [s for s, _ in where], [n for _, n in where]
+
+    def _finish(self, prepared) -> List[dict]:
+        if self.store is None:
+            return super()._finish(prepared)
+        fused = self.proposal_topk is not None and self._map_proposals(prepared, as_gt=True)
+        return [p[0] if fused and "gt_obj" in p[0] else change_proposals_as_gt(p[0]) for p in prepared]
+
+
+def get_mapper(dataset_name: str, cfg, is_train: bool, metadata=None, device=None) -> DatasetMapper:
+    """ovr/data/mappers/__init__.py:11-35 with the metadata given by the caller: "coco" -> CocoImageDatasetMapper, "lvis" ->
+    DatasetMapper; the "vaw" mapper and the noise mapper of every other name are not built."""
+    if "coco" in dataset_name:
+        return CocoImageDatasetMapper(cfg, metadata, is_train, device=device)
+    if "vaw" in dataset_name:
+        raise NotImplementedError(f"{dataset_name}: VawImageDatasetMapper is not built (locov_amd.data)")
+    if "lvis" in dataset_name:
+        return DatasetMapper(cfg, is_train, device=device)
+    raise NotImplementedError(f"{dataset_name}: TextImageDatasetMapperNoise is not built (locov_amd.data)")
 
 
 def iterate_batches(dataset_dicts: Iterable[dict], mapper: DatasetMapper, batch_size: int) -> Iterator[List[dict]]:

@@ -2787,6 +2787,85 @@ def resize_flip_images(images: Sequence[torch.Tensor], out_sizes, flips: Optiona
 
 
 # --------------------------------------------------------------------------------------
+# The proposal side of the dataset mapper (csrc/proposal_map.hip; data.py: transform_proposals + change_proposals_as_gt)
+PROPOSAL_DTYPES = (torch.float32, torch.float64)  # the row dtypes locov_map_proposals takes; any other goes to data.py's host definition
+
+
+class ProposalBuffers(NamedTuple):
+    """locov_map_proposals' outputs over T = sum(n_rows) rows and N images; every element is written by a call."""
+    prop_boxes: torch.Tensor     # fp32 [T, 4]
+    prop_logits: torch.Tensor    # fp32 [T]
+    prop_src: torch.Tensor       # int64 [T]
+    gt_boxes: torch.Tensor       # fp32 [T, 4]
+    gt_logits: torch.Tensor      # fp32 [T]
+    gt_classes: torch.Tensor     # int64 [T]
+    gt_src: torch.Tensor         # int64 [T]
+    counts: torch.Tensor         # int32 [N, 2]
+
+
+class MappedProposals(NamedTuple):
+    """One image's lists, views of the ProposalBuffers cut at its counts."""
+    prop_boxes: torch.Tensor
+    prop_logits: torch.Tensor
+    prop_src: torch.Tensor
+    gt_boxes: torch.Tensor
+    gt_logits: torch.Tensor
+    gt_classes: torch.Tensor
+    gt_src: torch.Tensor
+
+
+def proposal_buffers(total_rows: int, n_images: int, device) -> ProposalBuffers:
+    f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=device)
+    i = lambda *shape: torch.empty(shape, dtype=torch.int64, device=device)
+    T = int(total_rows)
+    return ProposalBuffers(f(T, 4), f(T), i(T), f(T, 4), f(T), i(T), i(T), torch.empty((int(n_images), 2), dtype=torch.int32, device=device))
+
+
+def map_proposals(store_rows: torch.Tensor, row_start: Sequence[int], n_rows: Sequence[int], factors, flips: Sequence[int], sizes,
+                  topk: int, thr: float, out: Optional[ProposalBuffers] = None) -> List[MappedProposals]:
+    """transform_proposals and change_proposals_as_gt of a batch (locov_map_proposals: one launch per 64 images) and ONE host read,
+    of the counts.  store_rows [R, 5] fp32 or fp64 on the device, XYXY + logit; image i owns rows [row_start[i], row_start[i] +
+    n_rows[i]), is resized by factors[i] = (fx, fy) -- Python floats, rounded to the rows' dtype in the kernel --, flipped by
+    flips[i] in sizes[i] = (new_h, new_w) and clipped to it.  Per image: the first topk non-empty boxes in their order with their
+    fp32 logits and source rows, and of those the ones with logit > fp32(thr) with gt_classes 1.  out: the caller's
+    ProposalBuffers instead of fresh ones."""
+    store_rows = _dev(store_rows, "store_rows", dtype=None)
+    if store_rows.dtype not in PROPOSAL_DTYPES or store_rows.dim() != 2 or store_rows.shape[1] != 5:
+        raise TypeError(f"map_proposals: store_rows must be fp32 or fp64 [R, 5], got {store_rows.dtype} {tuple(store_rows.shape)}")
+    starts, counts, flips = [int(s) for s in row_start], [int(c) for c in n_rows], [int(f) for f in flips]
+    n = len(counts)
+    if not (len(starts) == len(factors) == len(flips) == len(sizes) == n):
+        raise ValueError("map_proposals: one row_start, n_rows, factor pair, flip and size per image")
+    R = int(store_rows.shape[0])
+    if int(topk) < 0 or any(c < 0 or s < 0 or s + c > R for s, c in zip(starts, counts)):
+        raise ValueError(f"map_proposals: topk and the counts must not be negative and the rows must lie in the store's {R}")
+    offs = [0, *itertools.accumulate(counts)]
+    T = offs[-1]
+    if T > 2 ** 31 - 1:
+        raise ValueError(f"map_proposals: {T} rows leave int32")
+    bufs = proposal_buffers(T, n, store_rows.device) if out is None else out
+    if out is not None:
+        f, i = torch.float32, torch.int64
+        want = (((T, 4), f), ((T,), f), ((T,), i), ((T, 4), f), ((T,), f), ((T,), i), ((T,), i), ((n, 2), torch.int32))
+        if any(not b.is_contiguous() or b.device != store_rows.device or (tuple(b.shape), b.dtype) != w for b, w in zip(bufs, want)):
+            raise ValueError("map_proposals: out must be contiguous ProposalBuffers of this batch's sizes on the rows' device")
+    lib = _lib.load()
+    dtype = _lib.PROPOSAL_F32 if store_rows.dtype == torch.float32 else _lib.PROPOSAL_F64
+    with torch.cuda.device(store_rows.device):
+        for lo in range(0, n, IMAGE_BATCH_MAX_IMAGES):
+            hi = min(lo + IMAGE_BATCH_MAX_IMAGES, n)
+            m, part = hi - lo, slice(offs[lo], offs[hi])
+            ints = lambda vals: (ctypes.c_int * m)(*vals)
+            check(lib.locov_map_proposals(
+                _ptr(store_rows), R, dtype, (ctypes.c_int64 * m)(*starts[lo:hi]), ints(counts[lo:hi]),
+                (ctypes.c_double * m)(*[float(f[0]) for f in factors[lo:hi]]), (ctypes.c_double * m)(*[float(f[1]) for f in factors[lo:hi]]),
+                ints(flips[lo:hi]), ints([int(s[0]) for s in sizes[lo:hi]]), ints([int(s[1]) for s in sizes[lo:hi]]), m, int(topk), float(thr),
+                *[_ptr(b[part]) for b in bufs[:7]], _ptr(bufs.counts[lo:hi]), _stream(store_rows)), "locov_map_proposals")
+    kept = bufs.counts.tolist() if n else []                       # the call's ONE host read
+    return [MappedProposals(*[b[o:o + c[0]] for b in bufs[:3]], *[b[o:o + c[1]] for b in bufs[3:7]]) for o, c in zip(offs, kept)]
+
+
+# --------------------------------------------------------------------------------------
 # The caption path of the LSM step (csrc/caption.hip; language_backbone.py: BertEmbedding.forward_tokenized)
 CAPTION_MAX_TOKENS = _lib.CAPTION_MAX_TOKENS      # LOCOV_CAPTION_MAX_TOKENS
 CAPTION_MAX_HIDDEN = _lib.CAPTION_MAX_HIDDEN      # LOCOV_CAPTION_MAX_HIDDEN

@@ -2,6 +2,7 @@
 against Pillow on the same machine; and the resize kernel alone.
 
     timeout -k 10 600 python tools/time_data.py [--images 1 8] [--iters 50] [--warmup 10] [--threads 16] [--out records.json]
+    timeout -k 10 600 python tools/time_data.py --proposals 1000 --images 1 8 32      (the proposal side instead: proposals() below)
 
 For each source size (480 x 640 and 3000 x 4000, both to 800 x 1067: INPUT.MIN_SIZE_TEST 800, MAX_SIZE_TEST 1333) and batch size:
   (a) kernel     ops.resize_flip_images on images already on the device: device-event time per call, the kernel's device time
@@ -36,8 +37,76 @@ from time_detector import wall  # noqa: E402
 SOURCES = [(480, 640), (3000, 4000)]
 
 
+class _Metadata:
+    thing_classes = [f"class {i}" for i in range(80)]
+
+    def __init__(self, **entries):
+        self.entries = entries
+
+    def get(self, name, default=None):
+        return self.entries.get(name, default)
+
+
+def proposals(args, dev):
+    """--proposals N: CocoImageDatasetMapper.map_batch (training, MODEL.LOAD_OBJ_PROPOSALS) on 480 x 640 images with N fp32
+    proposals each, the three sides alternating in one process -- host wall time to the synchronised dicts:
+        fused     LOCOV_FUSED_PROPOSALS=1: the store's rows stay on the device, one descriptor and one launch per batch
+        host      LOCOV_FUSED_PROPOSALS=0: data.py's numpy / torch definition per image, its result moved to the device
+        no_proposals   the same mapper without object_proposals in its metadata (what the image and annotation side costs)
+    and ops.map_proposals alone: device-event time per call and the launch's own device time (torch.profiler)."""
+    import locov_amd
+    from locov_amd import data, ops
+    cfg = locov_amd.config.get_cfg()
+    cfg.MODEL.DEVICE, cfg.MODEL.LOAD_OBJ_PROPOSALS = str(dev), True
+    h, w, n_rows = 480, 640, int(args.proposals)
+    rec = {"device": torch.cuda.get_device_name(dev), "proposals_per_image": n_rows, "source": [h, w], "runs": {}}
+    for N in args.images:
+        rng = np.random.default_rng(N)
+        x1, y1 = rng.uniform(-20, w, (2, N, n_rows))
+        rows = np.stack([x1, y1, x1 + rng.uniform(-5, 300, (N, n_rows)), y1 + rng.uniform(-5, 300, (N, n_rows)),
+                         rng.uniform(0.3, 1.0, (N, n_rows))], axis=2).astype(np.float32)
+        dicts = [{"image_raw": rng.integers(0, 256, (h, w, 3), dtype=np.uint8), "image_id": i,
+                  "annotations": [{"bbox": [10.0 * k, 20.0, 100.0, 80.0], "bbox_mode": data.XYWH_ABS, "category_id": k} for k in range(7)]}
+                 for i in range(N)]
+        captions = {i: ["a caption", "another caption"] for i in range(N)}
+        with_store = data.CocoImageDatasetMapper(cfg, _Metadata(captions_dict=captions, object_proposals={i: rows[i] for i in range(N)}), True,
+                                                 device=dev, seed=1)
+        without = data.CocoImageDatasetMapper(cfg, _Metadata(captions_dict=captions), True, device=dev, seed=1)
+        sample = with_store.draw_sample(dicts)
+
+        def side(mapper, fused):
+            def step():
+                os.environ["LOCOV_FUSED_PROPOSALS"] = fused
+                return mapper.map_batch(dicts, sample)
+            return step
+
+        sides = {"fused": side(with_store, "1"), "host": side(with_store, "0"), "no_proposals": side(without, "1")}
+        for a, b in zip(sides["fused"](), sides["host"]()):
+            assert torch.equal(a["instances"].gt_boxes.tensor, b["instances"].gt_boxes.tensor), "the device path and the definition differ"
+        ms = {k: [] for k in sides}
+        names = list(sides)
+        for it in range(args.warmup + args.iters):
+            for k in (names if it % 2 == 0 else names[::-1]):
+                t = wall(sides[k], 1, 0)
+                if it >= args.warmup:
+                    ms[k].append(t["median_ms"])
+        size = data.ResizeShortestEdge.get_output_shape(h, w, 800, 1333)
+        table = [with_store.store.table[i] for i in range(N)]
+        launch = lambda: ops.map_proposals(with_store.store.rows, [s for s, _ in table], [n for _, n in table], [(size[1] / w, size[0] / h)] * N,
+                                           [int(f) for f in sample["flip"]], [size] * N, cfg.DATASETS.PRECOMPUTED_PROPOSAL_TOPK_TRAIN, data.OBJECTNESS_THR)
+        r = {"map_batch": {k: {"median_ms": float(np.median(v)), "p10_ms": float(np.percentile(v, 10)), "p90_ms": float(np.percentile(v, 90))}
+                           for k, v in ms.items()},
+             "pseudo_gt_per_image": [len(d["instances"]) for d in sides["fused"]()][:4],
+             "map_proposals": dict(alternate({"call": launch}, args.iters, args.warmup)["call"], device=kernels(launch, top=2))}
+        rec["runs"][f"images_{N}"] = r
+        print(json.dumps({f"proposals {n_rows} images {N}": r}), flush=True)
+    os.environ.pop("LOCOV_FUSED_PROPOSALS", None)
+    return rec
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--proposals", type=int, default=0, help="rows per image: time the proposal side of the mapper instead (see proposals())")
     ap.add_argument("--images", type=int, nargs="+", default=[1, 8])
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
@@ -50,6 +119,15 @@ def main(argv=None):
         raise SystemExit("time_data: needs a ROCm GPU")
     if args.iters < 50 or args.warmup < 10:
         raise SystemExit("time_data: the protocol asks for >= 10 warm-up and >= 50 timed iterations")
+    if args.proposals > 0:
+        dev = torch.device("cuda:0")
+        torch.cuda.set_device(dev)
+        rec = proposals(args, dev)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                json.dump(rec, f, indent=1)
+        return
     import locov_amd
     from locov_amd import data, ops
     try:
