@@ -40,7 +40,8 @@ extern "C" {
  *    locov_resnet_stem_fwd, locov_resnet_stem_fwd_sel, locov_resnet_stem_wgrad (+ _workspace_bytes),
  *    locov_preprocess_images, locov_detector_rescale, locov_sgd_step (+ _workspace_bytes),
  *    locov_coco_match (+ _workspace_bytes), locov_coco_accumulate, locov_lvis_match,
- *    locov_resize_flip_images, locov_resize_supported, locov_map_proposals */
+ *    locov_resize_flip_images, locov_resize_supported, locov_map_proposals,
+ *    locov_augment_images (+ _workspace_bytes), locov_augment_supported */
 #define LOCOV_ABI_VERSION 8
 
 #define LOCOV_OK 0
@@ -1371,6 +1372,79 @@ int locov_resize_supported(int in_h, int in_w, int out_h, int out_w, int channel
 int locov_resize_flip_images(const void *const *images_host, const int *heights_host, const int *widths_host, void *const *outs_host,
                              const int *out_heights_host, const int *out_widths_host, const int *flips_host, int n_images, int channels,
                              locov_stream_t stream);
+
+/* ---- the strong augmentation of the dataset mapper for the whole batch (csrc/image_augment.hip) -------------------------------
+ * Added under ABI version 8.  What BasicTextImageDatasetMapper.__call__ (ovr/data/mappers/basic_mappers.py:171-180) does with the
+ * Compose of build_complete_augmentation (ovr/data/detection_utils.py:60-100) AFTER the resize and flip: torchvision's ColorJitter,
+ * RandomGrayscale, the reference's GaussianBlur (Pillow's ImageFilter.GaussianBlur) and three RandomErasing between ToTensor and
+ * ToPILImage.  The draws are made by the caller; the bytes are Pillow's and torch's, bit for bit.
+ *
+ * locov_augment_images:
+ *   images_host : host array of n_images DEVICE pointers; image n is uint8 [3, height, width] PLANAR (what
+ *                 locov_resize_flip_images writes), contiguous, aligned to one byte only.  Plane 0 plays R.
+ *   outs_host   : host array of n_images DEVICE pointers to outputs of the same shape, each distinct from every input (the blur
+ *                 reads a pixel's neighbours).  EVERY byte of an output is written, nothing else.
+ *   descs_host  : host array of n_images locov_augment_desc, one image's draws each:
+ *     height, width : the image's size.
+ *     n_ops, ops  : the colour jitter, 0 .. 4 DISTINCT operations LOCOV_AUG_OP_* in the order they run (n_ops == 0: no jitter).
+ *     brightness, contrast, saturation : ImageEnhance's factors, i.e. Image.blend(degenerate, image, f): in fp32
+ *                   t = d + f * (x - d), the product rounded before the sum; for 0 <= f <= 1 the byte is (int)t, otherwise 0 for
+ *                   t <= 0, 255 for t >= 255, else (int)t.  d is 0 (brightness), the pixel's L (saturation) and
+ *                   (int)(sum(L) / (height * width) + 0.5), the division in fp64, over the WHOLE image as it stands when contrast
+ *                   runs.  L = (r * 19595 + g * 38470 + b * 7471 + 0x8000) >> 16.
+ *     hue_shift   : 0 .. 255, added modulo 256 to H between Pillow's convert("HSV") and convert("RGB"), which run even for 0.
+ *                   RGB -> HSV: v = max; max == min gives h = s = 0; else in fp32 cr = max - min, s = cr / max, rc = (max - r) / cr
+ *                   (gc, bc alike), h = bc - gc | 2 + rc - bc | 4 + gc - rc for r, g or b the maximum (tested in that order), summed
+ *                   in fp64 from the fp32 terms and rounded to fp32, h = fmod(h / 6 + 1, 1) in fp64 rounded to fp32, and the bytes
+ *                   are (int)((double)h * 255), (int)((double)s * 255).  HSV -> RGB in fp64: s == 0 gives grey v; else fs = s / 255,
+ *                   i = floor(h * 6 / 255), f = h * 6 / 255 - i, p = floor(v * (1 - fs) + 0.5), q = floor(v * (1 - fs * f) + 0.5),
+ *                   t = floor(v * (1 - fs * (1 - f)) + 0.5), and i % 6 selects (v,t,p) (q,v,p) (p,v,t) (p,q,v) (t,p,v) (v,p,q).
+ *     gray        : non-zero writes L to all three planes, after the jitter.
+ *     sigma       : 0 for no blur, else ImageFilter.GaussianBlur(radius = sigma): with s2 = sigma * sigma / 3 (fp32),
+ *                   L = (float)sqrt(12.0 * s2 + 1.0), l = (float)floor((L - 1.0) / 2.0), a = (2l + 1)(l(l + 1) - 3 s2) / (6 (s2 -
+ *                   (l + 1)^2)) in fp32, the box radius is fr = l + a.  Three horizontal box passes, then three vertical, each
+ *                   writing rounded bytes the next one reads: radius = (int)fr, ww = (uint32)(2^24 / (fr * 2 + 1)) (fp32 division),
+ *                   fw = (2^24 - (2 radius + 1) ww) / 2, out[x] = (ww * sum(in[x - radius .. x + radius]) + fw * (in[x - radius - 1]
+ *                   + in[x + radius + 1]) + 2^23) >> 24 in uint32, indices clamped to the line.
+ *     n_erase, erase : 0 .. LOCOV_AUG_MAX_ERASERS rectangles (i, j, eh, ew) inside the image (an empty one is allowed), applied in
+ *                   order, so a later one wins.  Eraser e takes its [3, eh, ew] fp32 values, plane-major, from `noise` at
+ *                   noise_offset + 3 * (the areas of the erasers before it), and writes (int)(v * 255.0f) & 255.
+ *     noise_offset : the image's first element in `noise`.
+ *   noise       : device, fp32 [n_noise], aligned to 4 bytes; may be NULL when no eraser reads it.
+ *   workspace   : device, aligned to 16 bytes, locov_augment_images_workspace_bytes(descs_host, n_images) bytes: the derived
+ *                 per-image table (copied there from the host on `stream`) and the contrast partials.
+ *   The table's copy is a hipMemcpyAsync from PAGEABLE host memory: the library's buffer is free once the call returns, but the
+ *   runtime may make the host wait until `stream` has drained before it stages the bytes, so the call is ordered on `stream`
+ *   without being asynchronous to the host (no pinned staging buffer is kept).
+ *   At most two launches and one host-to-device copy on `stream`, nothing read by the host: (1), only when some image's chain has
+ *   contrast, a workgroup redoes the operations before contrast on 4 096 pixels and writes their INTEGER sum of L to the workspace;
+ *   (2) a workgroup owns 32 x 64 output pixels, sums its image's partials, loads the tile with a halo of 3 * ((int)fr + 1) pixels
+ *   per side, runs jitter and grayscale in registers, the six box passes in LDS and substitutes the erasers' bytes at the store.
+ *   No atomics; no floating-point reduction; vector stores only; two calls give the same bits.
+ *   Supported sigma: (int)fr + 1 <= 2, which holds for 0 < sigma up to about 2.449 and so for the reference's [0.1, 2.0];
+ *   locov_augment_supported answers without a launch (1 / 0).
+ *   n_images == 0: LOCOV_OK, nothing is touched.  More than LOCOV_LABEL_MAX_IMAGES images, a null pointer, an output that is its
+ *   input, a size < 1, height * width * 3 above 2^31 - 1, an unknown or repeated operation, a factor that is not finite, hue_shift
+ *   outside 0 .. 255, a sigma that is neither 0 nor supported, more erasers than the maximum, a rectangle outside the image, noise
+ *   read before 0 or past n_noise, a misaligned or too small workspace: LOCOV_ERR_INVALID_ARG before any HIP call. */
+#define LOCOV_AUG_OP_BRIGHTNESS 1
+#define LOCOV_AUG_OP_CONTRAST 2
+#define LOCOV_AUG_OP_SATURATION 3
+#define LOCOV_AUG_OP_HUE 4
+#define LOCOV_AUG_MAX_ERASERS 3
+typedef struct locov_augment_desc {
+    int32_t height, width;
+    int32_t n_ops, ops[4];
+    float brightness, contrast, saturation;
+    int32_t hue_shift, gray;
+    float sigma;
+    int32_t n_erase, erase[LOCOV_AUG_MAX_ERASERS][4];
+    int64_t noise_offset;
+} locov_augment_desc;
+int locov_augment_supported(float sigma);
+int64_t locov_augment_images_workspace_bytes(const locov_augment_desc *descs_host, int n_images);
+int locov_augment_images(const void *const *images_host, void *const *outs_host, const locov_augment_desc *descs_host, int n_images,
+                         const float *noise, int64_t n_noise, void *workspace, int64_t workspace_bytes, locov_stream_t stream);
 
 /* ---- the proposal side of the dataset mapper in one launch for the whole batch (csrc/proposal_map.hip) ------------------------
  * Added under ABI version 8.  What the mapper does with an image's precomputed proposals under MODEL.LOAD_OBJ_PROPOSALS

@@ -28,3 +28,4 @@ from . import evaluation  # noqa: F401,E402
 from .evaluation import COCOEvaluator, LVISEvaluator, build_evaluator, inference_on_dataset  # noqa: F401,E402
 from . import data  # noqa: F401,E402
 from .data import DatasetMapper, build_augmentation, iterate_batches, resize_bilinear_host  # noqa: F401,E402
+from .strong_augment import StrongAugmentation, build_complete_augmentation  # noqa: F401,E402

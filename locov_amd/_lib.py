@@ -48,6 +48,7 @@ COCO_MAX_DET, COCO_MAX_BLOCKS = 4096, 8388608
 LVIS_CELL_NEG, LVIS_CELL_NOT_EXHAUSTIVE = 1, 2
 RESIZE_MAX_TAPS, FLIP_NONE, FLIP_HORIZONTAL, FLIP_VERTICAL = 17, 0, 1, 2
 PROPOSAL_F32, PROPOSAL_F64 = 0, 1
+AUG_OP_BRIGHTNESS, AUG_OP_CONTRAST, AUG_OP_SATURATION, AUG_OP_HUE, AUG_MAX_ERASERS = 1, 2, 3, 4, 3
 
 _p = c_void_p  # device pointer
 
@@ -59,6 +60,14 @@ PREP_PLAIN, PREP_TRANSPOSE, PREP_IM2COL, PREP_IM2COL_FLIP, PREP_WINO, PREP_WINO_
 class WeightPrepJob(ctypes.Structure):
     """locov_weight_prep_job of include/locov_hip.h"""
     _fields_ = [("w", c_void_p), ("row_scale", c_void_p), ("out", c_void_p), ("scale", c_float), ("kind", c_int), ("N", c_int), ("K", c_int)]
+
+
+class AugmentDesc(ctypes.Structure):
+    """locov_augment_desc of include/locov_hip.h"""
+    _fields_ = [("height", ctypes.c_int32), ("width", ctypes.c_int32), ("n_ops", ctypes.c_int32), ("ops", ctypes.c_int32 * 4),
+                ("brightness", c_float), ("contrast", c_float), ("saturation", c_float), ("hue_shift", ctypes.c_int32),
+                ("gray", ctypes.c_int32), ("sigma", c_float), ("n_erase", ctypes.c_int32),
+                ("erase", (ctypes.c_int32 * 4) * AUG_MAX_ERASERS), ("noise_offset", c_int64)]
 
 
 # name -> (restype, argtypes); mirrors include/locov_hip.h declaration by declaration
@@ -252,6 +261,9 @@ SIGNATURES = {
     "locov_map_proposals": (c_int, [_p, c_int64, c_int, POINTER(c_int64), POINTER(c_int), POINTER(c_double), POINTER(c_double),
                                     POINTER(c_int), POINTER(c_int), POINTER(c_int), c_int, c_int, c_float, _p, _p, _p, _p, _p, _p, _p,
                                     _p, _p]),
+    "locov_augment_supported": (c_int, [c_float]),
+    "locov_augment_images_workspace_bytes": (c_int64, [POINTER(AugmentDesc), c_int]),
+    "locov_augment_images": (c_int, [POINTER(c_void_p), POINTER(c_void_p), POINTER(AugmentDesc), c_int, _p, c_int64, _p, c_int64, _p]),
 }
 
 _lib = None

@@ -33,9 +33,15 @@ filter_empty_instances, transform_proposals.  annotations_to_instances and check
 (ovr/data/mappers/coco_mappers.py:24-106, __init__.py:11-35).  The annotated boxes stay on the host, in float64 numpy as upstream: a
 handful of boxes per image.
 
-Not built: INPUT.CROP, the strong augmentations (COLOR_JITTER, RANDOM_GRAY_SCALE, GAUSSIAN_BLUR, RANDOM_ERASE), masks, keypoints,
-VawImageDatasetMapper, TextImageDatasetMapperNoise and its NOISE_* options, dataset registration and reading the proposal file --
-the first two groups and the two mappers are refused with an error, never ignored.
+The strong augmentations (INPUT.COLOR_JITTER, RANDOM_GRAY_SCALE, GAUSSIAN_BLUR, RANDOM_ERASE; basic_mappers.py:171-180) are opt-in
+through the reference's own constructor parameter: DatasetMapper(cfg, is_train, device, seed, train_aug =
+strong_augment.build_complete_augmentation(cfg, is_train)).  strong_augment.apply_host is their definition (Pillow's and
+torchvision's bytes); on a cuda device the batch goes through ops.augment_images (csrc/image_augment.hip) in at most two launches
+after the resize's one.  The host path serves CPU tensors, LOCOV_FUSED_AUGMENT=0 and a sigma outside ops.augment_supported.
+Without train_aug the four keys are refused as before, and build_augmentation refuses them always.
+
+Not built: INPUT.CROP, masks, keypoints, VawImageDatasetMapper, TextImageDatasetMapperNoise and its NOISE_* options, dataset
+registration and reading the proposal file -- the crop and the two mappers are refused with an error, never ignored.
 """
 from __future__ import annotations
 
@@ -249,11 +255,14 @@ class RandomFlip:
         return HFlipTransform(w) if self.horizontal else VFlipTransform(h)
 
 
-def _refuse_unbuilt(cfg) -> None:
+def _refuse_unbuilt(cfg, strong_given: bool = False) -> None:
+    """strong_given: the caller holds a StrongAugmentation (DatasetMapper's train_aug), which lifts the four strong keys only."""
     inp = cfg.INPUT
     crop = getattr(inp, "CROP", None)
     if crop is not None and getattr(crop, "ENABLED", False):
         raise NotImplementedError("INPUT.CROP.ENABLED: RandomCrop is not built (locov_amd.data)")
+    if strong_given:
+        return
     for key, off in (("COLOR_JITTER", 0.0), ("RANDOM_GRAY_SCALE", False), ("GAUSSIAN_BLUR", False), ("RANDOM_ERASE", False)):
         v = getattr(inp, key, off)
         if (v > 0) if key == "COLOR_JITTER" else bool(v):
@@ -261,8 +270,13 @@ def _refuse_unbuilt(cfg) -> None:
 
 
 def build_augmentation(cfg, is_train: bool) -> list:
-    """[ResizeShortestEdge] plus, in training and unless INPUT.RANDOM_FLIP is "none", [RandomFlip]."""
+    """[ResizeShortestEdge] plus, in training and unless INPUT.RANDOM_FLIP is "none", [RandomFlip].  The strong keys are refused
+    here, always: they are served by DatasetMapper(..., train_aug=strong_augment.build_complete_augmentation(cfg, is_train))."""
     _refuse_unbuilt(cfg)
+    return _resize_and_flip(cfg, is_train)
+
+
+def _resize_and_flip(cfg, is_train: bool) -> list:
     if is_train:
         min_size, max_size, sample_style = cfg.INPUT.MIN_SIZE_TRAIN, cfg.INPUT.MAX_SIZE_TRAIN, cfg.INPUT.MIN_SIZE_TRAIN_SAMPLING
     else:
@@ -434,6 +448,10 @@ def _fused_enabled() -> bool:
     return os.environ.get("LOCOV_FUSED_RESIZE", "1") != "0"
 
 
+def _fused_augment_enabled() -> bool:
+    return os.environ.get("LOCOV_FUSED_AUGMENT", "1") != "0"
+
+
 def _fused_proposals_enabled() -> bool:
     return os.environ.get("LOCOV_FUSED_PROPOSALS", "1") != "0"
 
@@ -466,12 +484,21 @@ class DatasetMapper:
     `device`.  On a cuda device the batch's rows are packed into one pinned buffer, uploaded once and mapped in one launch
     (ops.map_proposals); LOCOV_FUSED_PROPOSALS=0, a CPU device and rows that are not fp32 / fp64 take the host definition.
 
+    train_aug: None, or strong_augment.build_complete_augmentation(cfg, is_train).  Given, it lifts the refusal of the four strong
+    keys (INPUT.CROP stays refused) and is applied in training to "image" after the resize and flip; boxes, captions and proposals
+    are untouched.  draw_sample then also returns "strong" (StrongAugmentation.draw's dict per image, drawn for the resized size)
+    and "erase_seed"; the erasers' noise is torch.randn on `device` from a torch.Generator seeded with it (erase_noise), or
+    sample["erase_noise"] when the caller carries noise from one device to another.
+
     Every random draw comes from draw_sample(dataset_dicts) (the edge length, the flip and the caption index per image, from
     self.rng); map_batch(dataset_dicts, sample=...) replays one."""
 
-    def __init__(self, cfg, is_train: bool = True, device=None, seed: Optional[int] = None):
+    def __init__(self, cfg, is_train: bool = True, device=None, seed: Optional[int] = None, train_aug=None):
         self.is_train = bool(is_train)
-        self.augmentations = build_augmentation(cfg, is_train)
+        _refuse_unbuilt(cfg, strong_given=train_aug is not None)
+        self.augmentations = _resize_and_flip(cfg, is_train)
+        self._decoded: Optional[Dict[str, Optional[np.ndarray]]] = None   # files draw_sample read for their size (train_aug only), until _raw takes them
+        self.train_aug = train_aug if self.is_train else None      # (basic_mappers.py:171: applied in training only)
         if getattr(cfg.MODEL, "MASK_ON", False) or getattr(cfg.MODEL, "KEYPOINT_ON", False):
             raise NotImplementedError("MODEL.MASK_ON / KEYPOINT_ON: only the box side of the mapper is built")
         self.proposal_topk: Optional[int] = None                   # (basic_mappers.py:82-87)
@@ -491,12 +518,40 @@ class DatasetMapper:
         resize = self.augmentations[0]
         flip = self.augmentations[1] if len(self.augmentations) > 1 else None
         sample = {"short_edge": [], "flip": [], "caption": []}
+        if self._decoded:
+            self._decoded.clear()
         for d in dataset_dicts:
             sample["short_edge"].append(int(resize.draw(self.rng)))
             sample["flip"].append(bool(flip.draw(self.rng)) if flip is not None else False)
             cap = self._caption_choices(d)
             sample["caption"].append(self.rng.randrange(len(cap)) if self.is_train and isinstance(cap, list) and len(cap) else 0)
+            if self.train_aug is not None:
+                h, w = self._raw_size(d)
+                nh, nw = resize.get_transform(h, w, sample["short_edge"][-1]).output_shape(h, w)
+                sample.setdefault("strong", []).append(self.train_aug.draw(self.rng, nh, nw))
+        if self.train_aug is not None:
+            sample.setdefault("strong", [])
+            sample["erase_seed"] = self.rng.getrandbits(62)
         return sample
+
+    def _raw_size(self, d: dict) -> Tuple[int, int]:
+        """(h, w) of the image _raw will return: the erasers are drawn for the resized image's size.  A file is DECODED here, once,
+        and kept for _raw: whether the black-image fallback applies is known only after the decode (a truncated file has a header),
+        and the draws must be for the image the batch will really hold."""
+        raw = d.get("image_raw")
+        if raw is not None:
+            return int(raw.shape[0]), int(raw.shape[1])
+        try:
+            image = _read_file(d["file_name"], self.image_format)
+        except Exception:
+            image = None
+        if "file_name" in d:
+            if self._decoded is None:
+                self._decoded = {}
+            self._decoded[d["file_name"]] = image
+        if image is None:
+            return int(d["height"]), int(d["width"])               # (the black image of _raw)
+        return int(image.shape[0]), int(image.shape[1])
 
     # -- one image's host-side part: the raw image, the transforms, the boxes, the caption
     def _raw(self, d: dict):
@@ -508,6 +563,11 @@ class DatasetMapper:
                 raise TypeError(f"image_raw must be uint8 [H, W, C], got {raw.dtype} {tuple(raw.shape)}")
             return raw, True
         try:
+            if self._decoded and d.get("file_name") in self._decoded:                # (draw_sample read it for its size; None: it failed there)
+                image = self._decoded.pop(d["file_name"])
+                if image is None:
+                    raise OSError("not decoded")
+                return image, True
             return _read_file(d["file_name"], self.image_format), True
         except Exception:
             print("Image not loaded {}, replaced by black image".format(d.get("file_name")))
@@ -545,6 +605,8 @@ class DatasetMapper:
         dataset_dicts = list(dataset_dicts)
         sample = self.draw_sample(dataset_dicts) if sample is None else sample
         prepared = [self._prepare(d, i, sample) for i, d in enumerate(dataset_dicts)]
+        if self._decoded:
+            self._decoded.clear()
         on_device = self.device.type == "cuda" and _fused_enabled()
         fused: Dict[int, List[int]] = {}                           # channel count -> the images the kernel takes
         images: List[Optional[torch.Tensor]] = [None] * len(prepared)
@@ -563,7 +625,57 @@ class DatasetMapper:
                         images[i] = image
         for image, (d, raw, transforms, _) in zip(images, prepared):
             d["image"] = image if image is not None else self._host_image(raw, transforms)
+        if self.train_aug is not None:
+            self._strong(prepared, sample)
         return self._finish(prepared)
+
+    def erase_noise(self, sample: Dict[str, list]) -> torch.Tensor:
+        """The erasers' normal draws of a sample, fp32 [sum of the images' noise_count] on the mapper's device, image after image:
+        sample["erase_noise"] when the caller gives it (e.g. copied from another device), else torch.randn from a torch.Generator
+        on the device seeded with sample["erase_seed"]."""
+        from .strong_augment import noise_count
+        total = sum(noise_count(s) for s in sample["strong"])
+        given = sample.get("erase_noise")
+        if given is not None:
+            if given.dtype != torch.float32 or given.dim() != 1 or given.numel() < total:
+                raise ValueError(f"sample['erase_noise'] must be fp32 [>= {total}], got {given.dtype} {tuple(given.shape)}")
+            return given.to(self.device)
+        gen = torch.Generator(device=self.device)
+        gen.manual_seed(int(sample["erase_seed"]))
+        return torch.randn(total, generator=gen, device=self.device, dtype=torch.float32)
+
+    def _strong(self, prepared, sample: Dict[str, list]) -> None:
+        """The strong augmentation of the batch's "image" entries, after the resize and flip (basic_mappers.py:171-180)."""
+        from . import strong_augment as sa
+        draws = list(sample["strong"])
+        if len(draws) != len(prepared):
+            raise ValueError(f"sample['strong'] holds {len(draws)} entries for {len(prepared)} images")
+        for s, (d, _, _, (nh, nw)) in zip(draws, prepared):
+            if tuple(d["image"].shape[1:]) != (nh, nw) or any(e is not None and (e[0] + e[2] > nh or e[1] + e[3] > nw) for e in s["erase"]):
+                raise ValueError(f"sample['strong']: an eraser was drawn for another size than the image's {(nh, nw)}")
+        noise = self.erase_noise(sample)
+        counts = [sa.noise_count(s) for s in draws]
+        offsets = [0] + list(np.cumsum(counts)[:-1])
+        fused: List[int] = []
+        if self.device.type == "cuda" and _fused_augment_enabled():
+            from . import ops
+            fused = [i for i, (s, p) in enumerate(zip(draws, prepared))
+                     if p[0]["image"].shape[0] == 3 and (not s["blur"] or ops.augment_supported(s["sigma"]))]
+            for lo in range(0, len(fused), ops.IMAGE_BATCH_MAX_IMAGES):
+                part = fused[lo:lo + ops.IMAGE_BATCH_MAX_IMAGES]
+                outs = ops.augment_images([prepared[i][0]["image"] for i in part], [draws[i] for i in part], noise,
+                                          [int(offsets[i]) for i in part])
+                for i, image in zip(part, outs):
+                    prepared[i][0]["image"] = image
+        host_noise = None
+        for i, (s, p) in enumerate(zip(draws, prepared)):
+            if i in fused:
+                continue
+            if host_noise is None:
+                host_noise = noise.cpu().numpy()
+            hwc = p[0]["image"].permute(1, 2, 0).cpu().numpy()
+            out = sa.apply_host(hwc, s, host_noise[offsets[i]:offsets[i] + counts[i]])
+            p[0]["image"] = torch.as_tensor(np.ascontiguousarray(out.transpose(2, 0, 1))).to(self.device)
 
     def __call__(self, dataset_dict: dict, sample: Optional[Dict[str, list]] = None) -> dict:
         return self.map_batch([dataset_dict], sample)[0]
@@ -640,8 +752,8 @@ class CocoImageDatasetMapper(DatasetMapper):
         and removes "proposals".  With the store on a cuda device both steps are ops.map_proposals' one launch on rows that never
         leave the device; "instances" is on the device, "gt_obj" on the host."""
 
-    def __init__(self, cfg, metadata, is_train: bool = True, device=None, seed: Optional[int] = None):
-        super().__init__(cfg, is_train, device, seed)
+    def __init__(self, cfg, metadata, is_train: bool = True, device=None, seed: Optional[int] = None, train_aug=None):
+        super().__init__(cfg, is_train, device, seed, train_aug)
         self.metadata = metadata
         store = metadata.get("object_proposals")
         if store is not None and not isinstance(store, ProposalStore):
@@ -683,15 +795,15 @@ class CocoImageDatasetMapper(DatasetMapper):
         return [p[0] if fused and "gt_obj" in p[0] else change_proposals_as_gt(p[0]) for p in prepared]
 
 
-def get_mapper(dataset_name: str, cfg, is_train: bool, metadata=None, device=None) -> DatasetMapper:
+def get_mapper(dataset_name: str, cfg, is_train: bool, metadata=None, device=None, train_aug=None) -> DatasetMapper:
     """ovr/data/mappers/__init__.py:11-35 with the metadata given by the caller: "coco" -> CocoImageDatasetMapper, "lvis" ->
-    DatasetMapper; the "vaw" mapper and the noise mapper of every other name are not built."""
+    DatasetMapper; the "vaw" mapper and the noise mapper of every other name are not built.  train_aug: the mappers' argument."""
     if "coco" in dataset_name:
-        return CocoImageDatasetMapper(cfg, metadata, is_train, device=device)
+        return CocoImageDatasetMapper(cfg, metadata, is_train, device=device, train_aug=train_aug)
     if "vaw" in dataset_name:
         raise NotImplementedError(f"{dataset_name}: VawImageDatasetMapper is not built (locov_amd.data)")
     if "lvis" in dataset_name:
-        return DatasetMapper(cfg, is_train, device=device)
+        return DatasetMapper(cfg, is_train, device=device, train_aug=train_aug)
     raise NotImplementedError(f"{dataset_name}: TextImageDatasetMapperNoise is not built (locov_amd.data)")
 
 

@@ -2787,6 +2787,91 @@ def resize_flip_images(images: Sequence[torch.Tensor], out_sizes, flips: Optiona
 
 
 # --------------------------------------------------------------------------------------
+# The strong augmentation of the dataset mapper (csrc/image_augment.hip; strong_augment.py: apply_host is the definition)
+AUG_MAX_ERASERS = _lib.AUG_MAX_ERASERS            # LOCOV_AUG_MAX_ERASERS
+
+
+def augment_supported(sigma: float) -> bool:
+    """Whether locov_augment_images takes a blur of this sigma: a box pass may reach two pixels, which holds for 0 < sigma up to
+    about 2.449 and so for the reference's [0.1, 2.0].  No launch; the library's own rule."""
+    sigma = float(sigma)
+    return sigma == sigma and bool(_lib.load().locov_augment_supported(sigma))
+
+
+def _augment_desc(desc, draws: dict, h: int, w: int, noise_offset: int) -> int:
+    """Fills one locov_augment_desc from StrongAugmentation.draw's dict; returns the noise elements the image takes."""
+    from . import strong_augment as sa
+    chain = sa.jitter_chain(draws)
+    if len(chain) > 4 or len(draws["erase"]) > AUG_MAX_ERASERS:
+        raise ValueError(f"augment_images: at most 4 jitter operations and {AUG_MAX_ERASERS} erasers per image")
+    desc.height, desc.width, desc.n_ops = h, w, len(chain)
+    for k, (op, _) in enumerate(chain):
+        desc.ops[k] = op
+    desc.brightness, desc.contrast, desc.saturation = float(draws["brightness"]), float(draws["contrast"]), float(draws["saturation"])
+    desc.hue_shift = sa.hue_shift(draws["hue"])
+    desc.gray = int(bool(draws["gray"]))
+    desc.sigma = float(draws["sigma"]) if draws["blur"] else 0.0
+    if draws["blur"] and not augment_supported(draws["sigma"]):
+        raise ValueError(f"augment_images: sigma {draws['sigma']} is outside augment_supported: the caller takes strong_augment.apply_host")
+    rects = [e for e in draws["erase"] if e is not None]
+    desc.n_erase, desc.noise_offset = len(rects), noise_offset
+    for k, rect in enumerate(rects):
+        for m in range(4):
+            desc.erase[k][m] = int(rect[m])
+    return sa.noise_count(draws)
+
+
+def augment_images(images: Sequence[torch.Tensor], draws: Sequence[dict], noise: Optional[torch.Tensor] = None,
+                   noise_offsets: Optional[Sequence[int]] = None, out: Optional[Sequence[torch.Tensor]] = None) -> List[torch.Tensor]:
+    """The strong augmentation of N uint8 [3, h_i, w_i] device images (what resize_flip_images returns), image i by draws[i] =
+    StrongAugmentation.draw's dict, in at most two launches (locov_augment_images) and no host read: the bytes of
+    strong_augment.apply_host, i.e. of torchvision's ColorJitter / RandomGrayscale / RandomErasing over Pillow and Pillow's
+    GaussianBlur.  noise: device fp32 [n], the erasers' normal draws; image i reads from noise_offsets[i] (default: the images'
+    blocks one after the other).  Returns N fresh uint8 [3, h_i, w_i] tensors, or `out` (distinct from the inputs), every byte of
+    which is written.  A sigma outside augment_supported raises: the caller takes apply_host for that image."""
+    images, draws = list(images), list(draws)
+    n = len(images)
+    if n == 0:
+        return []
+    ims = [_dev(t, f"images[{i}]", dtype=torch.uint8) for i, t in enumerate(images)]
+    if any(t.dim() != 3 or t.shape[0] != 3 or min(t.shape[1:]) < 1 or t.device != ims[0].device for t in ims):
+        raise ValueError("augment_images: the images must be non-empty [3, H, W], on one device")
+    if len(draws) != n or n > IMAGE_BATCH_MAX_IMAGES or (noise_offsets is not None and len(noise_offsets) != n):
+        raise ValueError(f"augment_images: one dict of draws (and one noise offset) per image, at most {IMAGE_BATCH_MAX_IMAGES} images")
+    descs = (_lib.AugmentDesc * n)()
+    at, end = 0, 0                                                 # end: one past the last noise element an eraser reads
+    for i, (t, d) in enumerate(zip(ims, draws)):
+        if noise_offsets is not None:
+            at = int(noise_offsets[i])
+        took = _augment_desc(descs[i], d, int(t.shape[1]), int(t.shape[2]), at)
+        if took and at < 0:
+            raise ValueError(f"augment_images: noise_offsets[{i}] is negative")
+        end = max(end, at + took) if took else end
+        at += took
+    n_noise = 0
+    if end:
+        noise = _dev(noise, "noise", dtype=torch.float32) if noise is not None else None
+        if noise is None or noise.dim() != 1 or noise.device != ims[0].device or end > noise.numel():
+            raise ValueError(f"augment_images: noise must be a device fp32 [>= {end}] vector holding every eraser's block")
+        n_noise = int(noise.numel())
+    if out is None:
+        outs = [torch.empty_like(t) for t in ims]
+    else:
+        outs = list(out)
+        if len(outs) != n or any(o.dtype != torch.uint8 or o.shape != t.shape or o.device != t.device or not o.is_contiguous()
+                                 or o.data_ptr() == t.data_ptr() for o, t in zip(outs, ims)):
+            raise ValueError("augment_images: out must hold one contiguous uint8 tensor of each image's shape, on its device, not the image itself")
+    lib = _lib.load()
+    ws_bytes = int(lib.locov_augment_images_workspace_bytes(descs, n))
+    workspace = torch.empty(ws_bytes, dtype=torch.uint8, device=ims[0].device)
+    with torch.cuda.device(ims[0].device):
+        check(lib.locov_augment_images(
+            (ctypes.c_void_p * n)(*[t.data_ptr() for t in ims]), (ctypes.c_void_p * n)(*[o.data_ptr() for o in outs]), descs, n,
+            _ptr(noise) if n_noise else None, n_noise, _ptr(workspace), ws_bytes, _stream(ims[0])), "locov_augment_images")
+    return outs
+
+
+# --------------------------------------------------------------------------------------
 # The proposal side of the dataset mapper (csrc/proposal_map.hip; data.py: transform_proposals + change_proposals_as_gt)
 PROPOSAL_DTYPES = (torch.float32, torch.float64)  # the row dtypes locov_map_proposals takes; any other goes to data.py's host definition
 

@@ -3,6 +3,7 @@ against Pillow on the same machine; and the resize kernel alone.
 
     timeout -k 10 600 python tools/time_data.py [--images 1 8] [--iters 50] [--warmup 10] [--threads 16] [--out records.json]
     timeout -k 10 600 python tools/time_data.py --proposals 1000 --images 1 8 32      (the proposal side instead: proposals() below)
+    timeout -k 10 600 python tools/time_data.py --strong --images 8                   (the strong augmentation instead: strong() below)
 
 For each source size (480 x 640 and 3000 x 4000, both to 800 x 1067: INPUT.MIN_SIZE_TEST 800, MAX_SIZE_TEST 1333) and batch size:
   (a) kernel     ops.resize_flip_images on images already on the device: device-event time per call, the kernel's device time
@@ -104,8 +105,122 @@ def proposals(args, dev):
     return rec
 
 
+STRONG_GROUPS = {"all": dict(COLOR_JITTER=0.4, RANDOM_GRAY_SCALE=True, GAUSSIAN_BLUR=True, RANDOM_ERASE=True),
+                 "blur": dict(GAUSSIAN_BLUR=True), "jitter": dict(COLOR_JITTER=0.4)}
+
+
+def strong(args, dev):
+    """--strong: DatasetMapper.map_batch (training) with train_aug on 480 x 640 images to 800 x 1067, for all four groups, the blur
+    alone and the jitter alone.  Every configured group is APPLIED to every image (the RandomApply probabilities and the erasers'
+    are forced to 1; grayscale keeps its 0.2): the most work the config can ask for.  Per group set:
+        map_batch    host wall time to the synchronised dicts: device (resize + augmentation launches), resize_only (the same
+                     mapper without train_aug), host (LOCOV_FUSED_AUGMENT=0: strong_augment.apply_host per image)
+        launches     ops.augment_images on images already on the device: device-event time per call and each launch's device time
+                     (torch.profiler), beside the algorithmic bytes -- every image read and written once, the contrast pass's
+                     second read, the erasers' noise -- at the measured copy rate --copy-tbs
+        pillow       the reference's own chain (ImageEnhance / convert / GaussianBlur, the erasers' torch expression) on the
+                     resized images with the same draws, then .to(device): one thread, and a pool of --threads threads"""
+    import locov_amd
+    from locov_amd import data, ops
+    from locov_amd import strong_augment as sa
+    try:
+        from PIL import Image, ImageEnhance, ImageFilter
+    except ImportError:
+        Image = None
+    h, w = 480, 640
+    rec = {"device": torch.cuda.get_device_name(dev), "source": [h, w], "copy_tbs": args.copy_tbs, "runs": {}}
+    pool = ThreadPoolExecutor(max_workers=args.threads)
+
+    def pillow_one(chw, d, noise):
+        im = Image.fromarray(np.ascontiguousarray(chw.transpose(1, 2, 0)), "RGB")
+        enhancers = {sa.OP_BRIGHTNESS: (ImageEnhance.Brightness, d["brightness"]), sa.OP_CONTRAST: (ImageEnhance.Contrast, d["contrast"]),
+                     sa.OP_SATURATION: (ImageEnhance.Color, d["saturation"])}
+        for op, _ in sa.jitter_chain(d):
+            if op == sa.OP_HUE:
+                hh, s, v = im.convert("HSV").split()
+                np_h = np.array(hh, dtype=np.uint8)
+                with np.errstate(over="ignore"):
+                    np_h += np.uint8(sa.hue_shift(d["hue"]))
+                im = Image.merge("HSV", (Image.fromarray(np_h, "L"), s, v)).convert("RGB")
+            else:
+                im = enhancers[op][0](im).enhance(enhancers[op][1])
+        if d["gray"]:
+            l = np.asarray(im.convert("L"))
+            im = Image.fromarray(np.dstack([l, l, l]), "RGB")
+        if d["blur"]:
+            im = im.filter(ImageFilter.GaussianBlur(radius=d["sigma"]))
+        out = np.asarray(im)
+        if any(e is not None for e in d["erase"]):
+            t = torch.from_numpy(np.ascontiguousarray(out.transpose(2, 0, 1))).float().div(255)
+            at = 0
+            for e in d["erase"]:
+                if e is not None:
+                    i, j, eh, ew = e
+                    t[:, i:i + eh, j:j + ew] = noise[at:at + 3 * eh * ew].view(3, eh, ew)
+                    at += 3 * eh * ew
+            return t.mul(255).byte()
+        return torch.as_tensor(np.ascontiguousarray(out.transpose(2, 0, 1)))
+
+    for name, keys in STRONG_GROUPS.items():
+        cfg = locov_amd.config.get_cfg()
+        cfg.MODEL.DEVICE = str(dev)
+        plain = data.DatasetMapper(cfg, True, device=dev, seed=1)
+        for k, v in keys.items():
+            cfg.INPUT[k] = v
+        aug = sa.build_complete_augmentation(cfg, True)
+        aug.JITTER_P = aug.BLUR_P = 1.0
+        for eraser in aug.erasers:
+            eraser.p = 1.0
+        mapper = data.DatasetMapper(cfg, True, device=dev, seed=1, train_aug=aug)
+        for N in args.images:
+            rng = np.random.default_rng(N)
+            dicts = [{"image_raw": rng.integers(0, 256, (h, w, 3), dtype=np.uint8)} for _ in range(N)]
+            sample = mapper.draw_sample(dicts)
+            noise = mapper.erase_noise(sample)
+            sample["erase_noise"] = noise
+            base = {k: sample[k] for k in ("short_edge", "flip", "caption")}
+            resized = [d["image"] for d in plain.map_batch(dicts, base)]
+            counts = [sa.noise_count(s) for s in sample["strong"]]
+            offsets = [int(o) for o in np.concatenate([[0], np.cumsum(counts)[:-1]])]
+
+            def side(fused, m=mapper, s=sample):
+                def step():
+                    os.environ["LOCOV_FUSED_AUGMENT"] = fused
+                    return m.map_batch(dicts, s)
+                return step
+
+            got = side("1")()
+            for a, b in zip(got, side("0")()):
+                assert torch.equal(a["image"], b["image"]), "the device path and the definition differ"
+            r = {"output": list(resized[0].shape[1:]), "sigma": [round(s["sigma"], 3) for s in sample["strong"]][:8],
+                 "erased_pixels": sum(counts) // 3,
+                 "map_batch": {"device": wall(side("1"), args.iters, args.warmup), "resize_only": wall(lambda: plain.map_batch(dicts, base), args.iters, args.warmup),
+                               "host": wall(side("0"), args.host_iters, 1)}}
+            os.environ.pop("LOCOV_FUSED_AUGMENT", None)
+            launch = lambda: ops.augment_images(resized, sample["strong"], noise, offsets)
+            k = kernels(launch, top=3)
+            pixels = sum(int(x.shape[1] * x.shape[2]) for x in resized)
+            contrast = sum(int(x.shape[1] * x.shape[2]) for x, s in zip(resized, sample["strong"]) if s["jitter"])
+            nbytes = 3 * (2 * pixels + contrast) + 4 * sum(counts)
+            r["launches"] = dict(alternate({"call": launch}, args.iters, args.warmup)["call"], device=k, bytes=nbytes,
+                                 tbs=nbytes / (k["total_us"] * 1e-6) / 1e12, bound_us=nbytes / (args.copy_tbs * 1e12) * 1e6)
+            if Image is not None:
+                host_images = [x.cpu().numpy() for x in resized]
+                host_noise = noise.cpu()
+                jobs = [(x, s, host_noise[o:o + c]) for x, s, o, c in zip(host_images, sample["strong"], offsets, counts)]
+                for a, j in zip(got, jobs):
+                    assert torch.equal(a["image"].cpu(), pillow_one(*j)), "the device path and Pillow differ"
+                r["pillow"] = {"1_thread": wall(lambda: [pillow_one(*j).to(dev) for j in jobs], args.host_iters, 1),
+                               f"{args.threads}_threads": wall(lambda: [y.to(dev) for y in pool.map(lambda j: pillow_one(*j), jobs)],
+                                                               args.host_iters, 1)}
+            rec["runs"][f"{name}_images_{N}"] = r
+            print(json.dumps({f"strong {name} images {N}": r}), flush=True)
+    return rec
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--strong", action="store_true", help="time the strong augmentation of the mapper instead (see strong())")
     ap.add_argument("--proposals", type=int, default=0, help="rows per image: time the proposal side of the mapper instead (see proposals())")
     ap.add_argument("--images", type=int, nargs="+", default=[1, 8])
     ap.add_argument("--iters", type=int, default=50)
@@ -119,10 +234,10 @@ def main(argv=None):
         raise SystemExit("time_data: needs a ROCm GPU")
     if args.iters < 50 or args.warmup < 10:
         raise SystemExit("time_data: the protocol asks for >= 10 warm-up and >= 50 timed iterations")
-    if args.proposals > 0:
+    if args.proposals > 0 or args.strong:
         dev = torch.device("cuda:0")
         torch.cuda.set_device(dev)
-        rec = proposals(args, dev)
+        rec = strong(args, dev) if args.strong else proposals(args, dev)
         if args.out:
             os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
             with open(args.out, "w") as f:
