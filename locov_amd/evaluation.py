@@ -28,9 +28,11 @@ The protocol, as every path below computes it (float64 and integers only, so the
     per-category AP50 x 100 over `seen_names` / `unseen_names` (the reference imports those lists from a file it does not ship;
     nan for an empty list).
 
-Paths: the numpy functions of this file are the definition; they serve CPU tensors, LOCOV_FUSED_COCOEVAL=0 (A/B runs, like
-LOCOV_FUSED_ATTENTION) and sizes beyond the kernels' limits.  Device tensors take ops.coco_order / coco_match / coco_accumulate
-(csrc/coco_eval.hip) with one device-to-host copy, of the result arrays.  The evaluator scores what its own process saw.
+Paths (one for both protocols; what LVIS switches is stated under its rules below): the numpy functions of this file are the
+definition; they serve CPU tensors, LOCOV_FUSED_COCOEVAL=0 (A/B runs, like LOCOV_FUSED_ATTENTION) and sizes beyond the kernels'
+limits.  Device tensors take _evaluate_device: ops.coco_order / coco_match / coco_accumulate (csrc/coco_eval.hip) with one
+device-to-host copy, of the result arrays.  COCOEvaluator.evaluate() chooses between the two; a protocol is three hooks of the
+evaluator (its host function, its device function, its derive_results).  The evaluator scores what its own process saw.
 
 LVIS-protocol box AP with APr / APc / APf (the public lvis-api's LVISEval and LVISResults, and Detectron2's LVISEvaluator, which
 the reference's select_and_build_evaluator returns for every dataset whose name contains "lvis": ovr/evaluation/evaluator.py:39-50),
@@ -62,10 +64,13 @@ integers again:
   * Stated differences (COCO's too): a gt with id 0 counts as a match like any other (LVISEval reads a stored id 0 as
     "unmatched"); an image id absent from the ground truth raises in process().
 
-Paths: the *_lvis numpy functions are the definition and drop the unlisted dets literally.  Device tensors take ops.lvis_limit
-(the cap: two stable integer-key sorts and the in-image position; a det past the cap goes to the trailing cell), ops.coco_order,
-ops.lvis_match (the COCO match kernel's other instantiation, which writes the dets of an unlisted cell as ignored: the accumulation
-passes over an ignored det, so precision and recall do not move) and ops.coco_accumulate without scores, then the one copy.
+Paths: the same two, switched as the kernel's template parameter is.  On the host _match_host is the one matching loop; under LVIS
+it takes the gt's `ignore` as the flag of the ignore test, an all-false crowd (so no crowd union and no second taking of a matched
+gt) and the cells' flags; evaluate_host_lvis drops the unlisted dets literally before it.  On the device _evaluate_device first
+runs ops.lvis_limit (the cap: two stable integer-key sorts and the in-image position; a det past the cap goes to the trailing
+cell), calls ops.lvis_match in place of ops.coco_match (the match kernel's other instantiation, which writes the dets of an unlisted
+cell as ignored: the accumulation passes over an ignored det, so precision and recall do not move) and ops.coco_accumulate without
+scores, and summarises precision [T, R, K, A] with the thirteen stats.
 """
 from __future__ import annotations
 
@@ -108,22 +113,27 @@ class _GroundTruth:
         anns = [a for a in gt.get("annotations", ()) if a["image_id"] in self.image_rank and a["category_id"] in cat_rank]
         cell = np.array([cat_rank[a["category_id"]] * I + self.image_rank[a["image_id"]] for a in anns], dtype=np.int64)
         order = np.argsort(cell, kind="stable")
+        anns, cell = [anns[i] for i in order], cell[order]
         self.n_images, self.n_categories, self.n_cells = I, K, I * K
-        self.box = np.array([anns[i]["bbox"] for i in order], dtype=np.float64).reshape(-1, 4)
-        self.area = np.array([anns[i]["area"] for i in order], dtype=np.float64)
-        self.crowd = np.array([1 if anns[i].get("iscrowd", 0) else 0 for i in order], dtype=np.uint8)
-        cell = cell[order]
+        self.box = np.array([a["bbox"] for a in anns], dtype=np.float64).reshape(-1, 4)
+        self.area = np.array([a["area"] for a in anns], dtype=np.float64)
+        self.crowd = np.array([1 if a.get("iscrowd", 0) else 0 for a in anns], dtype=np.uint8)
         self.offsets = np.searchsorted(cell, np.arange(I * K + 1, dtype=np.int64), side="left").astype(np.int32)
         self.cat_offsets = self.offsets[::I].astype(np.int64) if I else np.zeros(K + 1, dtype=np.int64)   # [K + 1]
+        self._read_more(gt, cats, cat_rank, anns)
         self._device = {}
+
+    _uploaded = ("box", "area", "crowd", "offsets", "cat_offsets")                             # what on() copies to the device
+
+    def _read_more(self, gt, cats, cat_rank, anns):
+        """What a protocol reads beyond the arrays above, from the loaded dict, its categories in ascending id, their ranks and the
+        annotations in cell order (_LVISGroundTruth's fields)."""
 
     def on(self, device):
         """The device copies of the arrays, made once per device."""
         d = self._device.get(device)
         if d is None:
-            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
-            d = self._device[device] = dict(box=up(self.box), area=up(self.area), crowd=up(self.crowd), offsets=up(self.offsets),
-                                            cat_offsets=up(self.cat_offsets))
+            d = self._device[device] = {k: torch.from_numpy(np.ascontiguousarray(getattr(self, k))).to(device) for k in self._uploaded}
         return d
 
 
@@ -148,8 +158,11 @@ def order_host(img_rank, cls, score, n_images, n_categories):
     return perm, det_offsets, rank, acc_index, cat_offsets
 
 
-def match_host(gt: _GroundTruth, det_offsets, boxes, max_det, area_rng=AREA_RNG, iou_thrs=IOU_THRS):
-    """boxes: fp32 XYXY in cell order.  -> det_bits uint8 [N, A * T] (bit 0 matched, bit 1 ignored), gt_ignore uint8 [A, G]."""
+def _match_host(gt: _GroundTruth, flag, flag_is_crowd, cell_flags, det_offsets, boxes, max_det, area_rng, iou_thrs):
+    """The matching of both protocols, with the switches csrc/coco_eval.hip's header lists.  flag uint8 [G]: the gt's own ignore
+    flag (iscrowd, or LVIS's ignore).  flag_is_crowd: the flag also selects the crowd union and lets a matched gt be taken again.
+    cell_flags uint8 [C] or None: the federated lists; None: every det is listed and no cell is not-exhaustive.
+    -> det_bits uint8 [N, A * T] (bit 0 matched, bit 1 ignored), gt_ignore uint8 [A, G], listed bool [N]."""
     A, T = len(area_rng), len(iou_thrs)
     lo, hi = area_rng[:, 0], area_rng[:, 1]
     boxes = np.asarray(boxes, dtype=np.float32).reshape(-1, 4)
@@ -157,19 +170,27 @@ def match_host(gt: _GroundTruth, det_offsets, boxes, max_det, area_rng=AREA_RNG,
     dh = (boxes[:, 3] - boxes[:, 1]).astype(np.float64)
     dx, dy = boxes[:, 0].astype(np.float64), boxes[:, 1].astype(np.float64)
     darea = dw * dh
-    gt_ignore = ((gt.crowd[None, :] != 0) | (gt.area[None, :] < lo[:, None]) | (gt.area[None, :] > hi[:, None]))
-    det_out = (darea[:, None] < lo[None, :]) | (darea[:, None] > hi[None, :])                 # [N, A]
-    bits = np.repeat(det_out.astype(np.uint8) * 2, T, axis=1)                                 # an unmatched det: ignored by its area
+    gt_ignore = ((flag[None, :] != 0) | (gt.area[None, :] < lo[:, None]) | (gt.area[None, :] > hi[:, None]))
+    all_crowd = flag != 0 if flag_is_crowd else np.zeros(len(flag), dtype=bool)
     counts = np.diff(det_offsets.astype(np.int64))
+    gcount = np.diff(gt.offsets.astype(np.int64))
     n_listed = int(det_offsets[-1])                                                            # (the rest: classes outside the bank)
     in_cell = np.arange(n_listed, dtype=np.int64) - np.repeat(det_offsets[:-1].astype(np.int64), counts)
+    listed, nel = np.ones(len(boxes), dtype=bool), np.zeros(len(boxes), dtype=bool)
+    if cell_flags is not None:
+        cell_of = np.repeat(np.arange(len(counts), dtype=np.int64), counts)
+        listed[:n_listed] = (gcount[cell_of] > 0) | ((cell_flags[cell_of] & _lib.LVIS_CELL_NEG) != 0)
+        listed[n_listed:] = False
+        nel[:n_listed] = (cell_flags[cell_of] & _lib.LVIS_CELL_NOT_EXHAUSTIVE) != 0
+    det_out = (darea[:, None] < lo[None, :]) | (darea[:, None] > hi[None, :]) | nel[:, None]   # [N, A]: an unmatched det is ignored
+    bits = np.repeat(det_out.astype(np.uint8) * 2, T, axis=1)
+    bits[~listed] = 0                                                                          # unlisted: no part, bits 0
     bits[:n_listed][in_cell >= max_det] = 0                                                    # past the cap: no part, bits 0
     start = np.minimum(iou_thrs, 1 - 1e-10)
-    gcount = np.diff(gt.offsets.astype(np.int64))
     for c in np.nonzero((counts > 0) & (gcount > 0))[0]:
         d0, g0, G = int(det_offsets[c]), int(gt.offsets[c]), int(gcount[c])
         D = min(int(counts[c]), max_det)
-        gb, crowd = gt.box[g0:g0 + G], gt.crowd[g0:g0 + G] != 0
+        gb, crowd = gt.box[g0:g0 + G], all_crowd[g0:g0 + G]
         sl = slice(d0, d0 + D)
         w = np.minimum((dx[sl] + dw[sl])[:, None], (gb[:, 0] + gb[:, 2])[None, :]) - np.maximum(dx[sl][:, None], gb[None, :, 0])
         h = np.minimum((dy[sl] + dh[sl])[:, None], (gb[:, 1] + gb[:, 3])[None, :]) - np.maximum(dy[sl][:, None], gb[None, :, 1])
@@ -189,21 +210,33 @@ def match_host(gt: _GroundTruth, det_offsets, boxes, max_det, area_rng=AREA_RNG,
                 best[ok] = iou[d, g]
                 m[ok] = g
             second = m < 0
-            for g in range(G):                                                                 # nothing there: the ignored gts
-                ok = second & gig[:, g, None] & ~(gtm[:, :, g] & ~crowd[g]) & (iou[d, g] >= best)
+            for g in range(G):                                                                 # nothing there: the ignored gts (a
+                ok = second & gig[:, g, None] & ~(gtm[:, :, g] & ~crowd[g]) & (iou[d, g] >= best)   # crowd one again and again)
                 best[ok] = iou[d, g]
                 m[ok] = g
             matched = m >= 0
             gtm[ai[matched], ti[matched], m[matched]] = True
             ign = np.where(matched, second, det_out[d0 + d][:, None])
             bits[d0 + d] = (matched.astype(np.uint8) | (ign.astype(np.uint8) << 1)).reshape(-1)
-    return bits, gt_ignore.astype(np.uint8)
+    return bits, gt_ignore.astype(np.uint8), listed
+
+
+def match_host(gt: _GroundTruth, det_offsets, boxes, max_det, area_rng=AREA_RNG, iou_thrs=IOU_THRS):
+    """boxes: fp32 XYXY in cell order.  -> det_bits uint8 [N, A * T] (bit 0 matched, bit 1 ignored), gt_ignore uint8 [A, G]."""
+    return _match_host(gt, gt.crowd, True, None, det_offsets, boxes, max_det, area_rng, iou_thrs)[:2]
 
 
 def npig_host(gt: _GroundTruth, gt_ignore):
     """int32 [K, A]: the category's gts that are not ignored in the range."""
     c = np.concatenate([np.zeros((gt_ignore.shape[0], 1), dtype=np.int64), np.cumsum(gt_ignore == 0, axis=1)], axis=1)
     return (c[:, gt.cat_offsets[1:]] - c[:, gt.cat_offsets[:-1]]).T.astype(np.int32)
+
+
+def npig_device(cat_offsets: torch.Tensor, gt_ignore: torch.Tensor) -> torch.Tensor:
+    """npig_host on device tensors (cat_offsets: _GroundTruth.on()'s int64 [K + 1]), without a host read."""
+    c = torch.cat([torch.zeros((gt_ignore.shape[0], 1), dtype=torch.int64, device=gt_ignore.device), torch.cumsum(gt_ignore == 0, dim=1)],
+                  dim=1)
+    return (c[:, cat_offsets[1:]] - c[:, cat_offsets[:-1]]).t().contiguous().to(torch.int32)
 
 
 def accumulate_host(cat_offsets, acc_index, acc_rank, acc_score, det_bits, npig, max_dets, n_thresholds, rec_thrs=REC_THRS):
@@ -242,24 +275,25 @@ def accumulate_host(cat_offsets, acc_index, acc_rank, acc_score, det_bits, npig,
     return precision, recall, scores
 
 
+def _mean(s):
+    """The mean over the entries > -1, -1 with none."""
+    s = s[s > -1]
+    return -1.0 if s.size == 0 else float(np.mean(s))
+
+
 def summarize(precision, recall):
     """COCOeval.summarize's twelve numbers.  AP and the area ARs use the last cap; a cap that is not configured gives -1."""
     M = precision.shape[-1]
-
-    def mean(s):
-        s = s[s > -1]
-        return -1.0 if s.size == 0 else float(np.mean(s))
-
     stats = np.full(12, -1.0)
-    stats[0] = mean(precision[:, :, :, 0, M - 1])
-    stats[1] = mean(precision[0, :, :, 0, M - 1])
+    stats[0] = _mean(precision[:, :, :, 0, M - 1])
+    stats[1] = _mean(precision[0, :, :, 0, M - 1])
     if precision.shape[0] > 5:
-        stats[2] = mean(precision[5, :, :, 0, M - 1])
+        stats[2] = _mean(precision[5, :, :, 0, M - 1])
     for i in range(1, min(4, precision.shape[3])):
-        stats[2 + i] = mean(precision[:, :, :, i, M - 1])
-        stats[8 + i] = mean(recall[:, :, i, M - 1])
+        stats[2 + i] = _mean(precision[:, :, :, i, M - 1])
+        stats[8 + i] = _mean(recall[:, :, i, M - 1])
     for m in range(M):
-        stats[6 + m] = mean(recall[:, :, 0, m])
+        stats[6 + m] = _mean(recall[:, :, 0, m])
     return stats
 
 
@@ -313,22 +347,47 @@ def device_supported(gt: _GroundTruth, n_det: int, max_dets) -> bool:
             and n_det < 2 ** 31 - 1 and len(gt.area) < 2 ** 31 - 1 and gt.n_cells > 0)
 
 
-def evaluate_device(gt: _GroundTruth, img_rank, cls, score, boxes, max_dets):
-    """The same on device tensors: orderings by stable integer sorts, two kernel launches, one copy to the host."""
+def _evaluate_device(gt: _GroundTruth, img_rank, cls, score, boxes, max_dets, lvis, mark=None):
+    """The device path of both protocols; `lvis` switches the cap step, the match wrapper, the scores and the result's shape.
+    mark: called with each step's name after the step (tools/time_evaluation.py synchronises there); None: nothing extra."""
     from . import ops
+    step = mark if mark is not None else (lambda name: None)
     g = gt.on(boxes.device)
     K, A, T, R, M = gt.n_categories, len(AREA_RNG), len(IOU_THRS), len(REC_THRS), len(max_dets)
+    if lvis:
+        cls = ops.lvis_limit(img_rank, cls, score, gt.n_images, K, max_dets[-1])
+        step("cap")
     o = ops.coco_order(img_rank, cls, score, boxes, gt.n_images, K)
-    bits, gt_ignore = ops.coco_match(o.det_offsets, g["offsets"], o.boxes, g["box"], g["area"], g["crowd"], AREA_RNG, IOU_THRS,
-                                     max_dets[-1])
-    c = torch.cat([torch.zeros((A, 1), dtype=torch.int64, device=boxes.device), torch.cumsum(gt_ignore == 0, dim=1)], dim=1)
-    npig = (c[:, g["cat_offsets"][1:]] - c[:, g["cat_offsets"][:-1]]).t().contiguous().to(torch.int32)
-    flat = ops.coco_accumulate(o.cat_offsets, o.acc_index, o.acc_rank, o.acc_score, bits, npig, T, max_dets, REC_THRS)
+    step("orderings")
+    if lvis:
+        bits, gt_ignore = ops.lvis_match(o.det_offsets, g["offsets"], g["cell_flags"], o.boxes, g["box"], g["area"], g["ignore"], AREA_RNG,
+                                         IOU_THRS, max_dets[-1])
+    else:
+        bits, gt_ignore = ops.coco_match(o.det_offsets, g["offsets"], o.boxes, g["box"], g["area"], g["crowd"], AREA_RNG, IOU_THRS,
+                                         max_dets[-1])
+    step("match")
+    npig = npig_device(g["cat_offsets"], gt_ignore)
+    step("npig")
+    flat = ops.coco_accumulate(o.cat_offsets, o.acc_index, o.acc_rank, o.acc_score, bits, npig, T, max_dets, REC_THRS, with_scores=not lvis)
+    step("accumulate")
     host = flat.cpu().numpy()                                                  # the one device-to-host copy
     n = T * R * K * A * M
-    precision, scores = host[:n].reshape(T, R, K, A, M), host[n:2 * n].reshape(T, R, K, A, M)
-    recall = host[2 * n:].reshape(T, K, A, M)
-    return dict(precision=precision, recall=recall, scores=scores, stats=summarize(precision, recall))
+    if lvis:
+        step("copy")
+        precision, recall = host[:n].reshape(T, R, K, A), host[n:].reshape(T, K, A)
+        ev = dict(precision=precision, recall=recall, stats=summarize_lvis(precision, recall, gt.freq_groups))
+        step("means")
+    else:
+        precision, scores = host[:n].reshape(T, R, K, A, M), host[n:2 * n].reshape(T, R, K, A, M)
+        recall = host[2 * n:].reshape(T, K, A, M)
+        ev = dict(precision=precision, recall=recall, scores=scores, stats=summarize(precision, recall))
+        step("copy_and_means")
+    return ev
+
+
+def evaluate_device(gt: _GroundTruth, img_rank, cls, score, boxes, max_dets, mark=None):
+    """The same on device tensors: orderings by stable integer sorts, two kernel launches, one copy to the host."""
+    return _evaluate_device(gt, img_rank, cls, score, boxes, max_dets, False, mark)
 
 
 class COCOEvaluator:
@@ -386,19 +445,26 @@ class COCOEvaluator:
         img_rank = torch.from_numpy(np.repeat(np.asarray(self._ranks, dtype=np.int64), self._counts)).to(device)
         return img_rank, cls, score, boxes
 
+    # the three places where a protocol differs; LVISEvaluator overrides them
+    def _evaluate_host(self, img_rank, cls, score, boxes):
+        return evaluate_host(self._gt, img_rank, cls, score, boxes, self.max_dets)
+
+    def _evaluate_device(self, img_rank, cls, score, boxes, mark=None):
+        return evaluate_device(self._gt, img_rank, cls, score, boxes, self.max_dets, mark)
+
+    def _derive_results(self, ev):
+        return derive_results(ev, self._class_names, self._seen, self._unseen)
+
     def evaluate(self):
         n = sum(self._counts)
         if n == 0:
             self.eval = None
-            return OrderedDict(bbox=derive_results(None, self._class_names))
+            return OrderedDict(bbox=self._derive_results(None))
         device = self._device or self._boxes[0].device
         on_device = device.type == "cuda" and _fused() and device_supported(self._gt, n, self.max_dets)
-        img_rank, cls, score, boxes = self._gathered(device if on_device else torch.device("cpu"))
-        if on_device:
-            self.eval = evaluate_device(self._gt, img_rank, cls, score, boxes, self.max_dets)
-        else:
-            self.eval = evaluate_host(self._gt, img_rank.numpy(), cls.numpy(), score.numpy(), boxes.numpy(), self.max_dets)
-        return OrderedDict(bbox=derive_results(self.eval, self._class_names, self._seen, self._unseen))
+        tensors = self._gathered(device if on_device else torch.device("cpu"))
+        self.eval = self._evaluate_device(*tensors) if on_device else self._evaluate_host(*(t.numpy() for t in tensors))
+        return OrderedDict(bbox=self._derive_results(self.eval))
 
 
 def inference_on_dataset(model, data_loader, evaluator):
@@ -426,32 +492,18 @@ class _LVISGroundTruth(_GroundTruth):
     """_GroundTruth plus what the federated protocol reads: each gt's `ignore` field (cell order), a byte per cell with the image's
     neg / not-exhaustive lists, and the frequency groups as arrays of category ranks.  `crowd` is kept but never read."""
 
-    def __init__(self, gt):
-        if isinstance(gt, (str, os.PathLike)):
-            with open(gt) as f:
-                gt = json.load(f)
-        super().__init__(gt)
+    _uploaded = _GroundTruth._uploaded + ("ignore", "cell_flags")
+
+    def _read_more(self, gt, cats, cat_rank, anns):
         I, K = self.n_images, self.n_categories
-        cat_rank = {cid: r for r, cid in enumerate(self.cat_ids)}
-        anns = [a for a in gt.get("annotations", ()) if a["image_id"] in self.image_rank and a["category_id"] in cat_rank]
-        cell = np.array([cat_rank[a["category_id"]] * I + self.image_rank[a["image_id"]] for a in anns], dtype=np.int64)
-        order = np.argsort(cell, kind="stable")                                               # (the parent's order)
-        self.ignore = np.array([1 if anns[i].get("ignore", 0) else 0 for i in order], dtype=np.uint8)
+        self.ignore = np.array([1 if a.get("ignore", 0) else 0 for a in anns], dtype=np.uint8)
         self.cell_flags = np.zeros(I * K, dtype=np.uint8)
         for field, bit in (("neg_category_ids", _lib.LVIS_CELL_NEG), ("not_exhaustive_category_ids", _lib.LVIS_CELL_NOT_EXHAUSTIVE)):
             cells = np.array([cat_rank[c] * I + self.image_rank[im["id"]] for im in gt["images"] for c in im.get(field, ())
                               if c in cat_rank], dtype=np.int64)
             self.cell_flags[cells] |= np.uint8(bit)                                            # (a scatter of one constant)
-        freq = [c.get("frequency") for c in sorted(gt["categories"], key=lambda c: c["id"])]
+        freq = [c.get("frequency") for c in cats]
         self.freq_groups = [np.array([r for r, f in enumerate(freq) if f == name], dtype=np.int64) for name in LVIS_FREQUENCIES]
-
-    def on(self, device):
-        d = self._device.get(device)
-        if d is None:
-            d = super().on(device)
-            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
-            d.update(ignore=up(self.ignore), cell_flags=up(self.cell_flags))
-        return d
 
 
 def limit_host(img_rank, cls, score, n_categories, max_dets_per_image):
@@ -476,78 +528,22 @@ def listed_host(gt: _LVISGroundTruth, img_rank, cls):
 def match_host_lvis(gt: _LVISGroundTruth, det_offsets, boxes, max_det, area_rng=AREA_RNG, iou_thrs=IOU_THRS):
     """match_host under the LVIS rules.  boxes: fp32 XYXY in cell order.  -> det_bits uint8 [N, A * T], gt_ignore uint8 [A, G],
     listed bool [N]: False for the dets of unlisted cells (and of the trailing cell), which take no part; their bits are 0."""
-    A, T = len(area_rng), len(iou_thrs)
-    lo, hi = area_rng[:, 0], area_rng[:, 1]
-    boxes = np.asarray(boxes, dtype=np.float32).reshape(-1, 4)
-    dw = (boxes[:, 2] - boxes[:, 0]).astype(np.float64)
-    dh = (boxes[:, 3] - boxes[:, 1]).astype(np.float64)
-    dx, dy = boxes[:, 0].astype(np.float64), boxes[:, 1].astype(np.float64)
-    darea = dw * dh
-    gt_ignore = ((gt.ignore[None, :] != 0) | (gt.area[None, :] < lo[:, None]) | (gt.area[None, :] > hi[:, None]))
-    counts = np.diff(det_offsets.astype(np.int64))
-    gcount = np.diff(gt.offsets.astype(np.int64))
-    n_listed = int(det_offsets[-1])
-    cell_of = np.repeat(np.arange(len(counts), dtype=np.int64), counts)
-    in_cell = np.arange(n_listed, dtype=np.int64) - np.repeat(det_offsets[:-1].astype(np.int64), counts)
-    listed = np.zeros(len(boxes), dtype=bool)
-    listed[:n_listed] = (gcount[cell_of] > 0) | ((gt.cell_flags[cell_of] & _lib.LVIS_CELL_NEG) != 0)
-    nel = np.zeros(len(boxes), dtype=bool)
-    nel[:n_listed] = (gt.cell_flags[cell_of] & _lib.LVIS_CELL_NOT_EXHAUSTIVE) != 0
-    det_out = (darea[:, None] < lo[None, :]) | (darea[:, None] > hi[None, :]) | nel[:, None]   # an unmatched det: ignored by these
-    bits = np.repeat(det_out.astype(np.uint8) * 2, T, axis=1)
-    bits[~listed] = 0
-    bits[:n_listed][in_cell >= max_det] = 0
-    start = np.minimum(iou_thrs, 1 - 1e-10)
-    for c in np.nonzero((counts > 0) & (gcount > 0))[0]:
-        d0, g0, G = int(det_offsets[c]), int(gt.offsets[c]), int(gcount[c])
-        D = min(int(counts[c]), max_det)
-        gb = gt.box[g0:g0 + G]
-        sl = slice(d0, d0 + D)
-        w = np.minimum((dx[sl] + dw[sl])[:, None], (gb[:, 0] + gb[:, 2])[None, :]) - np.maximum(dx[sl][:, None], gb[None, :, 0])
-        h = np.minimum((dy[sl] + dh[sl])[:, None], (gb[:, 1] + gb[:, 3])[None, :]) - np.maximum(dy[sl][:, None], gb[None, :, 1])
-        inter = w * h
-        union = darea[sl][:, None] + (gb[:, 2] * gb[:, 3])[None, :] - inter
-        with np.errstate(divide="ignore", invalid="ignore"):
-            iou = np.where((w > 0) & (h > 0), inter / union, 0.0)
-        gig = gt_ignore[:, g0:g0 + G]
-        gtm = np.zeros((A, T, G), dtype=bool)
-        ai, ti = np.meshgrid(np.arange(A), np.arange(T), indexing="ij")
-        for d in range(D):
-            best = np.broadcast_to(start[None, :], (A, T)).copy()
-            m = np.full((A, T), -1, dtype=np.int64)
-            for g in range(G):                                                                 # the gts not ignored in the range
-                ok = ~gig[:, g, None] & ~gtm[:, :, g] & (iou[d, g] >= best)
-                best[ok] = iou[d, g]
-                m[ok] = g
-            second = m < 0
-            for g in range(G):                                                                 # nothing there: the ignored, once each
-                ok = second & gig[:, g, None] & ~gtm[:, :, g] & (iou[d, g] >= best)
-                best[ok] = iou[d, g]
-                m[ok] = g
-            matched = m >= 0
-            gtm[ai[matched], ti[matched], m[matched]] = True
-            ign = np.where(matched, second, det_out[d0 + d][:, None])
-            bits[d0 + d] = (matched.astype(np.uint8) | (ign.astype(np.uint8) << 1)).reshape(-1)
-    return bits, gt_ignore.astype(np.uint8), listed
+    return _match_host(gt, gt.ignore, False, gt.cell_flags, det_offsets, boxes, max_det, area_rng, iou_thrs)
 
 
 def summarize_lvis(precision, recall, freq_groups):
     """LVISEval._summarize's thirteen numbers on precision [T, R, K, A] and recall [T, K, A]: AP, AP50, AP75, APs, APm, APl, APr,
     APc, APf, AR@cap, ARs, ARm, ARl."""
-    def mean(s):
-        s = s[s > -1]
-        return -1.0 if s.size == 0 else float(np.mean(s))
-
     stats = np.full(13, -1.0)
-    stats[0] = mean(precision[:, :, :, 0])
-    stats[1] = mean(precision[0, :, :, 0])
-    stats[2] = mean(precision[5, :, :, 0])
+    stats[0] = _mean(precision[:, :, :, 0])
+    stats[1] = _mean(precision[0, :, :, 0])
+    stats[2] = _mean(precision[5, :, :, 0])
     for i in range(1, 4):
-        stats[2 + i] = mean(precision[:, :, :, i])
-        stats[9 + i] = mean(recall[:, :, i])
+        stats[2 + i] = _mean(precision[:, :, :, i])
+        stats[9 + i] = _mean(recall[:, :, i])
     for i, group in enumerate(freq_groups):
-        stats[6 + i] = mean(precision[:, :, group, 0])
-    stats[9] = mean(recall[:, :, 0])
+        stats[6 + i] = _mean(precision[:, :, group, 0])
+    stats[9] = _mean(recall[:, :, 0])
     return stats
 
 
@@ -574,24 +570,10 @@ def evaluate_host_lvis(gt: _LVISGroundTruth, img_rank, cls, score, boxes, max_de
     return dict(precision=precision, recall=recall, stats=summarize_lvis(precision, recall, gt.freq_groups))
 
 
-def evaluate_device_lvis(gt: _LVISGroundTruth, img_rank, cls, score, boxes, max_dets_per_image):
+def evaluate_device_lvis(gt: _LVISGroundTruth, img_rank, cls, score, boxes, max_dets_per_image, mark=None):
     """The same on device tensors: the cap and the orderings by stable integer sorts, two launches, one copy to the host.  The
     unlisted dets stay in their cells; locov_lvis_match marks them ignored, which leaves precision and recall unchanged."""
-    from . import ops
-    g = gt.on(boxes.device)
-    K, A, T, R = gt.n_categories, len(AREA_RNG), len(IOU_THRS), len(REC_THRS)
-    cls = ops.lvis_limit(img_rank, cls, score, gt.n_images, K, max_dets_per_image)
-    o = ops.coco_order(img_rank, cls, score, boxes, gt.n_images, K)
-    bits, gt_ignore = ops.lvis_match(o.det_offsets, g["offsets"], g["cell_flags"], o.boxes, g["box"], g["area"], g["ignore"], AREA_RNG,
-                                     IOU_THRS, max_dets_per_image)
-    c = torch.cat([torch.zeros((A, 1), dtype=torch.int64, device=boxes.device), torch.cumsum(gt_ignore == 0, dim=1)], dim=1)
-    npig = (c[:, g["cat_offsets"][1:]] - c[:, g["cat_offsets"][:-1]]).t().contiguous().to(torch.int32)
-    flat = ops.coco_accumulate(o.cat_offsets, o.acc_index, o.acc_rank, o.acc_score, bits, npig, T, (max_dets_per_image,), REC_THRS,
-                               with_scores=False)
-    host = flat.cpu().numpy()                                                  # the one device-to-host copy
-    n = T * R * K * A
-    precision, recall = host[:n].reshape(T, R, K, A), host[n:].reshape(T, K, A)
-    return dict(precision=precision, recall=recall, stats=summarize_lvis(precision, recall, gt.freq_groups))
+    return _evaluate_device(gt, img_rank, cls, score, boxes, (max_dets_per_image,), True, mark)
 
 
 class LVISEvaluator(COCOEvaluator):
@@ -601,7 +583,7 @@ class LVISEvaluator(COCOEvaluator):
     gt: an LVIS-format dict or the path of its JSON (images with neg_category_ids / not_exhaustive_category_ids, annotations,
     categories with frequency).  class_names: one name per category in ascending category id (checked for length; LVIS reports no
     per-category rows).  max_dets_per_image: the cap over all categories of an image.  device: where evaluate() runs.
-    process() and reset() are COCOEvaluator's; .eval holds {"precision" [T, R, K, A], "recall" [T, K, A], "stats" [13]}."""
+    process(), reset() and evaluate() are COCOEvaluator's; .eval holds {"precision" [T, R, K, A], "recall" [T, K, A], "stats" [13]}."""
 
     def __init__(self, gt, class_names: Optional[Sequence[str]] = None, max_dets_per_image: int = 300, device=None):
         if int(max_dets_per_image) != max_dets_per_image or max_dets_per_image < 1:
@@ -610,19 +592,14 @@ class LVISEvaluator(COCOEvaluator):
                          max_dets=(int(max_dets_per_image),), device=device)
         self.max_dets_per_image = int(max_dets_per_image)
 
-    def evaluate(self):
-        n = sum(self._counts)
-        if n == 0:
-            self.eval = None
-            return OrderedDict(bbox=derive_results_lvis(None))
-        device = self._device or self._boxes[0].device
-        on_device = device.type == "cuda" and _fused() and device_supported(self._gt, n, self.max_dets)
-        img_rank, cls, score, boxes = self._gathered(device if on_device else torch.device("cpu"))
-        if on_device:
-            self.eval = evaluate_device_lvis(self._gt, img_rank, cls, score, boxes, self.max_dets_per_image)
-        else:
-            self.eval = evaluate_host_lvis(self._gt, img_rank.numpy(), cls.numpy(), score.numpy(), boxes.numpy(), self.max_dets_per_image)
-        return OrderedDict(bbox=derive_results_lvis(self.eval))
+    def _evaluate_host(self, img_rank, cls, score, boxes):
+        return evaluate_host_lvis(self._gt, img_rank, cls, score, boxes, self.max_dets_per_image)
+
+    def _evaluate_device(self, img_rank, cls, score, boxes, mark=None):
+        return evaluate_device_lvis(self._gt, img_rank, cls, score, boxes, self.max_dets_per_image, mark)
+
+    def _derive_results(self, ev):
+        return derive_results_lvis(ev)
 
 
 def build_evaluator(dataset_name: str, gt, **kwargs):

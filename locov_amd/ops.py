@@ -3223,19 +3223,23 @@ def coco_order(img_rank: torch.Tensor, cls: torch.Tensor, score: torch.Tensor, b
                      score[perm][acc].contiguous())
 
 
-def coco_match(det_offsets: torch.Tensor, gt_offsets: torch.Tensor, det_boxes: torch.Tensor, gt_boxes: torch.Tensor,
-               gt_area: torch.Tensor, gt_crowd: torch.Tensor, area_ranges, iou_thresholds, max_det: int):
-    """locov_coco_match: -> det_bits uint8 [N, A * T] (bit 0 matched, bit 1 ignored), gt_ignore uint8 [A, G].  One launch, no host
-    read.  det_offsets / gt_offsets: int32 [C + 1]; det_boxes fp32 [N, 4] XYXY in cell order; gt_boxes fp64 [G, 4] XYWH, gt_area
-    fp64 [G], gt_crowd uint8 [G]; area_ranges [A][2] and iou_thresholds [T]: host doubles."""
+def _match(fn: str, det_offsets, gt_offsets, cell_flags, det_boxes, gt_boxes, gt_area, gt_flag, area_ranges, iou_thresholds, max_det):
+    """coco_match (cell_flags unused, gt_flag = gt_crowd) and lvis_match (gt_flag = gt_ignore_in): the checks, the outputs, the shared
+    workspace and the call of the entry point.  fn is the public name: it selects the protocol and the messages carry it."""
     import numpy as np
+    lvis = fn == "lvis_match"
+    flag_name = "gt_ignore_in" if lvis else "gt_crowd"
     det_offsets, gt_offsets = _dev(det_offsets, "det_offsets", torch.int32), _dev(gt_offsets, "gt_offsets", torch.int32)
+    if lvis:
+        cell_flags = _dev(cell_flags, "cell_flags", torch.uint8)
     det_boxes = _dev(det_boxes, "det_boxes")
     gt_boxes, gt_area = _dev(gt_boxes, "gt_boxes", torch.float64), _dev(gt_area, "gt_area", torch.float64)
-    gt_crowd = _dev(gt_crowd, "gt_crowd", torch.uint8)
+    gt_flag = _dev(gt_flag, flag_name, torch.uint8)
     C, N, G = det_offsets.shape[0] - 1, det_boxes.shape[0], gt_area.shape[0]
-    if gt_offsets.shape[0] != C + 1 or det_boxes.shape != (N, 4) or gt_boxes.shape != (G, 4) or gt_crowd.shape[0] != G:
-        raise ValueError("coco_match: offsets of C + 1 entries each, det_boxes [N,4], gt_boxes [G,4], gt_area [G], gt_crowd [G]")
+    if (gt_offsets.shape[0] != C + 1 or (lvis and cell_flags.shape[0] != C) or det_boxes.shape != (N, 4) or gt_boxes.shape != (G, 4)
+            or gt_flag.shape[0] != G):
+        raise ValueError(f"{fn}: offsets of C + 1 entries each, {'cell_flags [C], ' if lvis else ''}det_boxes [N,4], gt_boxes [G,4], "
+                         f"gt_area [G], {flag_name} [G]")
     ar = np.ascontiguousarray(area_ranges, dtype=np.float64).reshape(-1, 2)
     th = np.ascontiguousarray(iou_thresholds, dtype=np.float64).reshape(-1)
     A, T = len(ar), len(th)
@@ -3245,12 +3249,21 @@ def coco_match(det_offsets: torch.Tensor, gt_offsets: torch.Tensor, det_boxes: t
     lib = _lib.load()
     with torch.cuda.device(dev):
         ws_bytes = int(lib.locov_coco_match_workspace_bytes(G, int(max_det))) if N and G else 0
-        ws = _workspace("coco_match", det_boxes, ws_bytes) if ws_bytes else None
+        ws = _workspace("coco_match", det_boxes, ws_bytes) if ws_bytes else None      # one cached buffer for both protocols
         dp = ctypes.POINTER(ctypes.c_double)
-        check(lib.locov_coco_match(_ptr(det_offsets), _ptr(gt_offsets), C, N, G, int(max_det), _ptr(det_boxes), _ptr(gt_boxes), _ptr(gt_area),
-                                   _ptr(gt_crowd), ar.ctypes.data_as(dp), A, th.ctypes.data_as(dp), T, _ptr(bits), _ptr(gt_ignore), _ptr(ws),
-                                   ws_bytes, _stream(det_boxes)), "locov_coco_match")
+        entry, cells = (lib.locov_lvis_match, (_ptr(cell_flags),)) if lvis else (lib.locov_coco_match, ())
+        check(entry(_ptr(det_offsets), _ptr(gt_offsets), *cells, C, N, G, int(max_det), _ptr(det_boxes), _ptr(gt_boxes), _ptr(gt_area),
+                    _ptr(gt_flag), ar.ctypes.data_as(dp), A, th.ctypes.data_as(dp), T, _ptr(bits), _ptr(gt_ignore), _ptr(ws), ws_bytes,
+                    _stream(det_boxes)), "locov_" + fn)
     return bits, gt_ignore
+
+
+def coco_match(det_offsets: torch.Tensor, gt_offsets: torch.Tensor, det_boxes: torch.Tensor, gt_boxes: torch.Tensor,
+               gt_area: torch.Tensor, gt_crowd: torch.Tensor, area_ranges, iou_thresholds, max_det: int):
+    """locov_coco_match: -> det_bits uint8 [N, A * T] (bit 0 matched, bit 1 ignored), gt_ignore uint8 [A, G].  One launch, no host
+    read.  det_offsets / gt_offsets: int32 [C + 1]; det_boxes fp32 [N, 4] XYXY in cell order; gt_boxes fp64 [G, 4] XYWH, gt_area
+    fp64 [G], gt_crowd uint8 [G]; area_ranges [A][2] and iou_thresholds [T]: host doubles."""
+    return _match("coco_match", det_offsets, gt_offsets, None, det_boxes, gt_boxes, gt_area, gt_crowd, area_ranges, iou_thresholds, max_det)
 
 
 def coco_accumulate(cat_offsets: torch.Tensor, acc_index: torch.Tensor, acc_rank: torch.Tensor, acc_score: torch.Tensor,
@@ -3310,29 +3323,5 @@ def lvis_match(det_offsets: torch.Tensor, gt_offsets: torch.Tensor, cell_flags: 
     """locov_lvis_match: -> det_bits uint8 [N, A * T] (bit 0 matched, bit 1 ignored; 2 for every det of an unlisted cell),
     gt_ignore uint8 [A, G].  One launch, no host read.  As coco_match, with cell_flags uint8 [C] (_lib.LVIS_CELL_NEG |
     _lib.LVIS_CELL_NOT_EXHAUSTIVE) and gt_ignore_in uint8 [G] (the annotation's ignore field) in place of gt_crowd."""
-    import numpy as np
-    det_offsets, gt_offsets = _dev(det_offsets, "det_offsets", torch.int32), _dev(gt_offsets, "gt_offsets", torch.int32)
-    cell_flags = _dev(cell_flags, "cell_flags", torch.uint8)
-    det_boxes = _dev(det_boxes, "det_boxes")
-    gt_boxes, gt_area = _dev(gt_boxes, "gt_boxes", torch.float64), _dev(gt_area, "gt_area", torch.float64)
-    gt_ignore_in = _dev(gt_ignore_in, "gt_ignore_in", torch.uint8)
-    C, N, G = det_offsets.shape[0] - 1, det_boxes.shape[0], gt_area.shape[0]
-    if (gt_offsets.shape[0] != C + 1 or cell_flags.shape[0] != C or det_boxes.shape != (N, 4) or gt_boxes.shape != (G, 4)
-            or gt_ignore_in.shape[0] != G):
-        raise ValueError("lvis_match: offsets of C + 1 entries each, cell_flags [C], det_boxes [N,4], gt_boxes [G,4], gt_area [G], "
-                         "gt_ignore_in [G]")
-    ar = np.ascontiguousarray(area_ranges, dtype=np.float64).reshape(-1, 2)
-    th = np.ascontiguousarray(iou_thresholds, dtype=np.float64).reshape(-1)
-    A, T = len(ar), len(th)
-    dev = det_boxes.device
-    bits = torch.empty((N, A * T), dtype=torch.uint8, device=dev)
-    gt_ignore = torch.empty((A, G), dtype=torch.uint8, device=dev)
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        ws_bytes = int(lib.locov_coco_match_workspace_bytes(G, int(max_det))) if N and G else 0
-        ws = _workspace("coco_match", det_boxes, ws_bytes) if ws_bytes else None
-        dp = ctypes.POINTER(ctypes.c_double)
-        check(lib.locov_lvis_match(_ptr(det_offsets), _ptr(gt_offsets), _ptr(cell_flags), C, N, G, int(max_det), _ptr(det_boxes),
-                                   _ptr(gt_boxes), _ptr(gt_area), _ptr(gt_ignore_in), ar.ctypes.data_as(dp), A, th.ctypes.data_as(dp), T,
-                                   _ptr(bits), _ptr(gt_ignore), _ptr(ws), ws_bytes, _stream(det_boxes)), "locov_lvis_match")
-    return bits, gt_ignore
+    return _match("lvis_match", det_offsets, gt_offsets, cell_flags, det_boxes, gt_boxes, gt_area, gt_ignore_in, area_ranges, iou_thresholds,
+                  max_det)

@@ -144,6 +144,23 @@ def test_the_host_path_is_selected_by_the_environment(launches, monkeypatch):
     assert repr(res_host) == repr(res_dev)                                           # (repr: nan compares unequal to itself)
 
 
+def test_the_mark_hook_names_the_steps_and_changes_nothing(launches):
+    """evaluate_device calls `mark` after each of its steps, in order, and returns the arrays it returns without one."""
+    from locov_amd import evaluation as E
+    gt, dets = cases.handworked()
+    g = E._GroundTruth(gt)
+    arrays = (np.array([g.image_rank[d[0]] for d in dets], dtype=np.int64), np.array([d[1] for d in dets], dtype=np.int64),
+              np.array([float(d[2]) for d in dets], dtype=np.float64), np.stack([d[3] for d in dets]))
+    tensors = [torch.from_numpy(a).cuda() for a in arrays]
+    plain = E.evaluate_device(g, *tensors, (1, 10, 100))
+    names = []
+    marked = E.evaluate_device(g, *tensors, (1, 10, 100), mark=names.append)
+    assert names == ["orderings", "match", "npig", "accumulate", "copy_and_means"]
+    assert launches == dict(match=2, accumulate=2)
+    for key in KEYS:
+        assert marked[key].tobytes() == plain[key].tobytes(), key
+
+
 def test_end_to_end_on_device_instances_equals_the_cpu_evaluator(launches):
     gt, dets, max_dets, _ = _case("random3")
     names = [f"n{i}" for i in range(len(gt["categories"]))]

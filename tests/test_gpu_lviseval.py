@@ -211,6 +211,22 @@ def test_one_device_to_host_copy(monkeypatch):
     _assert_same(got, want)
 
 
+def test_the_mark_hook_names_the_steps_and_changes_nothing(launches):
+    """evaluate_device_lvis calls `mark` after each of its steps, in order, and returns the arrays it returns without one."""
+    from locov_amd import evaluation as E
+    gt, dets, cap, want = _case("handworked")
+    g, *arrays = _arrays(gt, dets)
+    tensors = [torch.from_numpy(a).cuda() for a in arrays]
+    plain = E.evaluate_device_lvis(g, *tensors, cap)
+    names = []
+    marked = E.evaluate_device_lvis(g, *tensors, cap, mark=names.append)
+    assert names == ["cap", "orderings", "match", "npig", "accumulate", "copy", "means"]
+    assert launches == dict(match=2, coco_match=0, accumulate=2)
+    for key in KEYS:
+        assert marked[key].tobytes() == plain[key].tobytes(), key
+    _assert_same(marked, want)
+
+
 def test_end_to_end_on_device_instances_equals_the_cpu_evaluator(launches):
     gt, dets, cap, _ = _case("random3")
     dev, res_dev = _run(gt, dets, cap, "cuda")

@@ -74,6 +74,34 @@ def test_the_host_path_equals_the_loop_restatement(name, cap):
     _same(ev.eval, lviseval_ref.evaluate(gt, dets, cap))
 
 
+def test_the_shared_matching_is_one_function_under_both_switches():
+    """With no ignore flag, no not-exhaustive entry and every cell listed, nothing the LVIS switches select can act (and without an
+    iscrowd field nothing the COCO ones select can): match_host and match_host_lvis give the same bits on the same dets."""
+    import copy
+    from locov_amd import evaluation as E
+    gt, dets = cases.random_case(2)
+    gt = copy.deepcopy(gt)
+    for a in gt["annotations"]:
+        a["ignore"] = 0
+    for im in gt["images"]:
+        im["not_exhaustive_category_ids"] = []
+        im["neg_category_ids"] = [c["id"] for c in gt["categories"]]
+    coco, lvis = E._GroundTruth(gt), E._LVISGroundTruth(gt)
+    assert not coco.crowd.any() and not lvis.ignore.any()
+    dets = [d for d in dets if 0 <= d[1] < coco.n_categories]                          # (the LVIS path leaves the others out first)
+    img = np.array([coco.image_rank[d[0]] for d in dets], dtype=np.int64)
+    cls = np.array([d[1] for d in dets], dtype=np.int64)
+    score = np.array([float(d[2]) for d in dets], dtype=np.float64)
+    perm, det_off, _, _, _ = E.order_host(img, cls, score, coco.n_images, coco.n_categories)
+    boxes = np.stack([d[3] for d in dets])[perm]
+    bits, gt_ignore = E.match_host(coco, det_off, boxes, 300)
+    bits_lvis, gt_ignore_lvis, listed = E.match_host_lvis(lvis, det_off, boxes, 300)
+    assert np.array_equal(bits, bits_lvis) and np.array_equal(gt_ignore, gt_ignore_lvis)
+    assert int(det_off[-1]) == len(dets) and listed[:int(det_off[-1])].all()
+    assert (bits == 1).any() and (bits == 0).any()                                     # matched and counted; unmatched and counted
+    assert ((np.diff(det_off) >= 2) & (np.diff(coco.offsets) >= 2)).any()              # a cell where the walk over the gts has a choice
+
+
 def test_the_large_case_equals_the_loop_restatement():
     gt, dets = cases.large_case()
     ev, _ = _run(gt, dets)

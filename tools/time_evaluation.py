@@ -9,10 +9,10 @@ image's gts with their class, 40 are random boxes of random classes; 5 % of the 
 one Instances per image, on the device for the device path and on the CPU for the host path; only evaluate() is timed.
 
 Per set: the wall time of evaluate() on the device (it ends in its one device-to-host copy, which synchronises) over `repeats`
-runs after `warmup`, median and 10th / 90th percentile; the same steps once more with a device synchronisation after each, to
-state the share of the gathering of the per-image tensors, the orderings (four stable sorts and two searches), the match launch,
-the accumulate launch, and the copy with the host's means; the host path's evaluate() `host-repeats` times; and whether the two
-paths' arrays are equal bit for bit.  Needs a ROCm GPU.
+runs after `warmup`, median and 10th / 90th percentile; the evaluator's own device function once more with a `mark` callback
+that synchronises the device after each of its steps, to state the share of the gathering of the per-image tensors, the orderings
+(four stable sorts and two searches), the match launch, the accumulate launch, and the copy with the host's means; the host
+path's evaluate() `host-repeats` times; and whether the two paths' arrays are equal bit for bit.  Needs a ROCm GPU.
 
 --protocol lvis (categories default to 1203): a federated set from a seed -- per image 11 gts over 4 of its categories (3 % with
 ignore = 1), 6 neg_category_ids and 1 not_exhaustive_category_id (drawn from all categories, so now and then a positive one), and
@@ -107,9 +107,8 @@ def feed(evaluator, per_image, device):
         evaluator.process([dict(image_id=img)], [dict(instances=inst)])
 
 
-def staged(ev, dev):
-    """evaluate_device's steps with a synchronisation after each -> milliseconds per step."""
-    from locov_amd import evaluation as E, ops
+def step_times(ev, dev):
+    """The evaluator's own device function with a synchronisation after each of its steps -> milliseconds per step."""
     t, marks = {}, [time.perf_counter()]
 
     def mark(name):
@@ -117,71 +116,19 @@ def staged(ev, dev):
         marks.append(time.perf_counter())
         t[name] = (marks[-1] - marks[-2]) * 1e3
 
-    gt, max_dets = ev._gt, ev.max_dets
-    img_rank, cls, score, boxes = ev._gathered(dev)
+    tensors = ev._gathered(dev)
     mark("gather")
-    g = gt.on(dev)
-    o = ops.coco_order(img_rank, cls, score, boxes, gt.n_images, gt.n_categories)
-    mark("orderings")
-    bits, gt_ignore = ops.coco_match(o.det_offsets, g["offsets"], o.boxes, g["box"], g["area"], g["crowd"], E.AREA_RNG, E.IOU_THRS, max_dets[-1])
-    mark("match")
-    c = torch.cat([torch.zeros((len(E.AREA_RNG), 1), dtype=torch.int64, device=dev), torch.cumsum(gt_ignore == 0, dim=1)], dim=1)
-    npig = (c[:, g["cat_offsets"][1:]] - c[:, g["cat_offsets"][:-1]]).t().contiguous().to(torch.int32)
-    mark("npig")
-    flat = ops.coco_accumulate(o.cat_offsets, o.acc_index, o.acc_rank, o.acc_score, bits, npig, len(E.IOU_THRS), max_dets, E.REC_THRS)
-    mark("accumulate")
-    host = flat.cpu().numpy()
-    K, A, T, R, M = gt.n_categories, len(E.AREA_RNG), len(E.IOU_THRS), len(E.REC_THRS), len(max_dets)
-    n = T * R * K * A * M
-    E.summarize(host[:n].reshape(T, R, K, A, M), host[2 * n:].reshape(T, K, A, M))
-    mark("copy_and_means")
-    return t
-
-
-def staged_lvis(ev, dev):
-    """evaluate_device_lvis's steps with a synchronisation after each -> milliseconds per step."""
-    from locov_amd import evaluation as E, ops
-    t, marks = {}, [time.perf_counter()]
-
-    def mark(name):
-        torch.cuda.synchronize(dev)
-        marks.append(time.perf_counter())
-        t[name] = (marks[-1] - marks[-2]) * 1e3
-
-    gt, cap = ev._gt, ev.max_dets_per_image
-    img_rank, cls, score, boxes = ev._gathered(dev)
-    mark("gather")
-    g = gt.on(dev)
-    cls = ops.lvis_limit(img_rank, cls, score, gt.n_images, gt.n_categories, cap)
-    mark("cap")
-    o = ops.coco_order(img_rank, cls, score, boxes, gt.n_images, gt.n_categories)
-    mark("orderings")
-    bits, gt_ignore = ops.lvis_match(o.det_offsets, g["offsets"], g["cell_flags"], o.boxes, g["box"], g["area"], g["ignore"], E.AREA_RNG,
-                                     E.IOU_THRS, cap)
-    mark("match")
-    c = torch.cat([torch.zeros((len(E.AREA_RNG), 1), dtype=torch.int64, device=dev), torch.cumsum(gt_ignore == 0, dim=1)], dim=1)
-    npig = (c[:, g["cat_offsets"][1:]] - c[:, g["cat_offsets"][:-1]]).t().contiguous().to(torch.int32)
-    mark("npig")
-    flat = ops.coco_accumulate(o.cat_offsets, o.acc_index, o.acc_rank, o.acc_score, bits, npig, len(E.IOU_THRS), (cap,), E.REC_THRS,
-                               with_scores=False)
-    mark("accumulate")
-    host = flat.cpu().numpy()
-    mark("copy")
-    K, A, T, R = gt.n_categories, len(E.AREA_RNG), len(E.IOU_THRS), len(E.REC_THRS)
-    n = T * R * K * A
-    E.summarize_lvis(host[:n].reshape(T, R, K, A), host[n:].reshape(T, K, A), gt.freq_groups)
-    mark("means")
+    ev._evaluate_device(*tensors, mark=mark)
     return t
 
 
 def measure(n_images, n_categories, args, dev):
     from locov_amd.evaluation import COCOEvaluator, LVISEvaluator
-    stage = staged
     t0 = time.perf_counter()
     if args.protocol == "lvis":
         gt, per_image = synthetic_lvis(n_images, n_categories)
         on_dev, on_host = LVISEvaluator(gt), LVISEvaluator(gt)
-        stage, keys = staged_lvis, ("precision", "recall", "stats")
+        keys = ("precision", "recall", "stats")
     else:
         gt, per_image = synthetic(n_images, n_categories)
         on_dev, on_host = COCOEvaluator(gt), COCOEvaluator(gt)
@@ -198,7 +145,7 @@ def measure(n_images, n_categories, args, dev):
         if it >= args.warmup:
             wall.append((time.perf_counter() - t0) * 1e3)
     rec["device_evaluate"] = spread(wall)
-    stages = [stage(on_dev, dev) for _ in range(args.warmup + args.repeats)][args.warmup:]
+    stages = [step_times(on_dev, dev) for _ in range(args.warmup + args.repeats)][args.warmup:]
     rec["device_stages_ms"] = {k: float(np.median([s[k] for s in stages])) for k in stages[0]}
     total = sum(rec["device_stages_ms"].values())
     rec["device_stage_share"] = {k: v / total for k, v in rec["device_stages_ms"].items()}
