@@ -134,16 +134,17 @@ __global__ __launch_bounds__(256) void rownorm_bwd_kernel(const float *__restric
     const float *p = x + row * D, *gr = g + row * D;
     float *q = dx + row * D;
     if (mode == LOCOV_NORM_L2) {
-        float ss = 0.f, xg = 0.f;
-        for (int k = lane; k < D; k += 64) {
-            ss += p[k] * p[k];
-            xg += p[k] * gr[k];
-        }
-        const float nrm = sqrtf(wave_sum(ss));
-        xg = wave_sum(xg);
+        float ss = 0.f;
+        for (int k = lane; k < D; k += 64) ss += p[k] * p[k];
+        const float nrm = sqrtf(wave_sum(ss));                               // (the same bits in every lane: the branch is uniform)
         if (nrm > eps) {
-            const float inv = 1.f / nrm, c = xg * inv * inv * inv;           // (y.g) y / den = x (x.g) / |x|^3
-            for (int k = lane; k < D; k += 64) q[k] = gr[k] * inv - p[k] * c;
+            // g and y (y.g) cancel -- completely for D = 1, where y = +-1 and dx = 0.  Both are formed from y = x / |x| itself, a
+            // correctly rounded quotient (exactly +-1 there), not from x and powers of a rounded 1 / |x|, whose roundings would
+            // leave an ulp of g / |x| behind where nothing should be.
+            float yg = 0.f;
+            for (int k = lane; k < D; k += 64) yg += (p[k] / nrm) * gr[k];
+            yg = wave_sum(yg);
+            for (int k = lane; k < D; k += 64) q[k] = (gr[k] - (p[k] / nrm) * yg) / nrm;
         } else {
             for (int k = lane; k < D; k += 64) q[k] = gr[k] / eps;
         }
