@@ -4,6 +4,7 @@
 // Compiled with -ffp-contract=off: the subtraction, the division and the products round one by one, as the torch ops they stand for.
 // The per-image tables travel in a by-value argument struct (the idiom of detect_common.h's DetGeom): no H2D copy, no workspace.
 #include "box_clip_common.h"
+#include "select_common.h"
 
 namespace locov {
 namespace {
@@ -107,14 +108,14 @@ struct RescaleArgs {
     float w[LOCOV_LABEL_MAX_IMAGES], h[LOCOV_LABEL_MAX_IMAGES];   // the output sizes, as the fp32 limits torch's clamp compares with
 };
 
-// One workgroup per image: 256 rows at a time, a ballot per wave and the four wave counts through LDS give each kept row its place.
+// One workgroup per image: 256 rows at a time, block_ballot_rank gives each kept row its place.
 __global__ __launch_bounds__(256) void detector_rescale_kernel(const float4 *__restrict__ boxes, RescaleArgs a, float4 *__restrict__ out_boxes,
                                                                int64_t *__restrict__ src, int *__restrict__ counts)
 {
     __shared__ int wave_kept[4];
     const int img = blockIdx.x, lo = a.roff[img], n = a.roff[img + 1] - lo;
     const float sx = a.sx[img], sy = a.sy[img], W = a.w[img], H = a.h[img];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     int kept = 0;
     for (int base = 0; base < n; base += 256) {
         const int r = base + tid;
@@ -128,16 +129,8 @@ __global__ __launch_bounds__(256) void detector_rescale_kernel(const float4 *__r
             b.w = clamp_like_torch(__fmul_rn(b.w, sy), H);
             keep = (__fsub_rn(b.z, b.x) > 0.f) && (__fsub_rn(b.w, b.y) > 0.f);
         }
-        const unsigned long long m = __ballot(keep);
-        if (lane == 0) wave_kept[wave] = __popcll(m);
-        __syncthreads();
-        int at = kept + __popcll(m & ((1ull << lane) - 1ull)), all = 0;
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const int ck = wave_kept[k];
-            at += k < wave ? ck : 0;
-            all += ck;
-        }
+        int all;
+        const int at = kept + block_ballot_rank<256>(keep, wave_kept, all);
         if (keep) {
             out_boxes[(int64_t)lo + at] = b;
             src[(int64_t)lo + at] = r;

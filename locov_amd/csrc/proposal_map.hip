@@ -5,6 +5,7 @@
 // Compiled with -ffp-contract=off: every product and difference rounds on its own, in the rows' dtype, as the numpy ops they stand for.
 // The per-image tables travel in a by-value argument struct (the idiom of image_batch.hip): no H2D copy, no workspace.
 #include "box_clip_common.h"
+#include "select_common.h"
 
 namespace locov {
 namespace {
@@ -45,10 +46,9 @@ __device__ __forceinline__ void map_axis(T a, T b, T factor, bool flipped, int s
     hi32 = clamp_like_torch((float)hi, (float)size);
 }
 
-// One workgroup per image, 256 rows at a time.  Two ballots per wave and the wave counts through LDS give every kept row its place
-// in the proposal list and, behind the cut at topk, every row above the threshold its place in the pseudo-GT list.  The counts are
-// integers carried from chunk to chunk, the same in every lane; the LDS counts alternate between two buffers so that a chunk needs
-// two barriers, not three.
+// One workgroup per image, 256 rows at a time.  Two block_ballot_ranks give every kept row its place in the proposal list and,
+// behind the cut at topk, every row above the threshold its place in the pseudo-GT list.  The counts are carried from chunk to chunk,
+// the same in every lane; the LDS counts alternate between two buffers, so a chunk needs the ranks' two barriers and no third.
 template <typename T>
 __global__ __launch_bounds__(256) void map_proposals_kernel(const T *__restrict__ rows, ProposalMapArgs a, int topk, float thr,
                                                             float4 *__restrict__ prop_boxes, float *__restrict__ prop_logits,
@@ -62,7 +62,7 @@ __global__ __launch_bounds__(256) void map_proposals_kernel(const T *__restrict_
     const T *src = rows + a.row_start[img] * 5;
     const T fx = (T)a.fx[img], fy = (T)a.fy[img];                 // (the weak Python scalar, rounded ONCE to the array's dtype)
     const int flip = a.flip[img], W = a.new_w[img], H = a.new_h[img];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     int kept = 0, gt_kept = 0, parity = 0;
     for (int base = 0; base < n && kept < topk; base += 256, parity ^= 1) {
         const int r = base + tid;
@@ -76,29 +76,11 @@ __global__ __launch_bounds__(256) void map_proposals_kernel(const T *__restrict_
             logit = (float)p[4];
             keep = (__fsub_rn(b.z, b.x) > 0.f) && (__fsub_rn(b.w, b.y) > 0.f);
         }
-        const unsigned long long below = (1ull << lane) - 1ull;
-        const unsigned long long m = __ballot(keep);
-        if (lane == 0) wave_count[parity][0][wave] = __popcll(m);
-        __syncthreads();
-        int at = kept + __popcll(m & below), all = 0;
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const int ck = wave_count[parity][0][k];
-            at += k < wave ? ck : 0;
-            all += ck;
-        }
+        int all, gt_all;
+        const int at = kept + block_ballot_rank<256>(keep, wave_count[parity][0], all);
         const bool take = keep && at < topk;
         const bool as_gt = take && logit > thr;
-        const unsigned long long mg = __ballot(as_gt);
-        if (lane == 0) wave_count[parity][1][wave] = __popcll(mg);
-        __syncthreads();
-        int gt_at = gt_kept + __popcll(mg & below), gt_all = 0;
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const int ck = wave_count[parity][1][k];
-            gt_at += k < wave ? ck : 0;
-            gt_all += ck;
-        }
+        const int gt_at = gt_kept + block_ballot_rank<256>(as_gt, wave_count[parity][1], gt_all);
         if (take) {
             prop_boxes[out + at] = b;
             prop_logits[out + at] = logit;

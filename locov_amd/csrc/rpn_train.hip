@@ -134,7 +134,7 @@ __global__ __launch_bounds__(kRtSelThreads) void rpn_sample_kernel(const signed 
     __shared__ int hist[kRtBins];
     __shared__ int wave_sum[kRtSelWaves];
     __shared__ int ctl[3];                                       // picked bin, keys before it, keys in it
-    const int img = blockIdx.x, part = blockIdx.y, tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+    const int img = blockIdx.x, part = blockIdx.y, tid = threadIdx.x;
     const signed char target = part == 0 ? 1 : 0;
     const signed char *L = labels + (int64_t)img * hwa;
     const unsigned long long *K = reinterpret_cast<const unsigned long long *>(rnd) + ((int64_t)part * n_images + img) * hwa;
@@ -193,16 +193,9 @@ __global__ __launch_bounds__(kRtSelThreads) void rpn_sample_kernel(const signed 
             }
         }
         if (!all && !none) {                                     // (uniform)
-            const unsigned long long bt = __ballot(tie);
-            if (lane == 0) wave_sum[wave] = (int)__popcll(bt);
-            __syncthreads();
-            int before = ties_seen, total = 0;
-            for (int q = 0; q < kRtSelWaves; q++) {
-                const int c = wave_sum[q];
-                before += q < wave ? c : 0;
-                total += c;
-            }
-            if (tie) take = before + lanes_below(bt) < need;
+            int total;
+            const int before = ties_seen + block_ballot_rank<kRtSelThreads>(tie, wave_sum, total);
+            if (__builtin_expect(tie, false)) take = before < need;         // (rare; the hint keeps the rank's sum a branch most waves skip)
             ties_seen += total;
             __syncthreads();
         }

@@ -1,6 +1,6 @@
 // The building blocks of every box-selection pipeline, ONE copy each: the IoU predicates, the block-wide scan and the radix digit
 // pick on top of it, the wave-level compacting append, the candidate key layout and the small index helpers.  Users: nms.hip,
-// detect.hip, detect_wide.hip, rpn.hip, rpn_train.hip, label.hip (rpn_select_kernel alone keeps its own text of the scan, the pick
+// detect.hip, detect_wide.hip, rpn.hip, rpn_train.hip, label.hip, image_batch.hip, proposal_map.hip (rpn_select_kernel alone keeps its own text of the scan, the pick
 // and the append: see the comment there).  Only __forceinline__ functions and constants live here -- no
 // kernels, no global state -- and a new selection kernel starts from these instead of copying a neighbour.
 //
@@ -93,6 +93,29 @@ __device__ __forceinline__ int block_exclusive_scan(int v, int (&wave_sum)[kThre
     int before = incl - v;
     for (int w = 0; w < wave; w++) before += wave_sum[w];
     return before;
+}
+
+// Ordered rank over a workgroup of kThreads threads: returns how many of the threads below this one have `flag` set, and leaves the
+// workgroup's number of flagged threads in `total` (the same in every thread).  One ballot per wave and ONE __syncthreads() inside,
+// between the write of wave_count[] (one int per wave: its flagged lanes) and its reads; as with block_exclusive_scan the caller
+// owns the barrier before wave_count[] is written again (it is still being read when the first thread returns).
+template <int kThreads>
+__device__ __forceinline__ int block_ballot_rank(bool flag, int (&wave_count)[kThreads / 64], int &total)
+{
+    static_assert(kThreads % 64 == 0, "block_ballot_rank: whole waves");
+    const int wave = threadIdx.x >> 6;
+    const unsigned long long b = __ballot(flag);
+    if ((threadIdx.x & 63) == 0) wave_count[wave] = __popcll(b);
+    __syncthreads();
+    int below = lanes_below(b);
+    total = 0;
+#pragma unroll
+    for (int w = 0; w < kThreads / 64; w++) {
+        const int c = wave_count[w];
+        below += w < wave ? c : 0;
+        total += c;
+    }
+    return below;
 }
 
 // One digit of a radix select by a workgroup of kThreads threads.  Thread t holds the counts v[] of bins t * kPer .. t * kPer + kPer - 1 of the digit's histogram; the

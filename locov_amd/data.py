@@ -49,11 +49,13 @@ import copy
 import math
 import os
 import random
-from typing import Dict, Iterable, Iterator, List, Optional, Sequence, Tuple
+from dataclasses import dataclass
+from typing import Dict, Iterable, Iterator, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
 
+from . import ops
 from .structures import Boxes, Instances
 
 PRECISION_BITS = 22                      # Pillow's PRECISION_BITS for 8-bit channels: 32 - 8 - 2
@@ -444,16 +446,27 @@ class ProposalStore:
 
 # ---- the mapper ----------------------------------------------------------------------------------------------------------------
 
-def _fused_enabled() -> bool:
-    return os.environ.get("LOCOV_FUSED_RESIZE", "1") != "0"
+@dataclass
+class _Prepared:
+    """One image between _prepare and _finish: the dict being built, the raw HWC image, its drawn transforms, their (new_h, new_w)."""
+    d: dict
+    raw: Union[np.ndarray, torch.Tensor]
+    transforms: TransformList
+    size: Tuple[int, int]
+
+    @property
+    def flip(self) -> int:
+        return max((t.flip for t in self.transforms.transforms), default=FLIP_NONE)
+
+    @property
+    def factors(self) -> Tuple[float, float]:                      # (fx, fy) as ResizeTransform.apply_coords forms them, in double
+        resize, (nh, nw) = self.transforms.transforms[0], self.size
+        return (nw * 1.0 / resize.w, nh * 1.0 / resize.h) if isinstance(resize, ResizeTransform) else (1.0, 1.0)
 
 
-def _fused_augment_enabled() -> bool:
-    return os.environ.get("LOCOV_FUSED_AUGMENT", "1") != "0"
-
-
-def _fused_proposals_enabled() -> bool:
-    return os.environ.get("LOCOV_FUSED_PROPOSALS", "1") != "0"
+def _slices(idx: List[int]) -> Iterator[List[int]]:               # the images a kernel takes, as many at a time as one call holds
+    for lo in range(0, len(idx), ops.IMAGE_BATCH_MAX_IMAGES):
+        yield idx[lo:lo + ops.IMAGE_BATCH_MAX_IMAGES]
 
 
 def _read_file(path: str, fmt: str) -> np.ndarray:
@@ -497,7 +510,7 @@ class DatasetMapper:
         self.is_train = bool(is_train)
         _refuse_unbuilt(cfg, strong_given=train_aug is not None)
         self.augmentations = _resize_and_flip(cfg, is_train)
-        self._decoded: Optional[Dict[str, Optional[np.ndarray]]] = None   # files draw_sample read for their size (train_aug only), until _raw takes them
+        self._decoded: Dict[str, Optional[np.ndarray]] = {}        # files draw_sample read for their size (train_aug only), until _raw takes them
         self.train_aug = train_aug if self.is_train else None      # (basic_mappers.py:171: applied in training only)
         if getattr(cfg.MODEL, "MASK_ON", False) or getattr(cfg.MODEL, "KEYPOINT_ON", False):
             raise NotImplementedError("MODEL.MASK_ON / KEYPOINT_ON: only the box side of the mapper is built")
@@ -510,6 +523,9 @@ class DatasetMapper:
         self.device = torch.device(device)
         self.rng = random.Random(seed)
 
+    def _on_device(self, stage: str) -> bool:                      # the stage's kernel serves a cuda mapper unless LOCOV_FUSED_<stage>=0
+        return self.device.type == "cuda" and os.environ.get(f"LOCOV_FUSED_{stage}", "1") != "0"
+
     # -- the draws
     def _caption_choices(self, d: dict):
         return d.get("caption")
@@ -518,8 +534,7 @@ class DatasetMapper:
         resize = self.augmentations[0]
         flip = self.augmentations[1] if len(self.augmentations) > 1 else None
         sample = {"short_edge": [], "flip": [], "caption": []}
-        if self._decoded:
-            self._decoded.clear()
+        self._decoded.clear()
         for d in dataset_dicts:
             sample["short_edge"].append(int(resize.draw(self.rng)))
             sample["flip"].append(bool(flip.draw(self.rng)) if flip is not None else False)
@@ -546,8 +561,6 @@ class DatasetMapper:
         except Exception:
             image = None
         if "file_name" in d:
-            if self._decoded is None:
-                self._decoded = {}
             self._decoded[d["file_name"]] = image
         if image is None:
             return int(d["height"]), int(d["width"])               # (the black image of _raw)
@@ -563,7 +576,7 @@ class DatasetMapper:
                 raise TypeError(f"image_raw must be uint8 [H, W, C], got {raw.dtype} {tuple(raw.shape)}")
             return raw, True
         try:
-            if self._decoded and d.get("file_name") in self._decoded:                # (draw_sample read it for its size; None: it failed there)
+            if d.get("file_name") in self._decoded:                                  # (draw_sample read it for its size; None: it failed there)
                 image = self._decoded.pop(d["file_name"])
                 if image is None:
                     raise OSError("not decoded")
@@ -594,37 +607,32 @@ class DatasetMapper:
             d["caption"] = d["caption"][int(sample["caption"][i])] if self.is_train else d["caption"][0]
             if not loaded:
                 d["caption"] = "A black image."
-        return d, raw, transforms, (nh, nw)
+        return _Prepared(d, raw, transforms, (nh, nw))
 
-    def _host_image(self, raw, transforms: TransformList) -> torch.Tensor:
-        img = raw.cpu().numpy() if isinstance(raw, torch.Tensor) else raw
-        img = transforms.apply_image(img)
-        return torch.as_tensor(np.ascontiguousarray(img.transpose(2, 0, 1))).to(self.device)
+    def _chw(self, hwc: np.ndarray) -> torch.Tensor:               # a host HWC image as the CHW tensor on the mapper's device
+        return torch.as_tensor(np.ascontiguousarray(hwc.transpose(2, 0, 1))).to(self.device)
+
+    def _host_image(self, p: _Prepared) -> torch.Tensor:
+        return self._chw(p.transforms.apply_image(p.raw.cpu().numpy() if isinstance(p.raw, torch.Tensor) else p.raw))
 
     def map_batch(self, dataset_dicts: Sequence[dict], sample: Optional[Dict[str, list]] = None) -> List[dict]:
         dataset_dicts = list(dataset_dicts)
         sample = self.draw_sample(dataset_dicts) if sample is None else sample
         prepared = [self._prepare(d, i, sample) for i, d in enumerate(dataset_dicts)]
-        if self._decoded:
-            self._decoded.clear()
-        on_device = self.device.type == "cuda" and _fused_enabled()
+        self._decoded.clear()
         fused: Dict[int, List[int]] = {}                           # channel count -> the images the kernel takes
-        images: List[Optional[torch.Tensor]] = [None] * len(prepared)
-        if on_device:
-            from . import ops
-            for i, (_, raw, _, size) in enumerate(prepared):
-                C = int(raw.shape[2])
-                if 1 <= C <= ops.IMAGE_BATCH_MAX_CHANNELS and ops.resize_supported(raw.shape[:2], size, C):
+        if self._on_device("RESIZE"):
+            for i, p in enumerate(prepared):
+                C = int(p.raw.shape[2])
+                if 1 <= C <= ops.IMAGE_BATCH_MAX_CHANNELS and ops.resize_supported(p.raw.shape[:2], p.size, C):
                     fused.setdefault(C, []).append(i)
-            for idx in fused.values():
-                for lo in range(0, len(idx), ops.IMAGE_BATCH_MAX_IMAGES):
-                    part = idx[lo:lo + ops.IMAGE_BATCH_MAX_IMAGES]
-                    raws = [torch.as_tensor(prepared[i][1]).to(self.device, non_blocking=True) for i in part]
-                    flips = [max((t.flip for t in prepared[i][2].transforms), default=FLIP_NONE) for i in part]
-                    for i, image in zip(part, ops.resize_flip_images(raws, [prepared[i][3] for i in part], flips)):
-                        images[i] = image
-        for image, (d, raw, transforms, _) in zip(images, prepared):
-            d["image"] = image if image is not None else self._host_image(raw, transforms)
+        images: Dict[int, torch.Tensor] = {}                       # what the kernel made, by the image's place in the batch
+        for idx in fused.values():
+            for part in _slices(idx):
+                raws = [torch.as_tensor(prepared[i].raw).to(self.device, non_blocking=True) for i in part]
+                images.update(zip(part, ops.resize_flip_images(raws, [prepared[i].size for i in part], [prepared[i].flip for i in part])))
+        for i, p in enumerate(prepared):
+            p.d["image"] = images[i] if i in images else self._host_image(p)
         if self.train_aug is not None:
             self._strong(prepared, sample)
         return self._finish(prepared)
@@ -650,46 +658,39 @@ class DatasetMapper:
         draws = list(sample["strong"])
         if len(draws) != len(prepared):
             raise ValueError(f"sample['strong'] holds {len(draws)} entries for {len(prepared)} images")
-        for s, (d, _, _, (nh, nw)) in zip(draws, prepared):
-            if tuple(d["image"].shape[1:]) != (nh, nw) or any(e is not None and (e[0] + e[2] > nh or e[1] + e[3] > nw) for e in s["erase"]):
+        for s, p in zip(draws, prepared):
+            nh, nw = p.size
+            if tuple(p.d["image"].shape[1:]) != (nh, nw) or any(e is not None and (e[0] + e[2] > nh or e[1] + e[3] > nw) for e in s["erase"]):
                 raise ValueError(f"sample['strong']: an eraser was drawn for another size than the image's {(nh, nw)}")
         noise = self.erase_noise(sample)
         counts = [sa.noise_count(s) for s in draws]
         offsets = [0] + list(np.cumsum(counts)[:-1])
-        fused: List[int] = []
-        if self.device.type == "cuda" and _fused_augment_enabled():
-            from . import ops
-            fused = [i for i, (s, p) in enumerate(zip(draws, prepared))
-                     if p[0]["image"].shape[0] == 3 and (not s["blur"] or ops.augment_supported(s["sigma"]))]
-            for lo in range(0, len(fused), ops.IMAGE_BATCH_MAX_IMAGES):
-                part = fused[lo:lo + ops.IMAGE_BATCH_MAX_IMAGES]
-                outs = ops.augment_images([prepared[i][0]["image"] for i in part], [draws[i] for i in part], noise,
-                                          [int(offsets[i]) for i in part])
-                for i, image in zip(part, outs):
-                    prepared[i][0]["image"] = image
+        takes = lambda s, p: p.d["image"].shape[0] == 3 and (not s["blur"] or ops.augment_supported(s["sigma"]))
+        fused = [i for i, (s, p) in enumerate(zip(draws, prepared)) if takes(s, p)] if self._on_device("AUGMENT") else []
+        images: Dict[int, torch.Tensor] = {}
+        for part in _slices(fused):
+            images.update(zip(part, ops.augment_images([prepared[i].d["image"] for i in part], [draws[i] for i in part], noise,
+                                                       [int(offsets[i]) for i in part])))
         host_noise = None
-        for i, (s, p) in enumerate(zip(draws, prepared)):
-            if i in fused:
-                continue
-            if host_noise is None:
-                host_noise = noise.cpu().numpy()
-            hwc = p[0]["image"].permute(1, 2, 0).cpu().numpy()
-            out = sa.apply_host(hwc, s, host_noise[offsets[i]:offsets[i] + counts[i]])
-            p[0]["image"] = torch.as_tensor(np.ascontiguousarray(out.transpose(2, 0, 1))).to(self.device)
+        for i, p in enumerate(prepared):
+            if i not in images:
+                host_noise = noise.cpu().numpy() if host_noise is None else host_noise
+                hwc = p.d["image"].permute(1, 2, 0).cpu().numpy()
+                images[i] = self._chw(sa.apply_host(hwc, draws[i], host_noise[offsets[i]:offsets[i] + counts[i]]))
+            p.d["image"] = images[i]
 
     def __call__(self, dataset_dict: dict, sample: Optional[Dict[str, list]] = None) -> dict:
         return self.map_batch([dataset_dict], sample)[0]
 
     # -- the proposal side (MODEL.LOAD_OBJ_PROPOSALS)
-    def _finish(self, prepared) -> List[dict]:
+    def _finish(self, prepared: List[_Prepared]) -> List[dict]:
         if self.proposal_topk is not None:
             self._map_proposals(prepared, as_gt=False)
-        return [p[0] for p in prepared]
+        return [p.d for p in prepared]
 
     def _proposal_rows(self, dicts: List[dict]):
         """(rows [R, 5] on the device, first row per image, rows per image) for the dicts, which all carry "proposal_boxes": their
         rows packed into ONE pinned buffer and uploaded once.  None where only the host definition applies."""
-        from . import ops
         boxes = [np.asarray(d["proposal_boxes"]) for d in dicts]
         logits = [np.asarray(d["proposal_objectness_logits"]) for d in dicts]
         dtypes = {a.dtype for a in boxes + logits}
@@ -705,38 +706,32 @@ class DatasetMapper:
             view[s:s + n, :4], view[s:s + n, 4] = b, l
         return pinned.to(self.device, non_blocking=True), starts, counts
 
-    def _map_proposals(self, prepared, as_gt: bool) -> bool:
-        """transform_proposals for the dicts that carry proposals.  On a cuda device, in one launch (ops.map_proposals), which with
-        as_gt also does change_proposals_as_gt; returns whether it did.  Otherwise -- LOCOV_FUSED_PROPOSALS=0, a CPU device, a
-        dtype or box mode the kernel does not take -- the host definition, its result moved to the device."""
-        idx = [i for i, p in enumerate(prepared) if "proposal_boxes" in p[0]]
-        if not idx:
-            return False
-        dicts = [prepared[i][0] for i in idx]
-        source = self._proposal_rows(dicts) if self.device.type == "cuda" and _fused_proposals_enabled() else None
+    def _map_proposals(self, prepared: List[_Prepared], as_gt: bool) -> None:
+        """transform_proposals, and with as_gt change_proposals_as_gt behind it, for the dicts that carry proposals; the others are
+        left as they are.  On a cuda device both are one launch (ops.map_proposals).  Otherwise -- LOCOV_FUSED_PROPOSALS=0, a CPU
+        device, a dtype or box mode the kernel does not take -- the host definition, its result moved to the device."""
+        carrying = [p for p in prepared if "proposal_boxes" in p.d]
+        if not carrying:
+            return
+        source = self._proposal_rows([p.d for p in carrying]) if self._on_device("PROPOSALS") else None
         if source is None:
-            for i in idx:
-                d, _, transforms, size = prepared[i]
-                transform_proposals(d, size, transforms, self.proposal_topk)
-                d["proposals"] = d["proposals"].to(self.device)
-            return False
-        from . import ops
-        factors, flips = [], []
-        for i in idx:
-            resize, (nh, nw) = prepared[i][2].transforms[0], prepared[i][3]
-            factors.append((nw * 1.0 / resize.w, nh * 1.0 / resize.h) if isinstance(resize, ResizeTransform) else (1.0, 1.0))
-            flips.append(max((t.flip for t in prepared[i][2].transforms), default=FLIP_NONE))
-        sizes = [prepared[i][3] for i in idx]
-        mapped = ops.map_proposals(*source, factors, flips, sizes, self.proposal_topk, OBJECTNESS_THR)
-        for d, m, size in zip(dicts, mapped, sizes):
+            for p in carrying:
+                transform_proposals(p.d, p.size, p.transforms, self.proposal_topk)
+                p.d["proposals"] = p.d["proposals"].to(self.device)
+                if as_gt:
+                    p.d = change_proposals_as_gt(p.d)
+            return
+        mapped = ops.map_proposals(*source, [p.factors for p in carrying], [p.flip for p in carrying], [p.size for p in carrying],
+                                   self.proposal_topk, OBJECTNESS_THR)
+        for p, m in zip(carrying, mapped):
+            d, size = p.d, tuple(p.size)
             for key in ("proposal_boxes", "proposal_bbox_mode", "proposal_objectness_logits"):
                 d.pop(key)
             if as_gt:
                 d["gt_obj"] = d.pop("instances")
-                d["instances"] = Instances(tuple(size), objectness_logits=m.gt_logits, gt_classes=m.gt_classes, gt_boxes=Boxes(m.gt_boxes))
+                d["instances"] = Instances(size, objectness_logits=m.gt_logits, gt_classes=m.gt_classes, gt_boxes=Boxes(m.gt_boxes))
             else:
-                d["proposals"] = Instances(tuple(size), proposal_boxes=Boxes(m.prop_boxes), objectness_logits=m.prop_logits)
-        return as_gt
+                d["proposals"] = Instances(size, proposal_boxes=Boxes(m.prop_boxes), objectness_logits=m.prop_logits)
 
 
 class CocoImageDatasetMapper(DatasetMapper):
@@ -788,11 +783,15 @@ class CocoImageDatasetMapper(DatasetMapper):
         where = [store.table[d["image_id"]] for d in dicts]
         return store.rows, [s for s, _ in where], [n for _, n in where]
 
-    def _finish(self, prepared) -> List[dict]:
+    def _finish(self, prepared: List[_Prepared]) -> List[dict]:
         if self.store is None:
             return super()._finish(prepared)
-        fused = self.proposal_topk is not None and self._map_proposals(prepared, as_gt=True)
-        return [p[0] if fused and "gt_obj" in p[0] else change_proposals_as_gt(p[0]) for p in prepared]
+        rest = [p for p in prepared if self.proposal_topk is None or "proposal_boxes" not in p.d]
+        if self.proposal_topk is not None:
+            self._map_proposals(prepared, as_gt=True)
+        for p in rest:                                             # (nobody made their "proposals": the reference's KeyError)
+            p.d = change_proposals_as_gt(p.d)
+        return [p.d for p in prepared]
 
 
 def get_mapper(dataset_name: str, cfg, is_train: bool, metadata=None, device=None, train_aug=None) -> DatasetMapper:

@@ -64,6 +64,30 @@ def _ptr(t: Optional[torch.Tensor]) -> ctypes.c_void_p:
     return ctypes.c_void_p(t.data_ptr() if t is not None else 0)
 
 
+def _images(images: Sequence[torch.Tensor], axis: int, dtype=torch.uint8) -> Tuple[List[torch.Tensor], int]:
+    """A data-side op's device images, contiguous, and their channel count: -1 unless all are rank 3, one size on `axis`, on one device."""
+    ims = [_dev(t, f"images[{i}]", dtype=dtype) for i, t in enumerate(images)]
+    C = int(ims[0].shape[axis]) if ims[0].dim() == 3 else -1
+    return ims, -1 if any(t.dim() != 3 or t.shape[axis] != C or t.device != ims[0].device for t in ims) else C
+
+
+def _ptrs(tensors: Sequence[torch.Tensor]):
+    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+def _ints(values: Sequence[int]):
+    return (ctypes.c_int * len(values))(*values)
+
+
+def _out_images(out: Sequence[torch.Tensor], shapes, device, what: str, apart_from=()) -> List[torch.Tensor]:
+    """A data-side op's `out` as a list: a contiguous uint8 tensor per shape on `device`, none the one at its place in `apart_from`."""
+    outs = list(out)
+    if len(outs) != len(shapes) or any(o.dtype != torch.uint8 or tuple(o.shape) != tuple(s) or o.device != device or not o.is_contiguous()
+                                       for o, s in zip(outs, shapes)) or any(o.data_ptr() == t.data_ptr() for o, t in zip(outs, apart_from)):
+        raise ValueError(what)
+    return outs
+
+
 def _dtype_code(dt: torch.dtype) -> int:
     if dt == torch.float32:
         return F32
@@ -2680,11 +2704,11 @@ def preprocess_images(images: Sequence[torch.Tensor], mean: Sequence[float], std
     images = list(images)
     if not images:
         raise ValueError("preprocess_images: no image")
-    ims = [_dev(t, f"images[{i}]", dtype=None) for i, t in enumerate(images)]
-    dt, C = ims[0].dtype, ims[0].shape[0] if ims[0].dim() == 3 else -1
+    ims, C = _images(images, 0, dtype=None)
+    dt = ims[0].dtype
     if dt not in (torch.uint8, torch.float32) or any(t.dtype != dt for t in ims):
         raise TypeError("preprocess_images: the images must all be uint8 or all be fp32")
-    if any(t.dim() != 3 or t.shape[0] != C or t.device != ims[0].device for t in ims):
+    if C < 0:
         raise ValueError("preprocess_images: the images must be [C, H, W] with one channel count, on one device")
     mean, std = [float(v) for v in mean], [float(v) for v in std]
     if not (1 <= C <= IMAGE_BATCH_MAX_CHANNELS) or len(mean) != C or len(std) != C or len(ims) > IMAGE_BATCH_MAX_IMAGES:
@@ -2694,10 +2718,9 @@ def preprocess_images(images: Sequence[torch.Tensor], mean: Sequence[float], std
     Hb, Wb = padded_batch_size(image_sizes, size_divisibility, padding_constraints)
     n = len(ims)
     out = _out(out, (n, C, Hb, Wb), ims[0], "preprocess_images")
-    ptrs = (ctypes.c_void_p * n)(*[t.data_ptr() for t in ims])
-    hs, ws = (ctypes.c_int * n)(*[s[0] for s in image_sizes]), (ctypes.c_int * n)(*[s[1] for s in image_sizes])
+    hs, ws = _ints([s[0] for s in image_sizes]), _ints([s[1] for s in image_sizes])
     with torch.cuda.device(out.device):
-        check(_lib.load().locov_preprocess_images(ptrs, hs, ws, n, _lib.IMAGE_U8 if dt == torch.uint8 else _lib.IMAGE_F32, C,
+        check(_lib.load().locov_preprocess_images(_ptrs(ims), hs, ws, n, _lib.IMAGE_U8 if dt == torch.uint8 else _lib.IMAGE_F32, C,
                                                   (ctypes.c_float * C)(*mean), (ctypes.c_float * C)(*std), float(pad_value),
                                                   _ptr(out), Hb, Wb, _stream(out)), "locov_preprocess_images")
     return out, image_sizes
@@ -2757,9 +2780,8 @@ def resize_flip_images(images: Sequence[torch.Tensor], out_sizes, flips: Optiona
     n = len(images)
     if n == 0:
         return []
-    ims = [_dev(t, f"images[{i}]", dtype=torch.uint8) for i, t in enumerate(images)]
-    C = ims[0].shape[2] if ims[0].dim() == 3 else -1
-    if any(t.dim() != 3 or t.shape[2] != C or t.device != ims[0].device for t in ims):
+    ims, C = _images(images, 2)
+    if C < 0:
         raise ValueError("resize_flip_images: the images must be [H, W, C] with one channel count, on one device")
     flips = [FLIP_NONE] * n if flips is None else [int(f) for f in flips]
     out_sizes = [(int(s[0]), int(s[1])) for s in out_sizes]
@@ -2770,19 +2792,13 @@ def resize_flip_images(images: Sequence[torch.Tensor], out_sizes, flips: Optiona
         if min(t.shape[0], t.shape[1]) < 1 or min(s) < 1 or not resize_supported(t.shape[:2], s, C):
             raise ValueError(f"resize_flip_images: {tuple(t.shape[:2])} -> {s} is outside the kernel's limits (positive sizes, at most "
                              f"{RESIZE_MAX_TAPS} taps per axis)")
-    if out is None:
-        outs = [torch.empty((C, s[0], s[1]), dtype=torch.uint8, device=ims[0].device) for s in out_sizes]
-    else:
-        outs = list(out)
-        if len(outs) != n or any(o.dtype != torch.uint8 or tuple(o.shape) != (C, s[0], s[1]) or o.device != ims[0].device
-                                 or not o.is_contiguous() for o, s in zip(outs, out_sizes)):
-            raise ValueError("resize_flip_images: out must hold one contiguous uint8 [C, new_h, new_w] tensor per image, on the images' device")
-    ints = lambda vals: (ctypes.c_int * n)(*vals)
+    shapes = [(C, s[0], s[1]) for s in out_sizes]
+    outs = [torch.empty(s, dtype=torch.uint8, device=ims[0].device) for s in shapes] if out is None else _out_images(
+        out, shapes, ims[0].device, "resize_flip_images: out must hold one contiguous uint8 [C, new_h, new_w] tensor per image, on the images' device")
     with torch.cuda.device(ims[0].device):
         check(_lib.load().locov_resize_flip_images(
-            (ctypes.c_void_p * n)(*[t.data_ptr() for t in ims]), ints([t.shape[0] for t in ims]), ints([t.shape[1] for t in ims]),
-            (ctypes.c_void_p * n)(*[o.data_ptr() for o in outs]), ints([s[0] for s in out_sizes]), ints([s[1] for s in out_sizes]),
-            ints(flips), n, C, _stream(ims[0])), "locov_resize_flip_images")
+            _ptrs(ims), _ints([t.shape[0] for t in ims]), _ints([t.shape[1] for t in ims]), _ptrs(outs), _ints([s[0] for s in out_sizes]),
+            _ints([s[1] for s in out_sizes]), _ints(flips), n, C, _stream(ims[0])), "locov_resize_flip_images")
     return outs
 
 
@@ -2833,8 +2849,8 @@ def augment_images(images: Sequence[torch.Tensor], draws: Sequence[dict], noise:
     n = len(images)
     if n == 0:
         return []
-    ims = [_dev(t, f"images[{i}]", dtype=torch.uint8) for i, t in enumerate(images)]
-    if any(t.dim() != 3 or t.shape[0] != 3 or min(t.shape[1:]) < 1 or t.device != ims[0].device for t in ims):
+    ims, C = _images(images, 0)
+    if C != 3 or any(min(t.shape[1:]) < 1 for t in ims):
         raise ValueError("augment_images: the images must be non-empty [3, H, W], on one device")
     if len(draws) != n or n > IMAGE_BATCH_MAX_IMAGES or (noise_offsets is not None and len(noise_offsets) != n):
         raise ValueError(f"augment_images: one dict of draws (and one noise offset) per image, at most {IMAGE_BATCH_MAX_IMAGES} images")
@@ -2854,20 +2870,14 @@ def augment_images(images: Sequence[torch.Tensor], draws: Sequence[dict], noise:
         if noise is None or noise.dim() != 1 or noise.device != ims[0].device or end > noise.numel():
             raise ValueError(f"augment_images: noise must be a device fp32 [>= {end}] vector holding every eraser's block")
         n_noise = int(noise.numel())
-    if out is None:
-        outs = [torch.empty_like(t) for t in ims]
-    else:
-        outs = list(out)
-        if len(outs) != n or any(o.dtype != torch.uint8 or o.shape != t.shape or o.device != t.device or not o.is_contiguous()
-                                 or o.data_ptr() == t.data_ptr() for o, t in zip(outs, ims)):
-            raise ValueError("augment_images: out must hold one contiguous uint8 tensor of each image's shape, on its device, not the image itself")
+    outs = [torch.empty_like(t) for t in ims] if out is None else _out_images(out, [t.shape for t in ims], ims[0].device, apart_from=ims, what=(
+        "augment_images: out must hold one contiguous uint8 tensor of each image's shape, on its device, not the image itself"))
     lib = _lib.load()
     ws_bytes = int(lib.locov_augment_images_workspace_bytes(descs, n))
     workspace = torch.empty(ws_bytes, dtype=torch.uint8, device=ims[0].device)
     with torch.cuda.device(ims[0].device):
-        check(lib.locov_augment_images(
-            (ctypes.c_void_p * n)(*[t.data_ptr() for t in ims]), (ctypes.c_void_p * n)(*[o.data_ptr() for o in outs]), descs, n,
-            _ptr(noise) if n_noise else None, n_noise, _ptr(workspace), ws_bytes, _stream(ims[0])), "locov_augment_images")
+        check(lib.locov_augment_images(_ptrs(ims), _ptrs(outs), descs, n, _ptr(noise) if n_noise else None, n_noise, _ptr(workspace), ws_bytes,
+                                       _stream(ims[0])), "locov_augment_images")
     return outs
 
 
@@ -2940,11 +2950,10 @@ def map_proposals(store_rows: torch.Tensor, row_start: Sequence[int], n_rows: Se
         for lo in range(0, n, IMAGE_BATCH_MAX_IMAGES):
             hi = min(lo + IMAGE_BATCH_MAX_IMAGES, n)
             m, part = hi - lo, slice(offs[lo], offs[hi])
-            ints = lambda vals: (ctypes.c_int * m)(*vals)
             check(lib.locov_map_proposals(
-                _ptr(store_rows), R, dtype, (ctypes.c_int64 * m)(*starts[lo:hi]), ints(counts[lo:hi]),
+                _ptr(store_rows), R, dtype, (ctypes.c_int64 * m)(*starts[lo:hi]), _ints(counts[lo:hi]),
                 (ctypes.c_double * m)(*[float(f[0]) for f in factors[lo:hi]]), (ctypes.c_double * m)(*[float(f[1]) for f in factors[lo:hi]]),
-                ints(flips[lo:hi]), ints([int(s[0]) for s in sizes[lo:hi]]), ints([int(s[1]) for s in sizes[lo:hi]]), m, int(topk), float(thr),
+                _ints(flips[lo:hi]), _ints([int(s[0]) for s in sizes[lo:hi]]), _ints([int(s[1]) for s in sizes[lo:hi]]), m, int(topk), float(thr),
                 *[_ptr(b[part]) for b in bufs[:7]], _ptr(bufs.counts[lo:hi]), _stream(store_rows)), "locov_map_proposals")
     kept = bufs.counts.tolist() if n else []                       # the call's ONE host read
     return [MappedProposals(*[b[o:o + c[0]] for b in bufs[:3]], *[b[o:o + c[1]] for b in bufs[3:7]]) for o, c in zip(offs, kept)]

@@ -268,3 +268,36 @@ def test_without_train_aug_the_bytes_are_the_existing_path(pkg):
     # identity draws through the kernel are a copy of the existing path's bytes
     same = pkg.ops.augment_images([w["image"] for w in want], [sc.draws() for _ in want])
     assert all(torch.equal(a, w["image"]) for a, w in zip(same, want))
+
+
+def test_a_batch_past_one_call_with_a_host_image_in_each_stage(pkg, monkeypatch):
+    """The mapper's own dispatch: IMAGE_BATCH_MAX_IMAGES + 2 images, one outside ops.resize_supported and another outside
+    ops.augment_supported.  Each stage sends 64 and 1 images through its op and one through the host definition, and every
+    image is the CPU mapper's, byte for byte."""
+    import random
+    from locov_amd import data
+    cfg = _cfg("cuda", **ALL_ON)
+    cfg.INPUT.MIN_SIZE_TRAIN = (10, 14, 20)
+    aug = sa.build_complete_augmentation(cfg, True)
+    on_device = data.DatasetMapper(cfg, True, device="cuda", seed=21, train_aug=aug)
+    on_host = data.DatasetMapper(cfg, True, device="cpu", seed=21, train_aug=aug)
+    n, big, wide = pkg.ops.IMAGE_BATCH_MAX_IMAGES + 2, 40, 13
+    rng = np.random.default_rng(8)
+    dicts = [{"image_raw": rng.integers(0, 256, (90, 90, 3) if i == big else (12 + i % 3, 16 + i % 5, 3), dtype=np.uint8), "image_id": i}
+             for i in range(n)]
+    sample = on_device.draw_sample(dicts)
+    sample["short_edge"][big] = 10                                                   # 90 -> 10: 19 taps a side
+    sample["strong"][big] = aug.draw(random.Random(3), 10, 10)
+    sample["strong"][wide] = dict(sample["strong"][wide], blur=True, sigma=3.0)
+    assert not pkg.ops.resize_supported((90, 90), (10, 10), 3) and not pkg.ops.augment_supported(3.0)
+    assert all(pkg.ops.augment_supported(s["sigma"]) for i, s in enumerate(sample["strong"]) if s["blur"] and i != wide)
+    sample["erase_noise"] = on_device.erase_noise(sample).cpu()
+    want = on_host.map_batch(dicts, sample)
+    calls = {"resize_flip_images": [], "augment_images": []}
+    for name, seen in calls.items():
+        monkeypatch.setattr(pkg.ops, name, lambda images, *a, _op=getattr(pkg.ops, name), _seen=seen, **k: (_seen.append(len(images)), _op(images, *a, **k))[1])
+    got = on_device.map_batch(dicts, sample)
+    assert calls == {"resize_flip_images": [64, 1], "augment_images": [64, 1]}
+    assert len(got) == n and tuple(got[big]["image"].shape) == (3, 10, 10)
+    for g, w in zip(got, want):
+        assert g["image"].is_cuda and g["image"].dtype == torch.uint8 and torch.equal(g["image"].cpu(), w["image"])
