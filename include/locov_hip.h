@@ -41,7 +41,7 @@ extern "C" {
  *    locov_preprocess_images, locov_detector_rescale, locov_sgd_step (+ _workspace_bytes),
  *    locov_coco_match (+ _workspace_bytes), locov_coco_accumulate, locov_lvis_match,
  *    locov_resize_flip_images, locov_resize_supported, locov_map_proposals,
- *    locov_augment_images (+ _workspace_bytes), locov_augment_supported */
+ *    locov_augment_images (+ _workspace_bytes), locov_augment_supported, locov_proposal_recall */
 #define LOCOV_ABI_VERSION 8
 
 #define LOCOV_OK 0
@@ -1653,6 +1653,44 @@ int locov_lvis_match(const int *det_offsets, const int *gt_offsets, const uint8_
                      int max_det, const float *det_boxes, const double *gt_boxes, const double *gt_area, const uint8_t *gt_ignore_in,
                      const double *area_ranges_host, int n_areas, const double *iou_thresholds_host, int n_thresholds,
                      uint8_t *det_bits, uint8_t *gt_ignore, void *workspace, int64_t workspace_bytes, locov_stream_t stream);
+
+/* ---- Class-agnostic proposal recall (csrc/proposal_recall.hip): Detectron2's _evaluate_box_proposals ----------------------------
+ * (what its COCOEvaluator / LVISEvaluator, which ovr/evaluation/evaluator.py:47-50 builds, report as "box_proposals": AR, ARs, ARm,
+ * ARl at 100 and at 1000 proposals per image).  Added under ABI version 8.  fp32, each step rounded on its own, and integers: the
+ * outputs equal proposal_recall_host in locov_amd/evaluation.py bit for bit, and two calls give the same bits.
+ *
+ * locov_proposal_recall: the greedy one-to-one matching of every image's proposals to its gts, for every area range and limit.
+ *   prop_offsets, gt_offsets : int32 [n_images + 1], CSR by image.  The entry cannot read them: the kernel clamps every offset into
+ *                 [0, n_prop] / [0, n_gt] and takes a descending pair as an empty image, so no content can send it out of bounds.
+ *   prop_boxes  : fp32 [n_prop, 4] XYXY, an image's proposals in descending objectness (ties in input order); under limit l only
+ *                 the first limits_host[l] of an image take part.  gt_boxes : fp32 [n_gt, 4] XYXY;  gt_area : fp32 [n_gt] (the
+ *                 annotation's own field).  Both box arrays 16-byte aligned.  The boxes are finite.
+ *   gt_skip     : uint8 [n_gt] or NULL: a gt with a nonzero byte is left out before anything else (COCO: iscrowd; LVIS: NULL).
+ *   max_gt_per_image : the caller's statement of the largest gt count of one image; a longer segment is cut to it.
+ *   area_ranges_host : n_areas (1 .. LOCOV_COCO_MAX_AREAS) pairs lo, hi;  limits_host : n_limits (1 ..
+ *                 LOCOV_PROPOSAL_RECALL_MAX_LIMITS) positive ascending ints;  iou_thresholds_host : n_thresholds (1 ..
+ *                 LOCOV_COCO_MAX_THRESHOLDS) floats.  They travel as kernel arguments.
+ *   Per (image, range a, limit l): an image with no gt left after gt_skip, or with no proposal, is SKIPPED: all its counts are 0.
+ *                 Otherwise num_pos = its gts with lo <= area <= hi (fp32), and min(P, num_pos) times: over the unused proposals x
+ *                 unused gts in the range, the largest IoU (select_common.h's box_pairwise_iou), ties to the lowest gt, then to
+ *                 the lowest proposal; the IoU is that step's overlap and both are used from then on.
+ *   gt_overlaps : out fp32 [n_areas * n_limits, n_gt]: row a * n_limits + l holds, in each image's gt segment, the steps' overlaps
+ *                 in match order, then zeros (the maxima never rise: the walk ends at the first 0).  Every element of a segment is
+ *                 written.
+ *   counts      : out int32 [n_images, n_areas * n_limits, n_thresholds + 1]: per threshold t the overlaps >= it (fp32 compare),
+ *                 then num_pos.  Every element is written.  The totals are the integer sum over the images, the caller's.
+ *   One workgroup per (image, range, limit); no atomics on global memory, no host read.  limits_host[last] >
+ *   LOCOV_PROPOSAL_RECALL_MAX_LIMIT, max_gt_per_image > LOCOV_PROPOSAL_RECALL_MAX_GT or n_images * n_areas * n_limits >
+ *   LOCOV_COCO_MAX_BLOCKS: LOCOV_ERR_UNSUPPORTED before any launch.  n_images == 0, or no proposal and no gt: LOCOV_OK, nothing
+ *   launched.  A null pointer, a negative count, limits not ascending, a range with lo > hi, list lengths outside their limits, a
+ *   misaligned pointer: LOCOV_ERR_INVALID_ARG before any HIP call. */
+#define LOCOV_PROPOSAL_RECALL_MAX_LIMIT 2048 /* proposals per image: 16 B each in LDS */
+#define LOCOV_PROPOSAL_RECALL_MAX_GT 1024    /* gts per image (COCO: below 100; LVIS: a few hundred) */
+#define LOCOV_PROPOSAL_RECALL_MAX_LIMITS 4
+int locov_proposal_recall(const int *prop_offsets, const int *gt_offsets, int n_images, int n_prop, int n_gt, int max_gt_per_image,
+                          const float *prop_boxes, const float *gt_boxes, const float *gt_area, const uint8_t *gt_skip,
+                          const float *area_ranges_host, int n_areas, const int *limits_host, int n_limits,
+                          const float *iou_thresholds_host, int n_thresholds, float *gt_overlaps, int *counts, locov_stream_t stream);
 
 #ifdef __cplusplus
 }

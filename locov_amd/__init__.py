@@ -15,7 +15,7 @@ from .proposal_generator import RPN, DefaultAnchorGenerator, StandardRPNHead, bu
 from .backbone import BasicStem, ResNet, build_backbone, build_resnet_backbone  # noqa: F401
 from . import meta_arch  # noqa: F401,E402
 from .meta_arch import (META_ARCH_REGISTRY, DistillOnlyProposalMMSSRCNN, DistillProposalMMSSRCNN, GeneralizedRCNN,  # noqa: F401
-                        OvrRCNN, build_model, detector_postprocess)
+                        OvrRCNN, ProposalNetwork, build_model, detector_postprocess)
 from . import language_backbone, mmss_heads  # noqa: F401,E402
 from .language_backbone import (LANGUAGE_BACKBONES_REGISTRY, BertEmbedding, WordPieceTokenizer,  # noqa: F401,E402
                                 build_bertemb_backbone, build_language_backbone)

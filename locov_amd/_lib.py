@@ -46,6 +46,7 @@ SGD_CLIP_NONE, SGD_CLIP_VALUE, SGD_CLIP_NORM = 0, 1, 2
 COCO_MAX_AREAS, COCO_MAX_THRESHOLDS, COCO_MAX_CAPS, COCO_MAX_RECALL_THRESHOLDS = 4, 16, 3, 256
 COCO_MAX_DET, COCO_MAX_BLOCKS = 4096, 8388608
 LVIS_CELL_NEG, LVIS_CELL_NOT_EXHAUSTIVE = 1, 2
+PROPOSAL_RECALL_MAX_LIMIT, PROPOSAL_RECALL_MAX_GT, PROPOSAL_RECALL_MAX_LIMITS = 2048, 1024, 4
 RESIZE_MAX_TAPS, FLIP_NONE, FLIP_HORIZONTAL, FLIP_VERTICAL = 17, 0, 1, 2
 PROPOSAL_F32, PROPOSAL_F64 = 0, 1
 AUG_OP_BRIGHTNESS, AUG_OP_CONTRAST, AUG_OP_SATURATION, AUG_OP_HUE, AUG_MAX_ERASERS = 1, 2, 3, 4, 3
@@ -261,6 +262,8 @@ SIGNATURES = {
     "locov_map_proposals": (c_int, [_p, c_int64, c_int, POINTER(c_int64), POINTER(c_int), POINTER(c_double), POINTER(c_double),
                                     POINTER(c_int), POINTER(c_int), POINTER(c_int), c_int, c_int, c_float, _p, _p, _p, _p, _p, _p, _p,
                                     _p, _p]),
+    "locov_proposal_recall": (c_int, [_p, _p, c_int, c_int, c_int, c_int, _p, _p, _p, _p, POINTER(c_float), c_int, POINTER(c_int), c_int,
+                                      POINTER(c_float), c_int, _p, _p, _p]),
     "locov_augment_supported": (c_int, [c_float]),
     "locov_augment_images_workspace_bytes": (c_int64, [POINTER(AugmentDesc), c_int]),
     "locov_augment_images": (c_int, [POINTER(c_void_p), POINTER(c_void_p), POINTER(AugmentDesc), c_int, _p, c_int64, _p, c_int64, _p]),

@@ -43,6 +43,7 @@ FILE_FLAGS = {
     "image_batch.hip": ["-ffp-contract=off"],    # ((x - mean) / std and box * scale as the torch ops round them: the bit-identity tests)
     "nms.hip": ["-ffp-contract=off"],          # (select_common.h's box_iou_gt, rounded as in detect.hip / rpn.hip: the bit-identity tests)
     "coco_eval.hip": ["-ffp-contract=off"],    # (fp64 IoU and precision, each step rounded on its own: bit-equal to numpy)
+    "proposal_recall.hip": ["-ffp-contract=off"],  # (select_common.h's box_pairwise_iou, rounded as the torch ops round it: bit-equal overlaps)
     "image_resize.hip": ["-ffp-contract=off"],   # (Pillow's fp64 resampling weights, each step rounded on its own: bit-equal taps)
     "image_augment.hip": ["-ffp-contract=off"],  # (Image.blend's d + f * (x - d) and Pillow's HSV steps, each rounded on its own: bit-equal bytes)
     "proposal_map.hip": ["-ffp-contract=off"],   # (box * factor and size - box as the numpy ops round them, fp32 or fp64: the bit-identity tests)

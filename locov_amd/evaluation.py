@@ -71,6 +71,35 @@ runs ops.lvis_limit (the cap: two stable integer-key sorts and the in-image posi
 cell), calls ops.lvis_match in place of ops.coco_match (the match kernel's other instantiation, which writes the dets of an unlisted
 cell as ignored: the accumulation passes over an ignored det, so precision and recall do not move) and ops.coco_accumulate without
 scores, and summarises precision [T, R, K, A] with the thirteen stats.
+
+Class-agnostic proposal recall, AR@100 / AR@1000 with ARs / ARm / ARl (the public Detectron2's _evaluate_box_proposals and
+COCOEvaluator._eval_box_proposals, which both evaluators above report as "box_proposals" for outputs that hold
+{"proposals": Instances(proposal_boxes, objectness_logits)}; the reference has none of it).  The protocol, fp32 rounded step by
+step and integers:
+
+  * Parameters: limits (100, 1000); the four area ranges above; thresholds = torch.arange(0.5, 0.95 + 1e-5, 0.05, dtype=fp32),
+    formed once on the CPU: its ten fp32 values are what every path compares against.
+  * Ground truth of an image: every annotation of the image, whatever its category, in the order of the annotation file; COCO
+    takes those with iscrowd == 0, LVIS all of them.  Box = fp32(x), fp32(y), fp32(x + w), fp32(y + h), the sums taken in double
+    (BoxMode.convert on Python floats, then torch.as_tensor); area = the annotation's own field rounded to fp32.  A gt is in a
+    range if lo <= area <= hi in fp32 (an area of exactly 1024 is small and medium).
+  * Proposals of an image: stable-sorted by descending objectness_logits, ties in input order (upstream's sort is unstable: a
+    stated difference), the first `limit` kept.  The boxes are finite.
+  * Per (image, range, limit): an image with no gt before the area filter, or with no proposal, is skipped entirely.  Otherwise
+    num_pos += the gts in the range (so an image with gts and no proposal adds nothing: upstream's behaviour).  IoU in fp32 =
+    structures.pairwise_iou = csrc/select_common.h's box_pairwise_iou, each step rounded on its own.  min(P, G) times: among the
+    unused proposals x unused gts the largest IoU, ties to the lowest gt, then to the lowest proposal rank; that IoU is the step's
+    overlap and both are used from then on.  The maxima never rise, so from the first step whose maximum is 0 every overlap is 0;
+    the remaining entries of the image's G overlaps are 0.  (Upstream's literal overlaps.max(dim=0) / max_overlaps.max(dim=0) /
+    -1 marking loop gives the same overlaps: tests/proposal_recall_ref.py restates it.)
+  * Totals: count[a, l, t] = the overlaps >= thresholds[t], an integer; recalls = count.float() / float(num_pos) and ar =
+    recalls.mean(), formed on the host with the same torch CPU expressions on every path; NaN when num_pos == 0.
+  * Results: "AR@100", "ARs@100", "ARm@100", "ARl@100", "AR@1000", ... in that order, each float(ar.item() * 100).
+
+Paths: proposal_recall_host is the definition (CPU tensors, LOCOV_FUSED_COCOEVAL=0, sizes beyond the kernel's limits).  Device
+tensors take proposal_recall_device: ops.proposal_recall (two stable integer sorts, csrc/proposal_recall.hip's one launch, an
+integer sum over the images) with one device-to-host copy, of the totals.  evaluate() adds "box_proposals" behind "bbox" if, and
+only if, process() saw a "proposals" output; evaluator.proposal_eval keeps counts, num_pos, recalls and ar.
 """
 from __future__ import annotations
 
@@ -84,7 +113,8 @@ import torch
 
 from . import _lib
 
-__all__ = ["COCOEvaluator", "LVISEvaluator", "build_evaluator", "inference_on_dataset", "IOU_THRS", "REC_THRS", "AREA_RNG"]
+__all__ = ["COCOEvaluator", "LVISEvaluator", "build_evaluator", "inference_on_dataset", "IOU_THRS", "REC_THRS", "AREA_RNG",
+           "proposal_recall_host", "PROPOSAL_LIMITS", "PROPOSAL_THRS"]
 
 IOU_THRS = np.linspace(.5, .95, 10)
 REC_THRS = np.linspace(0., 1., 101)
@@ -122,18 +152,48 @@ class _GroundTruth:
         self.cat_offsets = self.offsets[::I].astype(np.int64) if I else np.zeros(K + 1, dtype=np.int64)   # [K + 1]
         self._read_more(gt, cats, cat_rank, anns)
         self._device = {}
+        self._annotations = gt.get("annotations", ())                                          # (the loaded list itself: image_index reads it)
+        self._image_index = None
 
     _uploaded = ("box", "area", "crowd", "offsets", "cat_offsets")                             # what on() copies to the device
+    _uploaded_by_image = ("image_offsets", "image_box", "image_area", "image_skip")            # ... and with by_image, once asked for
+    proposals_skip_crowd = True                                                                # COCO's proposal recall leaves crowd gts out
 
     def _read_more(self, gt, cats, cat_rank, anns):
         """What a protocol reads beyond the arrays above, from the loaded dict, its categories in ascending id, their ranks and the
         annotations in cell order (_LVISGroundTruth's fields)."""
 
-    def on(self, device):
-        """The device copies of the arrays, made once per device."""
+    def image_index(self):
+        """The annotations by image, for the proposal recall (module docstring): every annotation of an image of the ground truth,
+        whatever its category, in the order of the annotation file.  Built on the first call, so a user who never feeds proposals
+        pays nothing.  -> dict(offsets int32 [I + 1] (CSR by image rank), box fp32 [G, 4] XYXY (x + w and y + h summed in double,
+        then rounded once), area fp32 [G] (the annotation's own field), crowd uint8 [G], skip uint8 [G] or None (the gts the
+        protocol leaves out: crowd under COCO, none under LVIS), max_per_image)."""
+        if self._image_index is None:
+            anns = [a for a in self._annotations if a["image_id"] in self.image_rank]
+            rank = np.array([self.image_rank[a["image_id"]] for a in anns], dtype=np.int64)
+            order = np.argsort(rank, kind="stable")
+            anns, rank = [anns[i] for i in order], rank[order]
+            xywh = np.array([[float(v) for v in a["bbox"]] for a in anns], dtype=np.float64).reshape(-1, 4)
+            box = np.stack([xywh[:, 0], xywh[:, 1], xywh[:, 0] + xywh[:, 2], xywh[:, 1] + xywh[:, 3]], axis=1).astype(np.float32)
+            crowd = np.array([1 if a.get("iscrowd", 0) else 0 for a in anns], dtype=np.uint8)
+            offsets = np.searchsorted(rank, np.arange(self.n_images + 1, dtype=np.int64), side="left").astype(np.int32)
+            self._image_index = dict(offsets=offsets, box=box, area=np.array([a["area"] for a in anns], dtype=np.float64).astype(np.float32),
+                                     crowd=crowd, skip=crowd if self.proposals_skip_crowd else None,
+                                     max_per_image=int(np.diff(offsets.astype(np.int64)).max()) if self.n_images else 0)
+        return self._image_index
+
+    def on(self, device, by_image: bool = False):
+        """The device copies of the arrays, made once per device; by_image: image_index()'s arrays too, as image_offsets, image_box,
+        image_area and image_skip (None where the protocol leaves no gt out)."""
         d = self._device.get(device)
         if d is None:
             d = self._device[device] = {k: torch.from_numpy(np.ascontiguousarray(getattr(self, k))).to(device) for k in self._uploaded}
+        if by_image and "image_offsets" not in d:
+            index = self.image_index()
+            for k in self._uploaded_by_image:
+                v = index[k[len("image_"):]]
+                d[k] = torch.from_numpy(np.ascontiguousarray(v)).to(device) if v is not None else None
         return d
 
 
@@ -390,13 +450,112 @@ def evaluate_device(gt: _GroundTruth, img_rank, cls, score, boxes, max_dets, mar
     return _evaluate_device(gt, img_rank, cls, score, boxes, max_dets, False, mark)
 
 
+# ---- class-agnostic proposal recall (module docstring) ------------------------------------------------------------------------------
+PROPOSAL_LIMITS = (100, 1000)
+PROPOSAL_AREA_NAMES = ("", "s", "m", "l")                                                      # AR, ARs, ARm, ARl: AREA_RNG's rows
+PROPOSAL_AREA_RNG = AREA_RNG.astype(np.float32)
+PROPOSAL_THRS = torch.arange(0.5, 0.95 + 1e-5, 0.05, dtype=torch.float32).numpy()              # formed once, on the CPU
+
+
+def proposal_order_host(img_rank, logits):
+    """int64 [N]: the proposals by image rank, inside an image by descending objectness, ties in input order."""
+    p = np.argsort(-np.asarray(logits, dtype=np.float64), kind="stable")
+    return p[np.argsort(np.asarray(img_rank, dtype=np.int64)[p], kind="stable")]
+
+
+def proposal_recall_host(index, img_rank, logits, boxes, limits=PROPOSAL_LIMITS, area_rng=PROPOSAL_AREA_RNG, thrs=PROPOSAL_THRS):
+    """The definition of the proposal recall.  index: _GroundTruth.image_index(); img_rank int64 [N], logits [N], boxes fp32 [N, 4]
+    XYXY: the proposals of every processed image, in any order.
+    -> dict(counts int64 [A, L, T], num_pos int64 [A, L], gt_overlaps fp32 [A * L, G]: per (range, limit) row, in each image's gt
+    segment, the steps' overlaps in match order, then zeros)."""
+    from .structures import Boxes, pairwise_iou
+    img_rank = np.asarray(img_rank, dtype=np.int64)
+    boxes = np.asarray(boxes, dtype=np.float32).reshape(-1, 4)
+    area_rng, thrs = np.asarray(area_rng, dtype=np.float32).reshape(-1, 2), np.asarray(thrs, dtype=np.float32)
+    A, L, T = len(area_rng), len(limits), len(thrs)
+    perm = proposal_order_host(img_rank, logits)
+    img_rank, boxes = img_rank[perm], boxes[perm]
+    offsets, gt_box, gt_area, skip = index["offsets"], index["box"], index["area"], index["skip"]
+    counted = np.ones(len(gt_area), dtype=bool) if skip is None else skip == 0
+    overlaps = np.zeros((A * L, len(gt_area)), dtype=np.float32)
+    counts, num_pos = np.zeros((A, L, T), dtype=np.int64), np.zeros((A, L), dtype=np.int64)
+    images, first = np.unique(img_rank, return_index=True)
+    last = np.append(first[1:], len(img_rank))
+    for i, p0, p1 in zip(images, first, last):                                                 # (an image with no proposal is not here)
+        g0, g1 = int(offsets[i]), int(offsets[i + 1])
+        if not counted[g0:g1].any():
+            continue                                                                           # no gt before the area filter: skipped
+        for a in range(A):
+            cols = np.nonzero(counted[g0:g1] & (gt_area[g0:g1] >= area_rng[a, 0]) & (gt_area[g0:g1] <= area_rng[a, 1]))[0]
+            num_pos[a] += len(cols)
+            if len(cols) == 0:
+                continue
+            full = pairwise_iou(Boxes(torch.from_numpy(gt_box[g0:g1][cols])), Boxes(torch.from_numpy(boxes[p0:p1]))).numpy()
+            for l, limit in enumerate(limits):
+                iou = full[:, :limit].copy()                                                   # [gts in the range, first `limit` proposals]
+                row = overlaps[a * L + l]
+                for step in range(min(iou.shape)):
+                    g, p = np.unravel_index(np.argmax(iou), iou.shape)                         # (the first maximum: lowest gt, then lowest proposal)
+                    v = iou[g, p]
+                    if not v > 0:
+                        break                                                                  # the maxima never rise: the rest stay 0
+                    row[g0 + step] = v
+                    iou[g, :] = -1
+                    iou[:, p] = -1
+                counts[a, l] += (row[g0:g1, None] >= thrs[None, :]).sum(axis=0)
+    return dict(counts=counts, num_pos=num_pos, gt_overlaps=overlaps)
+
+
+def proposal_totals(counts, num_pos):
+    """recalls and AR from the integer totals, with the torch CPU expressions every path shares: recalls = counts.float() /
+    float(num_pos), ar = recalls.mean(); NaN where num_pos == 0.
+    -> dict(counts int64 [A, L, T], num_pos int64 [A, L], recalls fp32 [A, L, T], ar fp32 [A, L])."""
+    counts, num_pos = np.asarray(counts, dtype=np.int64), np.asarray(num_pos, dtype=np.int64)
+    A, L, T = counts.shape
+    recalls, ar = np.zeros((A, L, T), dtype=np.float32), np.zeros((A, L), dtype=np.float32)
+    for a in range(A):
+        for l in range(L):
+            r = torch.from_numpy(counts[a, l]).float() / float(num_pos[a, l]) if num_pos[a, l] else torch.full((T,), float("nan"))
+            recalls[a, l], ar[a, l] = r.numpy(), r.mean().item()
+    return dict(counts=counts, num_pos=num_pos, recalls=recalls, ar=ar)
+
+
+def derive_proposal_results(ev, limits=PROPOSAL_LIMITS):
+    """AR@100, ARs@100, ARm@100, ARl@100, AR@1000, ... from proposal_totals' dict."""
+    return OrderedDict((f"AR{name}@{limit}", float(ev["ar"][a, l].item() * 100)) for l, limit in enumerate(limits)
+                       for a, name in enumerate(PROPOSAL_AREA_NAMES))
+
+
+def proposal_device_supported(gt: _GroundTruth, n_prop: int, limits) -> bool:
+    """Sizes inside locov_proposal_recall's stated limits (beyond them it answers LOCOV_ERR_UNSUPPORTED: the host path is taken)."""
+    index = gt.image_index()
+    return (len(limits) <= _lib.PROPOSAL_RECALL_MAX_LIMITS and limits[-1] <= _lib.PROPOSAL_RECALL_MAX_LIMIT
+            and index["max_per_image"] <= _lib.PROPOSAL_RECALL_MAX_GT and 0 < n_prop < 2 ** 31 - 1 and len(index["area"]) < 2 ** 31 - 1
+            and 0 < gt.n_images * len(PROPOSAL_AREA_RNG) * len(limits) <= _lib.COCO_MAX_BLOCKS)
+
+
+def proposal_recall_device(gt: _GroundTruth, img_rank, logits, boxes, limits=PROPOSAL_LIMITS, mark=None):
+    """The same totals from device tensors: two stable integer sorts, one launch, an integer sum over the images and ONE copy to
+    the host, of the A * L * (T + 1) totals.  mark: as in _evaluate_device.  -> (counts int64 [A, L, T], num_pos int64 [A, L])."""
+    from . import ops
+    g = gt.on(boxes.device, by_image=True)
+    A, L, T = len(PROPOSAL_AREA_RNG), len(limits), len(PROPOSAL_THRS)
+    totals, _ = ops.proposal_recall(img_rank, logits, boxes, g["image_offsets"], g["image_box"], g["image_area"], g["image_skip"],
+                                    gt.image_index()["max_per_image"], PROPOSAL_AREA_RNG, limits, PROPOSAL_THRS, mark=mark)
+    host = totals.cpu().numpy().reshape(A, L, T + 1)                          # the one device-to-host copy
+    if mark is not None:
+        mark("copy")
+    return host[:, :, :T], host[:, :, T]
+
+
 class COCOEvaluator:
     """Box AP under the COCO protocol (module docstring), with the reference's AP50-seen / AP50-unseen.
 
     gt: a COCO-format dict or the path of its JSON (images, annotations, categories).  class_names: one name per category in
     ascending category id (default: the categories' own names).  seen_names / unseen_names: the two lists the reference imports
     from its dataset file.  max_dets: an ascending tuple of 1-3 caps.  device: where evaluate() runs (default: where the
-    processed tensors are)."""
+    processed tensors are).  Outputs that hold "proposals" are scored too, as "box_proposals" (the proposal recall of the module
+    docstring, at proposal_limits); .proposal_eval holds its totals."""
 
     def __init__(self, gt, class_names: Optional[Sequence[str]] = None, seen_names: Sequence[str] = (), unseen_names: Sequence[str] = (),
                  max_dets: Sequence[int] = (1, 10, 100), device=None):
@@ -413,20 +572,35 @@ class COCOEvaluator:
         self.eval = None
         self.reset()
 
+    proposal_limits = PROPOSAL_LIMITS                  # (an ascending tuple; an instance may set its own before evaluate())
+
     def reset(self) -> None:
         self._ranks, self._counts, self._boxes, self._scores, self._classes = [], [], [], [], []
+        self._prop_ranks, self._prop_counts, self._prop_boxes, self._prop_logits = [], [], [], []
         self.eval = None
+        self.proposal_eval = None
 
     def process(self, inputs, outputs) -> None:
-        """inputs[i]["image_id"], outputs[i]["instances"] (pred_boxes XYXY, scores, pred_classes).  The tensors are kept where
-        they are; nothing is read to the host (the image id is host data)."""
+        """inputs[i]["image_id"], outputs[i]["instances"] (pred_boxes XYXY, scores, pred_classes) and / or outputs[i]["proposals"]
+        (proposal_boxes XYXY, objectness_logits).  The tensors are kept where they are; nothing is read to the host (the image id
+        is host data)."""
         for inp, out in zip(inputs, outputs):
-            if "instances" not in out:
+            if "instances" not in out and "proposals" not in out:
                 continue
-            inst = out["instances"]
             iid = inp["image_id"]
             if iid not in self._gt.image_rank:
                 raise KeyError(f"image id {iid!r} is not in the ground truth")
+            if "proposals" in out:
+                prop = out["proposals"]
+                boxes = prop.proposal_boxes
+                boxes = boxes.tensor if hasattr(boxes, "tensor") else boxes
+                self._prop_ranks.append(self._gt.image_rank[iid])
+                self._prop_counts.append(int(boxes.shape[0]))
+                self._prop_boxes.append(boxes.detach().reshape(-1, 4))
+                self._prop_logits.append(prop.objectness_logits.detach().reshape(-1))
+            if "instances" not in out:
+                continue
+            inst = out["instances"]
             boxes = inst.pred_boxes
             boxes = boxes.tensor if hasattr(boxes, "tensor") else boxes
             self._ranks.append(self._gt.image_rank[iid])
@@ -435,15 +609,42 @@ class COCOEvaluator:
             self._scores.append(inst.scores.detach().reshape(-1))
             self._classes.append(inst.pred_classes.detach().reshape(-1))
 
-    def _gathered(self, device):
-        def cat(parts, dtype):
-            if len({(p.device, p.dtype) for p in parts}) == 1:             # one concatenation, then one move / conversion
-                return torch.cat(parts).to(device=device, dtype=dtype)
-            return torch.cat([p.to(device=device, dtype=dtype) for p in parts])
+    @staticmethod
+    def _cat(parts, device, dtype):
+        if len({(p.device, p.dtype) for p in parts}) == 1:                 # one concatenation, then one move / conversion
+            return torch.cat(parts).to(device=device, dtype=dtype)
+        return torch.cat([p.to(device=device, dtype=dtype) for p in parts])
 
-        boxes, score, cls = cat(self._boxes, torch.float32), cat(self._scores, torch.float64), cat(self._classes, torch.int64)
+    def _gathered(self, device):
+        cat = self._cat
+        boxes, score, cls = cat(self._boxes, device, torch.float32), cat(self._scores, device, torch.float64), cat(self._classes, device, torch.int64)
         img_rank = torch.from_numpy(np.repeat(np.asarray(self._ranks, dtype=np.int64), self._counts)).to(device)
         return img_rank, cls, score, boxes
+
+    def _gathered_proposals(self, device):
+        boxes, logits = self._cat(self._prop_boxes, device, torch.float32), self._cat(self._prop_logits, device, torch.float64)
+        img_rank = torch.from_numpy(np.repeat(np.asarray(self._prop_ranks, dtype=np.int64), self._prop_counts)).to(device)
+        return img_rank, logits, boxes
+
+    def _evaluate_proposals(self, mark=None):
+        """The proposal recall of what process() saw -> "box_proposals"' dict; the totals stay on self.proposal_eval (counts,
+        num_pos, recalls, ar).  The path is chosen as evaluate() chooses the AP's."""
+        limits = tuple(int(v) for v in self.proposal_limits)
+        if not limits or limits[0] < 1 or any(b <= a for a, b in zip(limits, limits[1:])):
+            raise ValueError(f"proposal_limits must be an ascending tuple of positive limits, got {limits}")
+        n = sum(self._prop_counts)
+        device = self._device or self._prop_boxes[0].device
+        on_device = device.type == "cuda" and _fused() and proposal_device_supported(self._gt, n, limits)
+        img_rank, logits, boxes = self._gathered_proposals(device if on_device else torch.device("cpu"))
+        if mark is not None:
+            mark("gather")
+        if on_device:
+            counts, num_pos = proposal_recall_device(self._gt, img_rank, logits, boxes, limits, mark)
+        else:
+            host = proposal_recall_host(self._gt.image_index(), img_rank.numpy(), logits.numpy(), boxes.numpy(), limits)
+            counts, num_pos = host["counts"], host["num_pos"]
+        self.proposal_eval = proposal_totals(counts, num_pos)
+        return derive_proposal_results(self.proposal_eval, limits)
 
     # the three places where a protocol differs; LVISEvaluator overrides them
     def _evaluate_host(self, img_rank, cls, score, boxes):
@@ -455,16 +656,25 @@ class COCOEvaluator:
     def _derive_results(self, ev):
         return derive_results(ev, self._class_names, self._seen, self._unseen)
 
-    def evaluate(self):
+    def _evaluate_bbox(self):
         n = sum(self._counts)
         if n == 0:
             self.eval = None
-            return OrderedDict(bbox=self._derive_results(None))
+            return self._derive_results(None)
         device = self._device or self._boxes[0].device
         on_device = device.type == "cuda" and _fused() and device_supported(self._gt, n, self.max_dets)
         tensors = self._gathered(device if on_device else torch.device("cpu"))
         self.eval = self._evaluate_device(*tensors) if on_device else self._evaluate_host(*(t.numpy() for t in tensors))
-        return OrderedDict(bbox=self._derive_results(self.eval))
+        return self._derive_results(self.eval)
+
+    def evaluate(self):
+        """"bbox" always; "box_proposals" behind it if, and only if, process() saw at least one "proposals" output."""
+        results = OrderedDict(bbox=self._evaluate_bbox())
+        if self._prop_counts:
+            results["box_proposals"] = self._evaluate_proposals()
+        else:
+            self.proposal_eval = None
+        return results
 
 
 def inference_on_dataset(model, data_loader, evaluator):
@@ -493,6 +703,7 @@ class _LVISGroundTruth(_GroundTruth):
     neg / not-exhaustive lists, and the frequency groups as arrays of category ranks.  `crowd` is kept but never read."""
 
     _uploaded = _GroundTruth._uploaded + ("ignore", "cell_flags")
+    proposals_skip_crowd = False                                                               # LVIS's proposal recall takes every annotation
 
     def _read_more(self, gt, cats, cat_rank, anns):
         I, K = self.n_images, self.n_categories

@@ -28,8 +28,8 @@ from .structures import ImageList, boxes_class_of, cat_rows
 
 META_ARCH_REGISTRY = Registry("META_ARCH")
 
-__all__ = ["META_ARCH_REGISTRY", "GeneralizedRCNN", "OvrRCNN", "DistillProposalMMSSRCNN", "DistillOnlyProposalMMSSRCNN", "build_model",
-           "detector_postprocess"]
+__all__ = ["META_ARCH_REGISTRY", "GeneralizedRCNN", "ProposalNetwork", "OvrRCNN", "DistillProposalMMSSRCNN", "DistillOnlyProposalMMSSRCNN",
+           "build_model", "detector_postprocess"]
 
 
 def build_model(cfg, **kwargs) -> nn.Module:
@@ -153,40 +153,87 @@ class GeneralizedRCNN(nn.Module):
         return ImageList.from_tensors(images, divisibility, padding_constraints=constraints)
 
     @staticmethod
-    def _postprocess(instances, batched_inputs: List[Dict[str, Any]], image_sizes: Sequence[Tuple[int, int]]):
+    def _postprocess(instances, batched_inputs: List[Dict[str, Any]], image_sizes: Sequence[Tuple[int, int]], *,
+                     box_field: str = "pred_boxes", output_key: str = "instances"):
         """The results rescaled to each input's "height" / "width" (default: the image's own size).  fp32 device pred_boxes of at
         most 64 images: one launch and one read of the counts for the batch; an image that loses no box keeps its other fields
-        untouched, the others gather theirs by the kept rows.  Otherwise the per-image torch function."""
+        untouched, the others gather theirs by the kept rows (in their order: the compaction keeps it).  Otherwise the per-image
+        torch function.  box_field / output_key: the Instances field that holds the boxes and the key of the result dicts
+        (ProposalNetwork: "proposal_boxes" under "proposals")."""
         instances = list(instances)
         out_sizes = [(inp.get("height", size[0]), inp.get("width", size[1])) for inp, size in zip(batched_inputs, image_sizes)]
-        if not _kernel_postprocess_ok(instances, out_sizes):
-            return [{"instances": detector_postprocess(r, h, w)} for r, (h, w) in zip(instances, out_sizes)]
+        if not _kernel_postprocess_ok(instances, out_sizes, box_field):
+            return [{output_key: detector_postprocess(r, h, w)} for r, (h, w) in zip(instances, out_sizes)]
         inst_cls, box_cls = boxes_class_of(instances)
         sizes = [len(r) for r in instances]
-        boxes = cat_rows([r.pred_boxes.tensor for r in instances])
+        boxes = cat_rows([r.get(box_field).tensor for r in instances])
         out_boxes, src, counts = ops.detector_rescale(boxes, sizes, [r.image_size for r in instances], out_sizes)
         processed, lo = [], 0
         for r, n, kept, size in zip(instances, sizes, counts, out_sizes):
             fields = dict(r.get_fields())
             if kept != n:
                 rows = src[lo:lo + kept]
-                fields = {k: v[rows] for k, v in fields.items() if k != "pred_boxes"}
-            fields["pred_boxes"] = box_cls(out_boxes[lo:lo + kept])
-            processed.append({"instances": inst_cls(size, **fields)})
+                fields = {k: v[rows] for k, v in fields.items() if k != box_field}
+            fields[box_field] = box_cls(out_boxes[lo:lo + kept])
+            processed.append({output_key: inst_cls(size, **fields)})
             lo += n
         return processed
 
 
-def _kernel_postprocess_ok(instances, out_sizes) -> bool:
+def _kernel_postprocess_ok(instances, out_sizes, box_field: str = "pred_boxes") -> bool:
     if not (0 < len(instances) <= ops.IMAGE_BATCH_MAX_IMAGES):
         return False
     for r, (h, w) in zip(instances, out_sizes):
-        if not r.has("pred_boxes") or not isinstance(h, numbers.Integral) or not isinstance(w, numbers.Integral):
+        if not r.has(box_field) or not isinstance(h, numbers.Integral) or not isinstance(w, numbers.Integral):
             return False
-        t = getattr(r.pred_boxes, "tensor", None)
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.device == instances[0].pred_boxes.tensor.device):
+        t = getattr(r.get(box_field), "tensor", None)
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.device == instances[0].get(box_field).tensor.device):
             return False
     return True
+
+
+@META_ARCH_REGISTRY.register()
+class ProposalNetwork(nn.Module):
+    """[D2-upstream] ProposalNetwork, the RPN-only meta-architecture: backbone -> proposal generator.  Training returns the
+    proposal losses; evaluation [{"proposals": Instances(proposal_boxes, objectness_logits)}] per image, rescaled to the input's
+    "height" / "width", in descending objectness -- what the evaluators score as "box_proposals".  state_dict() holds backbone.*
+    and proposal_generator.* only.  Both ends are GeneralizedRCNN's: one launch for the batch's preprocessing, one launch and one
+    read of the counts for the rescaling."""
+
+    @configurable
+    def __init__(self, *, backbone: nn.Module, proposal_generator: nn.Module, pixel_mean: Sequence[float], pixel_std: Sequence[float]):
+        super().__init__()
+        self.backbone = backbone
+        self.proposal_generator = proposal_generator
+        self.register_buffer("pixel_mean", torch.tensor(pixel_mean, dtype=torch.float32).view(-1, 1, 1), persistent=False)
+        self.register_buffer("pixel_std", torch.tensor(pixel_std, dtype=torch.float32).view(-1, 1, 1), persistent=False)
+        assert self.pixel_mean.shape == self.pixel_std.shape, f"{self.pixel_mean} and {self.pixel_std} have different shapes!"
+        self._pixel_stats = ([float(v) for v in pixel_mean], [float(v) for v in pixel_std])    # (host copies: the kernel's arguments)
+
+    @classmethod
+    def from_config(cls, cfg) -> Dict[str, Any]:
+        backbone = build_backbone(cfg)
+        return {"backbone": backbone, "proposal_generator": build_proposal_generator(cfg, backbone.output_shape()),
+                "pixel_mean": cfg.MODEL.PIXEL_MEAN, "pixel_std": cfg.MODEL.PIXEL_STD}
+
+    @property
+    def device(self) -> torch.device:
+        return self.pixel_mean.device
+
+    _kernel_preprocess_ok = GeneralizedRCNN._kernel_preprocess_ok
+    preprocess_image = GeneralizedRCNN.preprocess_image
+
+    def forward(self, batched_inputs: List[Dict[str, Any]]):
+        """Training: the proposal generator's losses.  Evaluation: [{"proposals": Instances}] per image."""
+        images = self.preprocess_image(batched_inputs)
+        features = self.backbone(images.tensor)
+        gt_instances = None
+        if self.training and "instances" in batched_inputs[0]:
+            gt_instances = [x["instances"].to(self.device) for x in batched_inputs]
+        proposals, proposal_losses = self.proposal_generator(images, features, gt_instances)
+        if self.training:
+            return proposal_losses
+        return GeneralizedRCNN._postprocess(proposals, batched_inputs, images.image_sizes, box_field="proposal_boxes", output_key="proposals")
 
 
 @META_ARCH_REGISTRY.register()

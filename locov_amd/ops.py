@@ -3334,3 +3334,54 @@ def lvis_match(det_offsets: torch.Tensor, gt_offsets: torch.Tensor, cell_flags: 
     _lib.LVIS_CELL_NOT_EXHAUSTIVE) and gt_ignore_in uint8 [G] (the annotation's ignore field) in place of gt_crowd."""
     return _match("lvis_match", det_offsets, gt_offsets, cell_flags, det_boxes, gt_boxes, gt_area, gt_ignore_in, area_ranges, iou_thresholds,
                   max_det)
+
+
+# --------------------------------------------------------------------------------------
+# Class-agnostic proposal recall (csrc/proposal_recall.hip); composed by locov_amd/evaluation.py, whose docstring states the protocol.
+def proposal_recall(img_rank: torch.Tensor, logits: torch.Tensor, boxes: torch.Tensor, gt_offsets: torch.Tensor, gt_boxes: torch.Tensor,
+                    gt_area: torch.Tensor, gt_skip: Optional[torch.Tensor], max_gt_per_image: int, area_ranges, limits: Sequence[int],
+                    iou_thresholds, mark=None):
+    """locov_proposal_recall behind its ordering: -> (totals int64 [A * L, T + 1]: per (range, limit) the overlaps >= each threshold,
+    then num_pos, summed over the images; gt_overlaps fp32 [A * L, G]), both on the device.  No host read.
+    img_rank int64 [N], logits fp64 [N], boxes fp32 [N, 4] XYXY: the proposals of every processed image in any order; they are put
+    by image rank, inside an image by descending logit with ties in input order, by two stable sorts on integer keys (as
+    lvis_limit orders its dets).  gt_offsets int32 [I + 1], gt_boxes fp32 [G, 4] XYXY, gt_area fp32 [G], gt_skip uint8 [G] or None:
+    the ground truth by image.  area_ranges [A][2], limits [L] (ascending) and iou_thresholds [T] are host values, rounded to
+    fp32.  mark: called with "orderings", "launch" and "sum" after each step (tools/time_evaluation.py synchronises there)."""
+    import numpy as np
+    step = mark if mark is not None else (lambda name: None)
+    boxes = _dev(boxes, "boxes")
+    logits = _dev(logits, "logits", torch.float64)
+    img_rank = _dev(img_rank, "img_rank", torch.int64)
+    gt_offsets = _dev(gt_offsets, "gt_offsets", torch.int32)
+    gt_boxes, gt_area = _dev(gt_boxes, "gt_boxes"), _dev(gt_area, "gt_area")
+    if gt_skip is not None:
+        gt_skip = _dev(gt_skip, "gt_skip", torch.uint8)
+    I, N, G = gt_offsets.shape[0] - 1, boxes.shape[0], gt_area.shape[0]
+    if (I < 0 or boxes.shape != (N, 4) or logits.shape != (N,) or img_rank.shape != (N,) or gt_boxes.shape != (G, 4)
+            or (gt_skip is not None and gt_skip.shape != (G,))):
+        raise ValueError("proposal_recall: img_rank [N], logits [N], boxes [N,4], gt_offsets [I + 1], gt_boxes [G,4], gt_area [G], gt_skip [G]")
+    ar = np.ascontiguousarray(area_ranges, dtype=np.float32).reshape(-1, 2)
+    th = np.ascontiguousarray(iou_thresholds, dtype=np.float32).reshape(-1)
+    lim = np.ascontiguousarray(limits, dtype=np.int32).reshape(-1)
+    A, L, T = len(ar), len(lim), len(th)
+    dev = boxes.device
+    p1 = torch.sort(_descending_key(logits), stable=True).indices
+    image, p2 = torch.sort(img_rank[p1], stable=True)
+    prop_offsets = torch.searchsorted(image, torch.arange(I + 1, dtype=torch.int64, device=dev)).to(torch.int32)
+    sorted_boxes = boxes[p1[p2]].contiguous()
+    step("orderings")
+    overlaps = torch.empty((A * L, G), dtype=torch.float32, device=dev)
+    counts = torch.empty((I, A * L, T + 1), dtype=torch.int32, device=dev)        # (the launch writes every element; with no image,
+    if I == 0 or (N == 0 and G == 0):                                             # or no proposal and no gt, nothing is launched)
+        counts.zero_()
+    fp, ip = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int)
+    with torch.cuda.device(dev):
+        check(_lib.load().locov_proposal_recall(_ptr(prop_offsets), _ptr(gt_offsets), I, N, G, int(max_gt_per_image), _ptr(sorted_boxes),
+                                                _ptr(gt_boxes), _ptr(gt_area), _ptr(gt_skip), ar.ctypes.data_as(fp), A,
+                                                lim.ctypes.data_as(ip), L, th.ctypes.data_as(fp), T, _ptr(overlaps), _ptr(counts),
+                                                _stream(boxes)), "locov_proposal_recall")
+    step("launch")
+    totals = counts.sum(0)
+    step("sum")
+    return totals, overlaps

@@ -2,7 +2,7 @@
 synthetic sets of COCO-val / LVIS-val size.
 
     timeout -k 10 900 python tools/time_evaluation.py [--protocol coco|lvis] [--images 5000] [--categories 80 1203] [--repeats 7]
-                                                      [--warmup 2] [--host-repeats 2] [--out records.json]
+                                                      [--warmup 2] [--host-repeats 2] [--proposals P] [--out records.json]
 
 A set: `images` images, `categories` categories, 7 gts and 100 dets per image from a seed (60 dets are jittered copies of the
 image's gts with their class, 40 are random boxes of random classes; 5 % of the gts are crowd; fp32 scores).  The dets are fed as
@@ -18,7 +18,12 @@ path's evaluate() `host-repeats` times; and whether the two paths' arrays are eq
 ignore = 1), 6 neg_category_ids and 1 not_exhaustive_category_id (drawn from all categories, so now and then a positive one), and
 300 dets (120 jittered copies of the image's gts with their class, 60 random boxes of its negative categories, 120 random boxes of
 random classes, nearly all of them unlisted); 320 dets are fed for every tenth image, so the cap of 300 acts; the categories are
-rare / common / frequent 337 : 461 : 405, as in LVIS v1.  The steps then start with the cap (ops.lvis_limit)."""
+rare / common / frequent 337 : 461 : 405, as in LVIS v1.  The steps then start with the cap (ops.lvis_limit).
+
+--proposals P: the proposal recall ("box_proposals") instead of the AP: the same gts (7 per image under coco, 11 under lvis) and P
+proposals per image -- three jittered copies of every gt, the rest random boxes, normal logits -- fed as {"proposals": Instances}.
+evaluate() on the device and the host definition beside it, the marks gather / orderings / launch / sum / copy, and whether the
+totals, recalls and ARs of the two paths are equal bit for bit (asserted)."""
 from __future__ import annotations
 
 import argparse
@@ -168,8 +173,96 @@ def measure(n_images, n_categories, args, dev):
     return rec
 
 
+def synthetic_proposals(gt, n_proposals, seed=1, copies=3):
+    """-> per image (image_id, boxes fp32 [P, 4] XYXY, logits fp32 [P]): `copies` jittered copies of each of the image's gts (as many
+    as fit), the rest random boxes; normal logits, the copies' a little higher."""
+    rng = np.random.default_rng(seed)
+    by_image = {}
+    for a in gt["annotations"]:
+        by_image.setdefault(a["image_id"], []).append(a["bbox"])
+    per_image = []
+    for im in gt["images"]:
+        g = np.array(by_image.get(im["id"], []), dtype=np.float64).reshape(-1, 4)
+        near = np.repeat(g, copies, axis=0)[:n_proposals]
+        bxy = near[:, :2] + rng.normal(0, 4, size=(len(near), 2))
+        bwh = near[:, 2:] * rng.uniform(0.8, 1.25, size=(len(near), 2))
+        m = n_proposals - len(near)
+        x1y1, wh = np.concatenate([bxy, rng.uniform(0, 400, size=(m, 2))]), np.concatenate([bwh, rng.uniform(8, 200, size=(m, 2))])
+        logits = rng.normal(0, 2, size=n_proposals) + np.concatenate([np.full(len(near), 1.0), np.zeros(m)])
+        per_image.append((im["id"], np.concatenate([x1y1, x1y1 + wh], axis=1).astype(np.float32), logits.astype(np.float32)))
+    return per_image
+
+
+def feed_proposals(evaluator, per_image, device):
+    from locov_amd.structures import Boxes, Instances
+    evaluator.reset()
+    for img, boxes, logits in per_image:
+        inst = Instances((480, 640))
+        inst.proposal_boxes = Boxes(torch.from_numpy(boxes).to(device))
+        inst.objectness_logits = torch.from_numpy(logits).to(device)
+        evaluator.process([dict(image_id=img)], [dict(proposals=inst)])
+
+
+def measure_proposals(n_images, args, dev):
+    """--proposals P: the "box_proposals" part of evaluate() (nothing else is fed, so "bbox" costs nothing), with the marks of
+    COCOEvaluator._evaluate_proposals: gather (the concatenation), orderings (two stable sorts and a search), launch, sum, copy."""
+    from locov_amd.evaluation import COCOEvaluator, LVISEvaluator
+    t0 = time.perf_counter()
+    if args.protocol == "lvis":
+        gt, _ = synthetic_lvis(n_images, 1203, dets_per_image=180)
+        on_dev, on_host = LVISEvaluator(gt), LVISEvaluator(gt)
+    else:
+        gt, _ = synthetic(n_images, 80, dets_per_image=60)
+        on_dev, on_host = COCOEvaluator(gt), COCOEvaluator(gt)
+    per_image = synthetic_proposals(gt, args.proposals)
+    rec = {"protocol": args.protocol, "images": n_images, "proposals": sum(len(p[2]) for p in per_image), "gts": len(gt["annotations"]),
+           "build_s": time.perf_counter() - t0}
+    feed_proposals(on_dev, per_image, dev)
+    wall = []
+    for it in range(args.warmup + args.repeats):
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        res = on_dev.evaluate()
+        torch.cuda.synchronize(dev)
+        if it >= args.warmup:
+            wall.append((time.perf_counter() - t0) * 1e3)
+    rec["device_evaluate"] = spread(wall)
+    stages = []
+    for _ in range(args.warmup + args.repeats):
+        t, marks = {}, [time.perf_counter()]
+
+        def mark(name):
+            torch.cuda.synchronize(dev)
+            marks.append(time.perf_counter())
+            t[name] = (marks[-1] - marks[-2]) * 1e3
+
+        on_dev._evaluate_proposals(mark=mark)
+        stages.append(t)
+    stages = stages[args.warmup:]
+    rec["device_stages_ms"] = {k: float(np.median([s[k] for s in stages])) for k in stages[0]}
+    total = sum(rec["device_stages_ms"].values())
+    rec["device_stage_share"] = {k: v / total for k, v in rec["device_stages_ms"].items()}
+    print(json.dumps({"proposals, device": rec}), flush=True)
+    feed_proposals(on_host, per_image, "cpu")
+    host = []
+    for _ in range(args.host_repeats):
+        t0 = time.perf_counter()
+        res_host = on_host.evaluate()
+        host.append((time.perf_counter() - t0) * 1e3)
+        print(json.dumps({"proposals, host evaluate ms": host[-1]}), flush=True)
+    rec["host_evaluate"] = spread(host)
+    rec["equal_bits"] = all(np.asarray(on_dev.proposal_eval[k]).tobytes() == np.asarray(on_host.proposal_eval[k]).tobytes()
+                            for k in ("counts", "num_pos", "recalls", "ar"))
+    assert rec["equal_bits"] and repr(res) == repr(res_host), "the device path and the host path differ"
+    rec["box_proposals"] = dict(res["box_proposals"])
+    rec["speedup_median"] = rec["host_evaluate"]["median_ms"] / rec["device_evaluate"]["median_ms"]
+    rec["launch_over_host"] = rec["device_stages_ms"]["launch"] / rec["host_evaluate"]["median_ms"]
+    return rec
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--proposals", type=int, default=0, help="time the proposal recall of this many proposals per image instead of the AP")
     ap.add_argument("--protocol", choices=("coco", "lvis"), default="coco")
     ap.add_argument("--images", type=int, default=5000)
     ap.add_argument("--categories", type=int, nargs="+", default=None)
@@ -185,6 +278,10 @@ def main(argv=None):
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
     rec = {"device": torch.cuda.get_device_name(dev), "torch": torch.__version__, "sets": []}
+    if args.proposals > 0:
+        rec["sets"].append(measure_proposals(args.images, args, dev))
+        print(json.dumps(rec["sets"][-1]), flush=True)
+        args.categories = []
     for k in args.categories:
         rec["sets"].append(measure(args.images, k, args, dev))
         print(json.dumps(rec["sets"][-1]), flush=True)
