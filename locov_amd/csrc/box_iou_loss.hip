@@ -10,7 +10,7 @@
 // A row is a hundred operations on twelve fp32 inputs, so the row's mathematics runs in fp64 and the loss and each gradient entry are
 // rounded to fp32 once: the result sits within rounding of the float64 evaluation instead of at an fp32 chain's distance from it.
 // One workgroup, a fixed tree for the sum, no atomics: the same inputs give the same bits.  Built with -ffp-contract=off.
-#include "common.h"
+#include "reduce_common.h"
 
 namespace locov {
 
@@ -19,20 +19,8 @@ namespace {
 constexpr int kIouThreads = 256;
 constexpr double kIouEps = 1e-7;                                     // fvcore's eps, all three losses
 
-// fixed-order sum over the workgroup (every thread returns the total)
-__device__ __forceinline__ double block_sum(double v, double *red)
-{
-    const int t = threadIdx.x;
-    red[t] = v;
-    __syncthreads();
-    for (int s = kIouThreads / 2; s > 0; s >>= 1) {
-        if (t < s) red[t] = red[t] + red[t + s];
-        __syncthreads();
-    }
-    const double r = red[0];
-    __syncthreads();
-    return r;
-}
+// fixed-order sum over the workgroup (reduce_common.h: every thread returns the total)
+__device__ __forceinline__ double block_sum(double v, double *red) { return block_tree_reduce<kIouThreads>(v, red, SumOp()); }
 
 // d max(a, b) / d a and d min(a, b) / d a as torch.max / torch.min of two tensors define them: equal arguments share the gradient
 __device__ __forceinline__ double dmax(double a, double b) { return a > b ? 1.0 : (a == b ? 0.5 : 0.0); }

@@ -17,7 +17,7 @@
 //   caption_ln_bwd_kernel   LayerNorm path only, one wave per token: dx = LN-backward(g_enc * keep / (1 - p)) + g_in.
 //   caption_scatter_kernel  grid-stride, one wave per vocabulary row: binary search of the row's run in the sorted ids, then
 //                           0.0f + the gradient rows of its tokens in ascending flat position; an empty run writes zeros.
-#include "common.h"
+#include "reduce_common.h"
 
 #include <cmath>
 
@@ -27,11 +27,7 @@ constexpr int kCapThreads = 256;
 constexpr int kCapRankThreads = 1024;
 constexpr int kCapMaxTokens = LOCOV_CAPTION_MAX_TOKENS;
 
-__device__ __forceinline__ float wave_sum(float v)
-{
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
+__device__ __forceinline__ float wave_sum(float v) { return wave_reduce(v, SumOp()); }
 
 struct CaptionMlm {
     double p, p_mask, p_mask_noise;      // MASKED_LANGUAGE_MODELING_PROB, _PROB_MASK, _PROB_MASK + _PROB_NOISE (summed in double by the host)

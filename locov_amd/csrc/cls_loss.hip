@@ -50,8 +50,7 @@ struct SoftmaxLoss {
             sum += (double)expf(v.z - m);
             sum += (double)expf(v.w - m);
         }
-#pragma unroll
-        for (int s = kWave / 2; s > 0; s >>= 1) sum += __shfl_xor(sum, s, kWave);
+        sum = wave_reduce(sum, SumOp());
         const float xl = row[label];
         const double term = ((double)m + log(sum)) - (double)xl;
 
@@ -90,7 +89,7 @@ __global__ __launch_bounds__(kClsThreads) void cls_loss_rows_kernel(const float 
         const int lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
         int n = 0;
         for (int64_t r = threadIdx.x; r < R; r += kClsThreads) n += policy.counts(labels[r], C) ? 1 : 0;
-        n = wave_sum_int(n);
+        n = wave_reduce(n, SumOp());
         if (lane == 0) red_n[wave] = n;
         __syncthreads();
         n = 0;

@@ -12,7 +12,7 @@
 //                                              every lane), and writes its gradient to drow unless that is null
 // Neither file has per-file compile flags (build.py FILE_FLAGS): the contraction setting is part of the bits.
 #pragma once
-#include "common.h"
+#include "reduce_common.h"
 
 #include <cmath>
 
@@ -65,27 +65,6 @@ __device__ __forceinline__ void store_chunk(float *__restrict__ row, int chunk, 
         if (c + 1 < C) row[c + 1] = v.y;
         if (c + 2 < C) row[c + 2] = v.z;
         if (c + 3 < C) row[c + 3] = v.w;
-    }
-}
-
-__device__ __forceinline__ int wave_sum_int(int v)
-{
-#pragma unroll
-    for (int s = kWave / 2; s > 0; s >>= 1) v += __shfl_xor(v, s, kWave);
-    return v;
-}
-
-// the lanes' (maximum, its lowest index) merged over the wave, in every lane: the greater value wins, equal values go to the lower index
-__device__ __forceinline__ void wave_argmax(float &m, int &arg)
-{
-#pragma unroll
-    for (int s = kWave / 2; s > 0; s >>= 1) {
-        const float om = __shfl_xor(m, s, kWave);
-        const int oa = __shfl_xor(arg, s, kWave);
-        if (om > m || (om == m && oa < arg)) {
-            m = om;
-            arg = oa;
-        }
     }
 }
 

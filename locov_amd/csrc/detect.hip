@@ -31,6 +31,7 @@
 // the LDS sort holds -- the caller then runs the torch chain.  The IoU test, the block scan, the key layout and the top-k write-out
 // are select_common.h's (through detect_common.h).
 #include "detect_common.h"
+#include "reduce_common.h"
 
 namespace locov {
 
@@ -53,7 +54,7 @@ __global__ __launch_bounds__(256) void det_count_kernel(const float *__restrict_
         n += (c < K && v > thr) ? 1 : 0;
     }
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o);
+    for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o);      // (its own text: reduce_common.h says why)
     if (__ballot(bad) != 0ull && lane == 0) atomicOr(flags, LOCOV_DETECT_FLAG_NONFINITE);
     if (lane == 0) row_count[r] = n;
 }
@@ -153,8 +154,7 @@ __global__ __launch_bounds__(kDetThreads) void det_sort_kernel(DetLists L, const
         const float4 b = gbox[(int)(key[i] & kKeyRowMask) * bk + (int)(key[i] >> (kKeyRowBits + kKeyScoreBits)) * cs];
         m = fmaxf(m, fmaxf(fmaxf(b.x, b.y), fmaxf(b.z, b.w)));
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    m = wave_reduce(m, FmaxOp());
     if (lane == 0) red[wave] = m;
     __syncthreads();
     m = red[0];

@@ -36,6 +36,7 @@
 //   dw_topk_kernel           a workgroup per image: bitonic sort of the <= kDwCap winners in LDS, the first top-k out.
 // The IoU test, the block scan, the radix digit pick, the compacting append and the key layout are select_common.h's.
 #include "detect_common.h"
+#include "reduce_common.h"
 
 namespace locov {
 
@@ -121,13 +122,11 @@ __global__ __launch_bounds__(256) void dw_count_kernel(const float *__restrict__
     if (__ballot(bad) != 0ull && lane == 0) atomicOr(w.flags, LOCOV_DETECT_FLAG_NONFINITE);
     if (n) atomicAdd(&w.cnt[img * K + c], n);
     if constexpr (CS) {                         // (a row has K different boxes: the maximum is over candidates, not over rows)
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) own = fmaxf(own, __shfl_xor(own, o));
+        own = wave_reduce(own, FmaxOp());
         if (lane == 0 && own >= 0.f) atomicMax(&w.info[img].umax, __float_as_uint(own));
         return;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mask |= __shfl_xor(mask, o);
+    mask = wave_reduce(mask, OrOp());
     if (lane == 0 && mask) atomicOr(&rows_hit, mask);
     __syncthreads();
     if (tid < 64) {                             // batched_nms's max coordinate: over the boxes of rows with a candidate
@@ -136,8 +135,7 @@ __global__ __launch_bounds__(256) void dw_count_kernel(const float *__restrict__
             const float4 b = w.boxes[r0 + tid];
             mx = fmaxf(fmaxf(b.x, b.y), fmaxf(b.z, b.w)) + 0.f;       // (+ 0: a -0 max becomes +0; max + 1 is the same)
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+        mx = wave_reduce(mx, FmaxOp());
         if (tid == 0 && mx >= 0.f) atomicMax(&w.info[img].umax, __float_as_uint(mx));
     }
 }

@@ -1,6 +1,6 @@
 // Internal interface of gemm_nt.hip (shared with head.hip).
 #pragma once
-#include "common.h"
+#include "reduce_common.h"
 
 namespace locov {
 
@@ -39,8 +39,7 @@ __device__ __forceinline__ void split_scale_of(const float *slot, float &s, floa
 // only a wave that would raise it issues the atomic: after the first few arrivals almost none does.
 __device__ __forceinline__ void amax_fold(float *slot, float m)
 {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    m = wave_reduce(m, FmaxOp());
     if ((threadIdx.x & 63) == 0 && m > 0.f) {
         unsigned *w = reinterpret_cast<unsigned *>(slot) + 2;
         const unsigned bits = __float_as_uint(m);                      // non-negative floats order like their bit patterns

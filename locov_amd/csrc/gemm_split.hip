@@ -661,8 +661,7 @@ __global__ __launch_bounds__(256) void split_amax_kernel(const float *__restrict
         m = fmaxf(fmaxf(m, fabsf(v[0])), fabsf(v[1]));
         m = fmaxf(fmaxf(m, fabsf(v[2])), fabsf(v[3]));
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    m = wave_reduce(m, FmaxOp());
     __shared__ float wmax[4];
     if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = m;
     __syncthreads();
@@ -701,7 +700,7 @@ __global__ __launch_bounds__(256) void amax_bound_kernel(AmaxBoundList L, float 
         m = fmaxf(fmaxf(m, fabsf(v[2])), fabsf(v[3]));
     }
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));     // (its own text: reduce_common.h says why)
     __shared__ float wmax[4];
     if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = m;
     __syncthreads();

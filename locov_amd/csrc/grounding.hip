@@ -22,24 +22,14 @@
 // on ties (torch's argmax rule); with no valid entry every entry equals the fill and the choice is
 // index 0, whose unmasked distance is used -- what the reference's one_hot(argmax) does.  The one-hot
 // is a constant, so the backward only scatters -g / (temperature * count) onto the chosen entries.
-#include "common.h"
+#include "reduce_common.h"
 
 namespace locov {
 
 constexpr int kGroundThreads = 256;
 
-__device__ __forceinline__ float wave_max(float v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
-    return v;
-}
-__device__ __forceinline__ float wave_add(float v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
+__device__ __forceinline__ float wave_max(float v) { return wave_reduce(v, FmaxOp()); }
+__device__ __forceinline__ float wave_add(float v) { return wave_reduce(v, SumOp()); }
 
 // BWD = false: cost_w2r[c,i], cost_r2w[c,i].   BWD = true: dS block from (g_w2r[c,i], g_r2w[c,i]).
 // HARD: one_hot(argmax) instead of the softmax.  A direction whose cost (forward) / gradient (backward)
@@ -90,12 +80,7 @@ __global__ __launch_bounds__(kGroundThreads) void grounding_kernel(
             int best = NR;
             for (int r = lane; r < NR; r += 64)
                 if (nr != 0.f && rm[r] > 0.f && row[r] > m) { m = row[r]; best = r; }
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                const float om = __shfl_xor(m, off);
-                const int ob = __shfl_xor(best, off);
-                if (om > m || (om == m && ob < best)) { m = om; best = ob; }
-            }
+            wave_argmax(m, best);
             if (nr == 0.f) { m = row[0]; best = 0; }
             if (!BWD) {
                 if (wv) acc_w += -m;                 // the chosen region's distance -s[t, r*]

@@ -9,6 +9,8 @@ namespace locov {
 
 constexpr int kMeanRows = 256;
 
+__device__ __forceinline__ float wave_sum(float v) { return wave_reduce(v, SumOp()); }
+
 // x [rows, HW] -> out [rows] (rows = R*C).  HBM-read-bound (0.40 MB per proposal at
 // C5=2048, HW=49).  A workgroup streams 256 consecutive rows (one contiguous run of
 // 256*HW floats) into LDS with 16-byte coalesced loads; each lane then sums its own row
@@ -51,7 +53,7 @@ __global__ __launch_bounds__(256) void spatial_mean_wave_kernel(const float *__r
     const float *p = x + row * HW;
     float s = 0.f;
     for (int k = lane; k < HW; k += 64) s += p[k];
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+    s = wave_sum(s);
     if (lane == 0) out[row] = s / (float)HW;
 }
 
@@ -79,13 +81,6 @@ __global__ __launch_bounds__(256) void spatial_mean_nhwc_kernel(const float *__r
         float4 o = {__fdiv_rn(s.x, d), __fdiv_rn(s.y, d), __fdiv_rn(s.z, d), __fdiv_rn(s.w, d)};
         reinterpret_cast<float4 *>(out + r * C)[c4] = o;
     }
-}
-
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
 }
 
 // One wave per row, wavefront-shuffle reductions.  L2: y = x / max(||x||_2, eps)

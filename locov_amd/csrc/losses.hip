@@ -17,6 +17,7 @@
 // Built with -ffp-contract=off: each step is the torch op it replaces, rounded on its own; the sums run in a fixed order (one
 // workgroup, a fixed tree), so a step's losses are reproducible run to run.
 #include "box_delta_common.h"
+#include "reduce_common.h"
 
 namespace locov {
 
@@ -24,34 +25,9 @@ namespace {
 
 constexpr int kLossThreads = 256;
 
-// fixed-order sum over the workgroup (every thread returns the total)
-__device__ __forceinline__ float block_sum(float v, float *red)
-{
-    const int t = threadIdx.x;
-    red[t] = v;
-    __syncthreads();
-    for (int s = kLossThreads / 2; s > 0; s >>= 1) {
-        if (t < s) red[t] = red[t] + red[t + s];
-        __syncthreads();
-    }
-    const float r = red[0];
-    __syncthreads();
-    return r;
-}
-
-__device__ __forceinline__ float block_max(float v, float *red)
-{
-    const int t = threadIdx.x;
-    red[t] = v;
-    __syncthreads();
-    for (int s = kLossThreads / 2; s > 0; s >>= 1) {
-        if (t < s) red[t] = fmaxf(red[t], red[t + s]);
-        __syncthreads();
-    }
-    const float r = red[0];
-    __syncthreads();
-    return r;
-}
+// fixed-order sum / maximum over the workgroup (reduce_common.h: every thread returns it)
+__device__ __forceinline__ float block_sum(float v, float *red) { return block_tree_reduce<kLossThreads>(v, red, SumOp()); }
+__device__ __forceinline__ float block_max(float v, float *red) { return block_tree_reduce<kLossThreads>(v, red, FmaxOp()); }
 
 }  // namespace
 

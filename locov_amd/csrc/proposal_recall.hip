@@ -14,6 +14,7 @@
 //   again: its value cannot rise, and the walk ends at the first step whose maximum is 0 (the rest of the overlaps are 0).
 //   That is P * G + (columns formed again) * P IoUs per workgroup where the literal loop reads min(P, G) * P * G.
 //   The gts outside the area range, and the ones the caller leaves out (gt_skip: COCO's crowd), start as used columns.
+#include "reduce_common.h"
 #include "select_common.h"
 
 namespace locov {
@@ -35,15 +36,7 @@ struct RecallArgs {
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
-__device__ __forceinline__ u64 wave_max(u64 v)
-{
-#pragma unroll
-    for (int o = kWave / 2; o > 0; o >>= 1) {
-        const u64 t = __shfl_xor(v, o, kWave);
-        v = t > v ? t : v;
-    }
-    return v;
-}
+__device__ __forceinline__ u64 wave_max(u64 v) { return wave_reduce(v, MaxOp()); }
 
 __device__ __forceinline__ bool bit_set(const unsigned *mask, int i) { return (mask[i >> 5] >> (i & 31)) & 1u; }
 

@@ -23,6 +23,7 @@
 // Both phases of the labelling take the IoU from select_common.h's box_pairwise_iou (the promotion's `==` needs the two to round
 // identically; this file is built with -ffp-contract=off), and the sampler's digit pick is that header's radix_pick.
 #include "box_delta_common.h"
+#include "reduce_common.h"
 #include "select_common.h"
 
 namespace locov {
@@ -60,11 +61,7 @@ __global__ __launch_bounds__(kRtThreads) void rpn_gt_max_kernel(const float4 *__
                 const unsigned q = live[k] ? __float_as_uint(box_pairwise_iou(a, b[k])) : 0u;
                 m = q > m ? q : m;
             }
-#pragma unroll
-            for (int o = kWave / 2; o > 0; o >>= 1) {
-                const unsigned t = (unsigned)__shfl_xor((int)m, o, kWave);
-                m = t > m ? t : m;
-            }
+            m = wave_reduce(m, MaxOp());
             if (lane == 0 && m != 0u) atomicMax(&smax[j], m);            // (an LDS integer maximum: the order does not matter)
         }
         __syncthreads();
@@ -249,11 +246,8 @@ __global__ __launch_bounds__(kRtThreads) void rpn_loss_kernel(const float *__res
         dlogits[at] = gl;
         ddeltas[at] = make_float4(gd[0], gd[1], gd[2], gd[3]);
     }
-#pragma unroll
-    for (int o = kWave / 2; o > 0; o >>= 1) {                    // a fixed tree over the wave, then the waves in order
-        sc += __shfl_xor(sc, o, kWave);
-        sl += __shfl_xor(sl, o, kWave);
-    }
+    sc = wave_reduce(sc, SumOp());                               // a fixed tree over the wave, then the waves in order
+    sl = wave_reduce(sl, SumOp());
     if (lane == 0) {
         red[0][wave] = sc;
         red[1][wave] = sl;

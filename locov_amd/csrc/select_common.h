@@ -41,7 +41,7 @@ __device__ __forceinline__ float box_pairwise_iou(const float4 a, const float4 b
     return inter > 0.f ? inter / ((area_a + area_b) - inter) : 0.f;
 }
 
-// ---- wave level -----------------------------------------------------------------------------------------------------------------------
+// ---- wave level (the reductions -- wave_reduce, wave_argmax, block_tree_reduce -- are reduce_common.h's) ------------------------------
 
 // how many of the lanes below this one have their bit set in a ballot
 __device__ __forceinline__ int lanes_below(unsigned long long ballot)

@@ -27,7 +27,7 @@ static_assert(kFedWords <= kFedThreads, "one bitmap word per thread");
 // the sum of v over the block, in every thread (red: kFedWaves ints; safe to call back to back)
 __device__ __forceinline__ int fed_block_sum(int v, int *red)
 {
-    v = wave_sum_int(v);
+    v = wave_reduce(v, SumOp());
     __syncthreads();                                                 // (the previous call's readers are done)
     if (threadIdx.x % kWave == 0) red[threadIdx.x / kWave] = v;
     __syncthreads();
@@ -189,9 +189,7 @@ struct SigmoidLoss {
             if (drow) store_chunk<VEC>(drow, k, C, make_float4(g[0], g[1], g[2], g[3]));
         }
         wave_argmax(m, arg);
-#pragma unroll
-        for (int s = kWave / 2; s > 0; s >>= 1) sum += __shfl_xor(sum, s, kWave);
-        return sum;
+        return wave_reduce(sum, SumOp());
     }
 };
 
