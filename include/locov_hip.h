@@ -612,6 +612,8 @@ int locov_nms_sorted(const float *boxes_sorted, int64_t K, float iou_threshold, 
  *   (16-byte aligned), rows of image i = [row_offsets[i], row_offsets[i + 1]) (n_images + 1 HOST ints), image_hw: n_images HOST
  *   (height, width) pairs; wx..wh: Box2BoxTransform weights, scale_clamp its clamp of dw / dh.
  *   out_boxes [n_images, topk, 4], out_scores / out_classes / out_rows [n_images, topk] (rows: proposal index inside its image);
+ *   every slot of a call is written: the slots at or beyond an image's count are empty (box 0, score 0, class -1, row -1), also
+ *   for an image without candidates, an image over the candidate limit and a call without a single proposal;
  *   counts_and_flags [n_images + 1] int32: detections per image, then LOCOV_DETECT_FLAG_* bits -- when one is set the outputs are
  *   not to be used (the caller runs the torch chain): NONFINITE = a decoded box or a probability is inf / NaN (the reference drops
  *   such proposals with a warning), OVERFLOW = an image has more than LOCOV_DETECT_MAX_CANDIDATES candidates.

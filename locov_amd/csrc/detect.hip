@@ -241,6 +241,7 @@ __global__ __launch_bounds__(kDetThreads) void det_nms_topk_kernel(DetLists L, c
     const int img = blockIdx.x, tid = threadIdx.x;
     const int n = img_count[img];
     if (n > kDetMaxCand || n == 0) {
+        empty_detections_write_out<kDetThreads>(0, img, topk, out_boxes, out_scores, out_classes, out_rows);
         if (tid == 0) counts[img] = 0;
         return;
     }
@@ -374,7 +375,7 @@ static int det_run(const char *who, const float *probs, int64_t ld_probs, int nu
     hipStream_t s = as_stream(stream);
     hipError_t e = hipMemsetAsync(counts_and_flags, 0, sizeof(int) * (size_t)(n_images + 1), s);
     if (e != hipSuccess) return set_error(LOCOV_ERR_LAUNCH, "%s: memset: %s", who, hipGetErrorString(e));
-    if (R == 0) return LOCOV_OK;
+    if (R == 0) return det_fill_empty(who, n_images, topk, out_boxes, out_scores, out_classes, out_rows, s);
     char *ws = static_cast<char *>(workspace);
     float4 *boxes = reinterpret_cast<float4 *>(ws);
     int *row_count = reinterpret_cast<int *>(ws + R * bk * 16);

@@ -104,4 +104,19 @@ __device__ __forceinline__ void det_bitonic_sort(unsigned long long *key, int P,
 }
 
 }  // namespace
+// A call without a single proposal launches nothing: its n_images * topk slots are written as empty here (box 0, score 0, class -1,
+// row -1), as the last kernel writes the slots behind an image's detections.  Null outputs (allowed when R == 0) are skipped.
+static int det_fill_empty(const char *who, int n_images, int topk, float *out_boxes, float *out_scores, int64_t *out_classes, int64_t *out_rows,
+                          hipStream_t s)
+{
+    const size_t n = (size_t)n_images * (size_t)topk;
+    hipError_t e = hipSuccess;
+    if (out_boxes && e == hipSuccess) e = hipMemsetAsync(out_boxes, 0, n * 16, s);
+    if (out_scores && e == hipSuccess) e = hipMemsetAsync(out_scores, 0, n * 4, s);
+    if (out_classes && e == hipSuccess) e = hipMemsetAsync(out_classes, 0xFF, n * 8, s);
+    if (out_rows && e == hipSuccess) e = hipMemsetAsync(out_rows, 0xFF, n * 8, s);
+    if (e != hipSuccess) return set_error(LOCOV_ERR_LAUNCH, "%s: memset: %s", who, hipGetErrorString(e));
+    return LOCOV_OK;
+}
+
 }  // namespace locov

@@ -460,6 +460,7 @@ __global__ __launch_bounds__(1024) void dw_topk_kernel(DetGeom g, DwWork w, int 
     const int img = blockIdx.x, tid = threadIdx.x;
     const int n = w.info[img].gcount, k = min(topk, w.info[img].surv);
     if (n == 0) {
+        empty_detections_write_out<1024>(0, img, topk, out_boxes, out_scores, out_classes, out_rows);
         if (tid == 0) counts[img] = 0;
         return;
     }
@@ -547,7 +548,7 @@ static int dw_run(const char *who, const float *probs, int64_t ld_probs, int num
     hipStream_t s = as_stream(stream);
     hipError_t e = hipMemsetAsync(counts_and_flags, 0, sizeof(int) * (size_t)(n_images + 1), s);
     if (e != hipSuccess) return set_error(LOCOV_ERR_LAUNCH, "%s: memset: %s", who, hipGetErrorString(e));
-    if (R == 0) return LOCOV_OK;
+    if (R == 0) return det_fill_empty(who, n_images, topk, out_boxes, out_scores, out_classes, out_rows, s);
     const int K = num_classes;
     const int64_t nK = (int64_t)n_images * K;
     char *ws = static_cast<char *>(workspace);

@@ -156,8 +156,22 @@ __device__ __forceinline__ unsigned long long merge_key(unsigned long long sort_
     return ((sort_key >> kKeyRowBits) << (kKeyRowBits + kKeyClsBits)) | ((sort_key & kKeyRowMask) << kKeyClsBits) | (unsigned long long)cls;
 }
 
+// Slots img * topk + j for j in [from, topk): no detection -- box 0, score 0, class -1, row -1 (every slot of a call is written).
+template <int kThreads>
+__device__ __forceinline__ void empty_detections_write_out(int from, int img, int topk, float4 *out_boxes, float *out_scores,
+                                                           int64_t *out_classes, int64_t *out_rows)
+{
+    for (int j = from + threadIdx.x; j < topk; j += kThreads) {
+        const int64_t slot = (int64_t)img * topk + j;
+        out_boxes[slot] = make_float4(0.f, 0.f, 0.f, 0.f);
+        out_scores[slot] = 0.f;
+        out_classes[slot] = -1;
+        out_rows[slot] = -1;
+    }
+}
+
 // The first `count` of an image's sorted merge keys as detections: box (of candidate (row, class): gbox[row * bk + class * cs]),
-// score, class and row into slots img * topk + j.
+// score, class and row into slots img * topk + j; the slots behind them are written as empty.
 template <int kThreads>
 __device__ __forceinline__ void merge_keys_write_out(const unsigned long long *key, int count, const float4 *gbox, int bk, int cs, int img,
                                                      int topk, float4 *out_boxes, float *out_scores, int64_t *out_classes,
@@ -172,6 +186,7 @@ __device__ __forceinline__ void merge_keys_write_out(const unsigned long long *k
         out_classes[slot] = cls;
         out_rows[slot] = row;
     }
+    empty_detections_write_out<kThreads>(count, img, topk, out_boxes, out_scores, out_classes, out_rows);
 }
 
 // ---- small things ---------------------------------------------------------------------------------------------------------------------

@@ -824,9 +824,10 @@ def detect_postprocess(probs: torch.Tensor, deltas: torch.Tensor, proposal_boxes
     probs [R, K + 1] = softmax of the logits, proposal_boxes [R, 4], deltas [R, 4] (class-agnostic regression) or [R, 4K]
     (class-specific: candidate (r, c) has the box decoded from deltas[r, 4c:4c + 4]), sizes: rows per image, image_shapes:
     (height, width) per image, weights: Box2BoxTransform's.
-    Returns (boxes [B, topk, 4], scores [B, topk], classes [B, topk] int64, rows [B, topk] int64, counts: list of B ints), or None
-    when the kernels flagged a case they do not take (non-finite values, more than DETECT_MAX_CANDIDATES candidates in an image):
-    the caller then runs the torch chain."""
+    Returns (boxes [B, topk, 4], scores [B, topk], classes [B, topk] int64, rows [B, topk] int64, counts: list of B ints) -- the
+    slots at or beyond an image's count are empty (box 0, score 0, class -1, row -1) --, or None when the kernels flagged a case
+    they do not take (non-finite values, more than DETECT_MAX_CANDIDATES candidates in an image): the caller then runs the torch
+    chain."""
     out, flags = _detect_postprocess_flags(probs, deltas, proposal_boxes, sizes, image_shapes, weights, scale_clamp, score_thresh,
                                            nms_thresh, topk)
     return None if flags else out
