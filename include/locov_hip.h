@@ -14,10 +14,14 @@
  *   - Every pointer is a DEVICE pointer unless the parameter name ends in `_host`.
  *   - `stream` is a hipStream_t passed as void* (torch.cuda.current_stream().cuda_stream).
  *     Calls only enqueue work on that stream: no allocation, no synchronisation, no
- *     hidden global state -> safe to capture in a hipGraph.  The ONE exception is the opt-in
+ *     hidden global state -> safe to capture in a hipGraph.  Exceptions, two: (1) the opt-in
  *     measurement aid locov_gemm_timing_* at the end of this header: a process-global,
  *     mutex-guarded list of HIP events, OFF by default, recording nothing while the launch
  *     stream is being captured; locov_gemm_timing_read() synchronises on those events.
+ *     (2) locov_augment_images uploads its per-image table with a hipMemcpyAsync from PAGEABLE
+ *     host memory: the runtime may make the host wait until `stream` has drained, and a captured
+ *     copy node would keep a pointer to host memory that is freed when the call returns, so the
+ *     call MUST NOT be captured (see its workspace note).  tests/stream_cases.py lists both.
  *   - Outputs are caller-allocated.  Tensors are dense row-major in the stated shape.
  *   - Return value: 0 on success, <0 on error (LOCOV_ERR_*); locov_last_error() returns
  *     a thread-local message for the last failing call on this thread.

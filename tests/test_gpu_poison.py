@@ -15,27 +15,17 @@ outputs too, which are the later op's inputs), so that the second call does not 
 A case with a `tier` also proves which kernel it ran: the library's GEMM launch record of the first run (or, where the choice is
 made elsewhere, the library's rule restated on the case's inputs) must show the tier the case's name claims.
 
-NONREPRODUCIBLE lists the outputs that already differ between two runs under the SAME pattern, with the reason read from the
+poison.NONREPRODUCIBLE lists the outputs that already differ between two runs under the SAME pattern, with the reason read from the
 kernel; they are compared with the gate of the op's own reference test plus equal NaN / inf positions."""
 import pytest
 import torch
 
 import poison
 import poison_cases
+from poison import compare as _compare
 from poison_cases import CASES
 
 pytestmark = pytest.mark.gpu
-
-# case name -> {output index: (gate, reason)}: max |a - b| <= gate * max(max |a|, 1), the gate of tests/test_gpu_roi_align_bwd.py
-_ATOMIC = ("the ROIAlign backward kernels add into the zero-filled map gradient with fp32 atomics (ops.roi_align_nhwc_bwd: 'fp32 atomics'; "
-           "csrc/roi_align.hip, roi_align_nhwc_bwd.hip): the order of the additions is the order of arrival")
-NONREPRODUCIBLE = {
-    "roi_align_plan_path": {1: (1e-5, _ATOMIC)},
-    "roi_align_exact_nhwc_copy": {1: (1e-5, _ATOMIC)},
-    "roi_align_nchw": {1: (1e-5, _ATOMIC)},
-    "roi_align_nhwc_even_bins_pos_major": {2: (1e-5, _ATOMIC)},
-    "roi_align_nhwc_all_bins_bf16_map": {2: (1e-5, _ATOMIC)},
-}
 
 
 @pytest.fixture(scope="module")
@@ -54,40 +44,6 @@ def _host(outputs):
 def _setup(case, monkeypatch):
     for k, v in (case.env or {}).items():
         monkeypatch.setenv(k, v)
-
-
-def _close(a, b, gate):
-    if a.shape != b.shape or a.dtype != b.dtype:
-        return False
-    a, b = a.double(), b.double()
-    if not (torch.equal(torch.isnan(a), torch.isnan(b)) and torch.equal(torch.isinf(a), torch.isinf(b))):
-        return False
-    fin = torch.isfinite(a)
-    if not fin.any():
-        return True
-    return float((a[fin] - b[fin]).abs().max()) <= gate * max(float(a[fin].abs().max()), 1.0)
-
-
-def _compare(case, got, want, what):
-    assert len(got) == len(want), f"{case.name}: {len(got)} outputs {what}, {len(want)} before"
-    masks = {i: (build, why) for i, build, why in case.unspecified}
-    loose = NONREPRODUCIBLE.get(case.name, {})
-    bad = []
-    for i, (a, b) in enumerate(zip(got, want)):
-        if a is None or b is None:
-            if a is not b:
-                bad.append(f"output {i}: present in one run only")
-            continue
-        mask = masks[i][0](want) if i in masks else None
-        if i in loose:
-            ok = _close(a if mask is None else a[mask], b if mask is None else b[mask], loose[i][0])
-        else:
-            ok = poison.same_bits(a, b, mask)
-        if not ok:
-            diff = (a.reshape(-1).view(torch.uint8) != b.reshape(-1).view(torch.uint8)) if a.shape == b.shape and a.dtype == b.dtype else None
-            where = "" if diff is None else f", {int(diff.sum())} of {diff.numel()} bytes differ, first at byte {int(diff.nonzero()[0])}"
-            bad.append(f"output {i} {tuple(a.shape)} {a.dtype}{where}")
-    assert not bad, f"{case.name} {what}: " + "; ".join(bad)
 
 
 def _gemm_launches(lib, fn):
