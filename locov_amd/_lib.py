@@ -269,6 +269,38 @@ SIGNATURES = {
     "locov_augment_images": (c_int, [POINTER(c_void_p), POINTER(c_void_p), POINTER(AugmentDesc), c_int, _p, c_int64, _p, c_int64, _p]),
 }
 
+# include/locov_jpeg.h: the JPEG decoder's entry points, in the same library, bound next to SIGNATURES by load()
+JPEG_RGB, JPEG_BGR, JPEG_L, JPEG_MAX_DEQUANTISED = 0, 1, 2, 1096
+
+
+class JpegHeader(ctypes.Structure):
+    """locov_jpeg_header of include/locov_jpeg.h"""
+    _fields_ = [("supported", ctypes.c_int32), ("reason", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32),
+                ("ncomp", ctypes.c_int32), ("comp_id", ctypes.c_int32 * 3), ("comp_h", ctypes.c_int32 * 3), ("comp_v", ctypes.c_int32 * 3),
+                ("comp_tq", ctypes.c_int32 * 3), ("comp_td", ctypes.c_int32 * 3), ("comp_ta", ctypes.c_int32 * 3),
+                ("restart_interval", ctypes.c_int32), ("scan_start", c_int64), ("qt_present", ctypes.c_uint8 * 4),
+                ("qt", (ctypes.c_uint16 * 64) * 4), ("dc_present", ctypes.c_uint8 * 4), ("ac_present", ctypes.c_uint8 * 4),
+                ("dc_counts", (ctypes.c_uint8 * 16) * 4), ("ac_counts", (ctypes.c_uint8 * 16) * 4),
+                ("dc_symbols", (ctypes.c_uint8 * 256) * 4), ("ac_symbols", (ctypes.c_uint8 * 256) * 4)]
+
+
+class JpegDesc(ctypes.Structure):
+    """locov_jpeg_desc of include/locov_jpeg.h"""
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("ncomp", ctypes.c_int32), ("hs", ctypes.c_int32), ("vs", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("record_offset", c_int64), ("record_bytes", c_int64), ("qt_offset", c_int64)]
+
+
+# name -> (restype, argtypes); mirrors include/locov_jpeg.h declaration by declaration
+JPEG_SIGNATURES = {
+    "locov_jpeg_parse": (c_int, [c_void_p, c_int64, POINTER(JpegHeader)]),
+    "locov_jpeg_entropy_bytes": (c_int64, [POINTER(JpegHeader), c_int64]),
+    "locov_jpeg_entropy_decode": (c_int, [POINTER(c_void_p), POINTER(c_int64), POINTER(JpegHeader), POINTER(c_void_p), POINTER(c_int64), c_int,
+                                          POINTER(ctypes.c_int32), POINTER(c_int64)]),
+    "locov_jpeg_entropy_pack": (c_int, [POINTER(JpegHeader), POINTER(c_void_p), POINTER(c_int64), POINTER(c_void_p), c_int]),
+    "locov_jpeg_decode_workspace_bytes": (c_int64, [POINTER(JpegDesc), c_int]),
+    "locov_jpeg_decode": (c_int, [_p, c_int64, POINTER(JpegDesc), c_int, c_int, POINTER(c_void_p), _p, c_int64, _p]),
+}
+
 _lib = None
 
 
@@ -286,7 +318,7 @@ def load() -> ctypes.CDLL:
             f"{LIB_PATH} not found: build it with `python -m locov_amd.build` "
             "(or __graft_entry__.build()).  The LSM ROI-head path has no fallback.")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in SIGNATURES.items():
+    for name, (restype, argtypes) in list(SIGNATURES.items()) + list(JPEG_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

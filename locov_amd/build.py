@@ -64,6 +64,7 @@ def sources():
 def _headers():
     hs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     hs.append(os.path.join(os.path.dirname(HERE), "include", "locov_hip.h"))
+    hs.append(os.path.join(os.path.dirname(HERE), "include", "locov_jpeg.h"))
     return hs
 
 

@@ -17,6 +17,10 @@ As in evaluation.py the numpy path of this module is the DEFINITION:
   * the device path (ops.resize_flip_images: csrc/image_resize.hip) does resize, flip and the HWC -> CHW transposition of a whole
     batch in one launch and gives the same bytes.  The host path serves CPU tensors, LOCOV_FUSED_RESIZE=0 and the sizes outside
     ops.resize_supported.
+  * a "file_name" that is a baseline JPEG is decoded without Pillow on a cuda mapper, to Pillow's bytes: jpeg.py is the definition,
+    the scans of the batch are Huffman-decoded on host threads inside the library and the pixels made in two launches
+    (ops.jpeg_entropy_stage / jpeg_pack / jpeg_decode_records: csrc/jpeg_entropy.h, csrc/jpeg.hip).  Pillow serves everything else:
+    CPU mappers, LOCOV_FUSED_JPEG=0, other files, streams the decoder does not take, any anomaly in a scan.
   * transform_proposals and change_proposals_as_gt are the definition of the proposal side (MODEL.LOAD_OBJ_PROPOSALS, as in
     coco_lsm.yaml: CocoImageDatasetMapper turns the image's precomputed OLN proposals with objectness > 0.7 into its "instances",
     gt_classes 1, and moves the annotated boxes to "gt_obj").  The boxes go through apply_box in the ARRAY'S dtype -- numpy rounds
@@ -61,6 +65,9 @@ from .structures import Boxes, Instances
 PRECISION_BITS = 22                      # Pillow's PRECISION_BITS for 8-bit channels: 32 - 8 - 2
 XYXY_ABS, XYWH_ABS = 0, 1                # [D2-upstream] BoxMode
 FLIP_NONE, FLIP_HORIZONTAL, FLIP_VERTICAL = 0, 1, 2
+# a JPEG file larger than this is Pillow's to answer on every mapper: libjpeg refuses more than 65 500 pixels a side, and Pillow
+# warns above Image.MAX_IMAGE_PIXELS (89 478 485) and raises DecompressionBombError -- the black image -- above twice that
+JPEG_MAX_SIDE, JPEG_MAX_PIXELS = 65500, 89478485
 
 
 # ---- Pillow's resampling -------------------------------------------------------------------------------------------------------
@@ -487,6 +494,10 @@ class DatasetMapper:
 
     The raw image is dataset_dict["image_raw"], HWC uint8 (numpy or tensor) already in INPUT.FORMAT order; without it "file_name"
     is read with Pillow, and when that fails the reference's fallback applies: a black image and the caption "A black image.".
+    On a cuda device a baseline JPEG file is decoded without Pillow, to Pillow's bytes (jpeg.py is the definition): the batch's
+    scans on host threads, one pinned upload, two launches (ops.jpeg_entropy_stage / jpeg_pack / jpeg_decode_records).  "cpu",
+    LOCOV_FUSED_JPEG=0, a file that is no JPEG, a header the decoder does not take (progressive, other sampling layouts, ...: jpeg.py)
+    and any anomaly in the scan take Pillow as before, with its error semantics -- the truncated file is still the black image.
 
     device: where "image" is produced.  A cuda device resizes, flips and transposes the whole batch in one launch
     (ops.resize_flip_images); "cpu" -- and LOCOV_FUSED_RESIZE=0, and any image outside ops.resize_supported -- takes the numpy
@@ -510,7 +521,9 @@ class DatasetMapper:
         self.is_train = bool(is_train)
         _refuse_unbuilt(cfg, strong_given=train_aug is not None)
         self.augmentations = _resize_and_flip(cfg, is_train)
-        self._decoded: Dict[str, Optional[np.ndarray]] = {}        # files draw_sample read for their size (train_aug only), until _raw takes them
+        # files by name until _raw takes them: what draw_sample decoded for its size (train_aug only; None: it failed there), and on
+        # the JPEG device path the staged scan (ops.JpegStaged), then the decoded device tensor
+        self._decoded: Dict[str, object] = {}
         self.train_aug = train_aug if self.is_train else None      # (basic_mappers.py:171: applied in training only)
         if getattr(cfg.MODEL, "MASK_ON", False) or getattr(cfg.MODEL, "KEYPOINT_ON", False):
             raise NotImplementedError("MODEL.MASK_ON / KEYPOINT_ON: only the box side of the mapper is built")
@@ -535,6 +548,8 @@ class DatasetMapper:
         flip = self.augmentations[1] if len(self.augmentations) > 1 else None
         sample = {"short_edge": [], "flip": [], "caption": []}
         self._decoded.clear()
+        if self.train_aug is not None:
+            self._jpeg_stage(dataset_dicts)                        # (the sizes below come from the entropy stage's verdict)
         for d in dataset_dicts:
             sample["short_edge"].append(int(resize.draw(self.rng)))
             sample["flip"].append(bool(flip.draw(self.rng)) if flip is not None else False)
@@ -556,6 +571,9 @@ class DatasetMapper:
         raw = d.get("image_raw")
         if raw is not None:
             return int(raw.shape[0]), int(raw.shape[1])
+        staged = self._decoded.get(d.get("file_name"))
+        if isinstance(staged, ops.JpegStaged):                     # (_jpeg_stage: the scan decoded without an anomaly; the record waits for _raw)
+            return int(staged.header.height), int(staged.header.width)
         try:
             image = _read_file(d["file_name"], self.image_format)
         except Exception:
@@ -565,6 +583,50 @@ class DatasetMapper:
         if image is None:
             return int(d["height"]), int(d["width"])               # (the black image of _raw)
         return int(image.shape[0]), int(image.shape[1])
+
+    # -- JPEG files on a cuda mapper: the scans on host threads, the pixels on the device (ops.decode_jpeg_images' two halves)
+    def _jpeg_stage(self, dataset_dicts: Sequence[dict]) -> None:
+        """Reads the files of the dicts without "image_raw" that start with FF D8 and are not in self._decoded yet, and
+        Huffman-decodes those whose header the device decoder takes, all in one call.  A stream that came through without an
+        anomaly is kept in self._decoded as its ops.JpegStaged; every other file is left to _read_file, with Pillow's error
+        semantics.  Does nothing unless the mapper is on a cuda device and LOCOV_FUSED_JPEG is not "0"."""
+        if not self._on_device("JPEG") or self.image_format not in ops.JPEG_FORMATS:
+            return
+        names, datas = [], []
+        for d in dataset_dicts:
+            name = d.get("file_name")
+            if d.get("image_raw") is not None or not isinstance(name, str) or name in self._decoded or name in names:
+                continue
+            try:
+                with open(name, "rb") as f:
+                    data = f.read(2)
+                    if data != b"\xff\xd8":
+                        continue
+                    data += f.read()
+            except OSError:
+                continue
+            names.append(name)
+            datas.append(data)
+        headers = [ops.jpeg_parse(data) for data in datas]
+        # (sizes at which Pillow itself refuses or warns -- libjpeg's 65 500 a side, Image.MAX_IMAGE_PIXELS -- stay Pillow's to answer)
+        take = [i for i, h in enumerate(headers) if h.supported and (self.image_format != "L" or h.ncomp == 1)
+                and max(h.width, h.height) <= JPEG_MAX_SIDE and h.width * h.height <= JPEG_MAX_PIXELS]
+        staged = ops.jpeg_entropy_stage([datas[i] for i in take], [headers[i] for i in take])
+        for i, s in zip(take, staged):
+            if s.status == 0:
+                self._decoded[names[i]] = s
+
+    def _jpeg_decode(self, dataset_dicts: Sequence[dict]) -> None:
+        """The staged streams of the batch's files become HWC uint8 device tensors: one pinned buffer, one upload and one
+        ops.jpeg_decode_records call per IMAGE_BATCH_MAX_IMAGES images.  What an earlier draw_sample staged for other dicts is dropped."""
+        wanted = {d.get("file_name") for d in dataset_dicts}
+        for name in [n for n, v in self._decoded.items() if isinstance(v, ops.JpegStaged) and n not in wanted]:
+            del self._decoded[name]
+        names = [name for name, v in self._decoded.items() if isinstance(v, ops.JpegStaged)]
+        for part in _slices(names):
+            batch = ops.jpeg_pack([self._decoded[name] for name in part], pin_memory=True)
+            images = ops.jpeg_decode_records(batch.records.to(self.device, non_blocking=True), batch.descs, self.image_format)
+            self._decoded.update(zip(part, images))
 
     # -- one image's host-side part: the raw image, the transforms, the boxes, the caption
     def _raw(self, d: dict):
@@ -618,6 +680,8 @@ class DatasetMapper:
     def map_batch(self, dataset_dicts: Sequence[dict], sample: Optional[Dict[str, list]] = None) -> List[dict]:
         dataset_dicts = list(dataset_dicts)
         sample = self.draw_sample(dataset_dicts) if sample is None else sample
+        self._jpeg_stage(dataset_dicts)
+        self._jpeg_decode(dataset_dicts)
         prepared = [self._prepare(d, i, sample) for i, d in enumerate(dataset_dicts)]
         self._decoded.clear()
         fused: Dict[int, List[int]] = {}                           # channel count -> the images the kernel takes

@@ -3386,3 +3386,168 @@ def proposal_recall(img_rank: torch.Tensor, logits: torch.Tensor, boxes: torch.T
     totals = counts.sum(0)
     step("sum")
     return totals, overlaps
+
+
+# --------------------------------------------------------------------------------------
+# Baseline JPEG decoding for the dataset mapper (csrc/jpeg_entropy.h on host threads, csrc/jpeg.hip; jpeg.py is the definition)
+JPEG_FORMATS = {"RGB": _lib.JPEG_RGB, "BGR": _lib.JPEG_BGR, "L": _lib.JPEG_L}
+
+
+def _jpeg_bytes(data) -> bytes:
+    return data if isinstance(data, bytes) else bytes(data)
+
+
+def jpeg_parse(data) -> "_lib.JpegHeader":
+    """The header of a JPEG stream (locov_jpeg_parse; jpeg.parse_jpeg is its definition, field by field): .supported says whether
+    the device decoder takes the stream and .reason (jpeg.REASONS) why not.  Never raises on a malformed stream.  No GPU."""
+    data = _jpeg_bytes(data)
+    header = _lib.JpegHeader()
+    check(_lib.load().locov_jpeg_parse(ctypes.cast(ctypes.c_char_p(data), ctypes.c_void_p), len(data), ctypes.byref(header)), "locov_jpeg_parse")
+    return header
+
+
+class JpegStaged(NamedTuple):
+    """One stream after locov_jpeg_entropy_decode: its header, the stage's status (jpeg.STATUSES; 0: decoded), the staging buffer
+    (scan order) and the bytes its record will take."""
+    header: "_lib.JpegHeader"
+    status: int
+    staging: Optional["object"]
+    record_bytes: int
+
+
+class JpegBatch(NamedTuple):
+    """The packed records of a batch, ready for the upload: `records` is ONE uint8 host buffer (pinned on request) holding, per
+    decoded image, its quantisation tables and its record; `descs` the locov_jpeg_desc fields of the decoded images, `index` their
+    places in the list the batch was made from; `headers` and `status` cover every stream of that list."""
+    records: torch.Tensor
+    descs: List[tuple]           # (width, height, ncomp, hs, vs, record_offset, record_bytes, qt_offset)
+    index: List[int]
+    headers: list
+    status: List[int]
+
+    def record(self, i: int):
+        """The record of stream i (of the original list) as uint32 words, its zero padding included; None if it was not decoded."""
+        if i not in self.index:
+            return None
+        d = self.descs[self.index.index(i)]
+        return self.records.numpy()[d[5]:d[5] + d[6]].view("uint32")
+
+
+def jpeg_entropy_stage(datas: Sequence, headers: Optional[Sequence] = None) -> List[JpegStaged]:
+    """Huffman-decodes the scans of a list of streams on up to min(16, n) host threads (locov_jpeg_entropy_decode; the GIL is
+    released).  A stream whose header is not supported is not decoded (status jpeg.STATUS_UNSUPPORTED).  No GPU."""
+    import numpy as np
+    datas = [_jpeg_bytes(d) for d in datas]
+    n = len(datas)
+    if n == 0:
+        return []
+    lib = _lib.load()
+    heads = (_lib.JpegHeader * n)()
+    for i, d in enumerate(datas):
+        if headers is not None:
+            heads[i] = headers[i]
+        else:
+            check(lib.locov_jpeg_parse(ctypes.cast(ctypes.c_char_p(d), ctypes.c_void_p), len(d), ctypes.byref(heads[i])), "locov_jpeg_parse")
+    need = [int(lib.locov_jpeg_entropy_bytes(ctypes.byref(heads[i]), len(d))) if heads[i].supported else 0 for i, d in enumerate(datas)]
+    staging = [np.empty(max(b, 4), dtype=np.uint8) for b in need]        # (untouched pages cost nothing: the bound is loose)
+    status, sizes = (ctypes.c_int32 * n)(), (ctypes.c_int64 * n)()
+    check(lib.locov_jpeg_entropy_decode(
+        (ctypes.c_void_p * n)(*[ctypes.cast(ctypes.c_char_p(d), ctypes.c_void_p) for d in datas]), (ctypes.c_int64 * n)(*[len(d) for d in datas]),
+        heads, (ctypes.c_void_p * n)(*[s.ctypes.data for s in staging]), (ctypes.c_int64 * n)(*need), n, status, sizes), "locov_jpeg_entropy_decode")
+    return [JpegStaged(_lib.JpegHeader.from_buffer_copy(heads[i]), int(status[i]), staging[i] if status[i] == 0 else None, int(sizes[i]))
+            for i in range(n)]
+
+
+def jpeg_pack(staged: Sequence[JpegStaged], pin_memory: bool = False) -> JpegBatch:
+    """Lays the records of the decoded streams of `staged` out in one host buffer (locov_jpeg_entropy_pack), each behind its
+    quantisation tables; pin_memory: a pinned buffer, for one asynchronous upload.  No GPU work."""
+    import numpy as np
+    staged = list(staged)
+    index = [i for i, s in enumerate(staged) if s.status == 0]
+    descs, at = [], 0
+    for i in index:
+        h = staged[i].header
+        qt_offset, at = at, at + (h.ncomp * 128 + 15) // 16 * 16
+        descs.append((h.width, h.height, h.ncomp, h.comp_h[0], h.comp_v[0], at, staged[i].record_bytes, qt_offset))
+        at += staged[i].record_bytes
+    records = torch.empty(max(at, 16), dtype=torch.uint8, pin_memory=bool(pin_memory))
+    n = len(index)
+    if n:
+        view, base = records.numpy(), records.data_ptr()
+        heads = (_lib.JpegHeader * n)()
+        for k, i in enumerate(index):
+            h = heads[k] = staged[i].header
+            qt = np.stack([np.ctypeslib.as_array(h.qt[h.comp_tq[c]]) for c in range(h.ncomp)]).astype(np.uint16)
+            view[descs[k][7]:descs[k][7] + h.ncomp * 128] = qt.reshape(-1).view(np.uint8)
+            view[descs[k][7] + h.ncomp * 128:descs[k][5]] = 0
+        check(_lib.load().locov_jpeg_entropy_pack(
+            heads, (ctypes.c_void_p * n)(*[staged[i].staging.ctypes.data for i in index]), (ctypes.c_int64 * n)(*[d[6] for d in descs]),
+            (ctypes.c_void_p * n)(*[base + d[5] for d in descs]), n), "locov_jpeg_entropy_pack")
+    return JpegBatch(records, descs, index, [s.header for s in staged], [s.status for s in staged])
+
+
+def jpeg_entropy_decode(datas: Sequence, pin_memory: bool = False) -> JpegBatch:
+    """jpeg_entropy_stage and jpeg_pack of a list of streams: the sparse coefficient records of jpeg.entropy_decode_host, packed for
+    the upload.  Needs no GPU."""
+    return jpeg_pack(jpeg_entropy_stage(datas), pin_memory)
+
+
+def jpeg_decode_records(records: torch.Tensor, descs: Sequence[tuple], fmt: str = "RGB") -> List[torch.Tensor]:
+    """The pixel pipeline (locov_jpeg_decode: two launches, no host read) over records already on the device: `records` is a
+    JpegBatch's buffer as a device tensor, `descs` its descriptors (at most IMAGE_BATCH_MAX_IMAGES).  Returns one fresh uint8
+    [height, width, 3] tensor per descriptor in `fmt` order, or [height, width, 1] for "L" (grey streams only): the bytes of
+    jpeg.decode_jpeg_host.  Every byte of the outputs and every byte of the workspace that is read is written by the call."""
+    descs = list(descs)
+    n = len(descs)
+    if n == 0:
+        return []
+    if fmt not in JPEG_FORMATS:
+        raise ValueError(f"jpeg_decode_records: format {fmt!r} is none of {sorted(JPEG_FORMATS)}")
+    if n > IMAGE_BATCH_MAX_IMAGES:
+        raise ValueError(f"jpeg_decode_records: at most {IMAGE_BATCH_MAX_IMAGES} images per call, got {n}")
+    records = _dev(records, "records", dtype=torch.uint8)
+    table = (_lib.JpegDesc * n)()
+    for t, d in zip(table, descs):
+        t.width, t.height, t.ncomp, t.hs, t.vs, t.record_offset, t.record_bytes, t.qt_offset = [int(v) for v in d]
+        if fmt == "L" and t.ncomp != 1:
+            raise ValueError("jpeg_decode_records: format 'L' takes grey streams only (a colour stream as 'L' is Pillow's conversion)")
+    lib = _lib.load()
+    ws_bytes = int(lib.locov_jpeg_decode_workspace_bytes(table, n))
+    if ws_bytes < 0:
+        raise ValueError("jpeg_decode_records: a descriptor is outside the decoder's sizes and layouts")
+    C = 1 if fmt == "L" else 3
+    outs = [torch.empty((t.height, t.width, C), dtype=torch.uint8, device=records.device) for t in table]
+    workspace = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=records.device)
+    with torch.cuda.device(records.device):
+        check(lib.locov_jpeg_decode(_ptr(records), int(records.numel()), table, n, JPEG_FORMATS[fmt], _ptrs(outs), _ptr(workspace), ws_bytes,
+                                    _stream(records)), "locov_jpeg_decode")
+    return outs
+
+
+def decode_jpeg_images(datas: Sequence, fmt: str = "RGB", device="cuda") -> List[torch.Tensor]:
+    """Baseline JPEG streams (at most IMAGE_BATCH_MAX_IMAGES, any mix of sizes and layouts) -> uint8 [height, width, 3] device
+    tensors in `fmt` order ("L": [height, width, 1], grey streams only): Pillow's bytes, as jpeg.decode_jpeg_host restates them.
+    The scans are Huffman-decoded on host threads into one pinned buffer, uploaded once, and the pixels made in two launches.  A
+    stream the decoder does not take -- an unsupported header, an anomaly in the scan -- raises ValueError naming the reason: the
+    caller takes Pillow for it, with Pillow's error semantics."""
+    from . import jpeg
+    datas = list(datas)
+    if fmt not in JPEG_FORMATS:
+        raise ValueError(f"decode_jpeg_images: format {fmt!r} is none of {sorted(JPEG_FORMATS)}")
+    if len(datas) > IMAGE_BATCH_MAX_IMAGES:
+        raise ValueError(f"decode_jpeg_images: at most {IMAGE_BATCH_MAX_IMAGES} images per call, got {len(datas)}")
+    device = torch.device(device)
+    staged = jpeg_entropy_stage(datas)
+    for i, s in enumerate(staged):                                 # (the refusals come first: they need no GPU)
+        if not s.header.supported:
+            raise ValueError(f"decode_jpeg_images: stream {i}: {jpeg.REASONS[s.header.reason]}")
+        if s.status != 0:
+            raise ValueError(f"decode_jpeg_images: stream {i}: {jpeg.STATUSES[s.status]}")
+        if fmt == "L" and s.header.ncomp != 1:
+            raise ValueError(f"decode_jpeg_images: stream {i}: a colour stream as 'L' is Pillow's conversion, not the decoder's")
+    if device.type != "cuda":
+        raise LocovError(f"decode_jpeg_images: device {device}: the decoder only runs on a ROCm GPU (jpeg.decode_jpeg_host is the host definition)")
+    if not staged:
+        return []
+    batch = jpeg_pack(staged, pin_memory=True)
+    return jpeg_decode_records(batch.records.to(device, non_blocking=True), batch.descs, fmt)

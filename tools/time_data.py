@@ -4,6 +4,7 @@ against Pillow on the same machine; and the resize kernel alone.
     timeout -k 10 600 python tools/time_data.py [--images 1 8] [--iters 50] [--warmup 10] [--threads 16] [--out records.json]
     timeout -k 10 600 python tools/time_data.py --proposals 1000 --images 1 8 32      (the proposal side instead: proposals() below)
     timeout -k 10 600 python tools/time_data.py --strong --images 8                   (the strong augmentation instead: strong() below)
+    timeout -k 10 900 python tools/time_data.py --jpeg --images 8                     (the mapper from JPEG files instead: jpeg() below)
 
 For each source size (480 x 640 and 3000 x 4000, both to 800 x 1067: INPUT.MIN_SIZE_TEST 800, MAX_SIZE_TEST 1333) and batch size:
   (a) kernel     ops.resize_flip_images on images already on the device: device-event time per call, the kernel's device time
@@ -218,8 +219,106 @@ def strong(args, dev):
     return rec
 
 
+def _photo_like(rng, h, w):
+    """A synthetic image with a photograph's spectrum rather than white noise: low-pass noise at three scales plus a little grain."""
+    out = np.zeros((h, w, 3), np.float32)
+    for cell, gain in ((64, 70.0), (16, 35.0), (4, 12.0)):
+        coarse = rng.standard_normal((h // cell + 2, w // cell + 2, 3)).astype(np.float32)
+        t = torch.from_numpy(coarse).permute(2, 0, 1)[None]
+        up = torch.nn.functional.interpolate(t, size=(h, w), mode="bilinear", align_corners=False)[0].permute(1, 2, 0).numpy()
+        out += gain * up
+    out += 128.0 + 3.0 * rng.standard_normal((h, w, 3)).astype(np.float32)
+    return np.clip(out, 0, 255).astype(np.uint8)
+
+
+def jpeg(args, dev):
+    """--jpeg: DatasetMapper.map_batch FROM FILES, the images of the default rows (white noise, 480 x 640 and 3000 x 4000, to
+    800 x 1067) and photograph-like ones of the same sizes, encoded by Pillow at quality 90, 4:2:0.  Per size and content:
+        map_batch    host wall time to the synchronised dicts, the two sides alternating in one process: device (the scans on
+                     host threads, one pinned upload, two launches, then the resize's one) and pillow (LOCOV_FUSED_JPEG=0: the path
+                     before the decoder existed, every file through Pillow on one thread, then the upload of the raw bytes)
+        pillow       Image.open(...).convert("RGB") alone, from memory: one thread, and a pool of --threads threads
+        entropy      ops.jpeg_entropy_stage alone: a call per image (one thread), and one call for the batch (min(16, n) threads)
+        pack / upload   ops.jpeg_pack into the pinned buffer (host wall), and its copy to the device (device-event time)
+        launches     ops.jpeg_decode_records on records already on the device: device-event time per call, each launch's device time
+        bytes        the record's bytes per pixel beside the file's and the raw image's 3"""
+    import io
+    import tempfile
+    import locov_amd
+    from locov_amd import data, ops
+    from PIL import Image
+    cfg = locov_amd.config.get_cfg()
+    cfg.MODEL.DEVICE = str(dev)
+    mapper = data.DatasetMapper(cfg, False, device=dev)
+    rec = {"device": torch.cuda.get_device_name(dev), "quality": 90, "subsampling": "4:2:0", "threads": args.threads, "runs": {}}
+    pool = ThreadPoolExecutor(max_workers=args.threads)
+    N = max(args.images)
+    tmp = tempfile.mkdtemp(prefix="time_data_jpeg_")
+    for h, w in SOURCES:
+        big = h * w > 1 << 21
+        iters, warmup = (args.jpeg_big_iters, 2) if big else (args.iters, args.warmup)
+        for content in ("noise", "photo"):
+            rng = np.random.default_rng(N)
+            raws = [rng.integers(0, 256, (h, w, 3), dtype=np.uint8) if content == "noise" else _photo_like(rng, h, w) for _ in range(N)]
+            datas, dicts = [], []
+            for i, x in enumerate(raws):
+                buf = io.BytesIO()
+                Image.fromarray(x).save(buf, "JPEG", quality=90, subsampling="4:2:0")
+                datas.append(buf.getvalue())
+                path = os.path.join(tmp, f"{content}_{h}x{w}_{i}.jpg")
+                with open(path, "wb") as f:
+                    f.write(datas[-1])
+                dicts.append({"file_name": path, "height": h, "width": w})
+            del raws
+
+            def side(fused):
+                def step():
+                    os.environ["LOCOV_FUSED_JPEG"] = fused
+                    return mapper.map_batch(dicts)
+                return step
+
+            sides = {"device": side("1"), "pillow": side("0")}
+            for a, b in zip(sides["device"](), sides["pillow"]()):
+                assert torch.equal(a["image"], b["image"]), "the device path and Pillow differ"
+            ms = {k: [] for k in sides}
+            names = list(sides)
+            for it in range(warmup + iters):
+                for k in (names if it % 2 == 0 else names[::-1]):
+                    t = wall(sides[k], 1, 0)
+                    if it >= warmup:
+                        ms[k].append(t["median_ms"])
+            os.environ.pop("LOCOV_FUSED_JPEG", None)
+            spread = lambda v: {"median_ms": float(np.median(v)), "p10_ms": float(np.percentile(v, 10)), "p90_ms": float(np.percentile(v, 90))}
+            r = {"images": N, "source": [h, w], "iters": iters, "map_batch": {k: spread(v) for k, v in ms.items()}}
+            pil = lambda d: np.asarray(Image.open(io.BytesIO(d)).convert("RGB"))
+            host_iters = max(args.host_iters, 3)
+            r["pillow"] = {"1_thread": wall(lambda: [pil(d) for d in datas], host_iters, 1),
+                           f"{args.threads}_threads": wall(lambda: list(pool.map(pil, datas)), host_iters, 1)}
+            r["entropy"] = {"1_thread": wall(lambda: [ops.jpeg_entropy_stage([d]) for d in datas], host_iters, 1),
+                            "batched": wall(lambda: ops.jpeg_entropy_stage(datas), host_iters, 1)}
+            staged = ops.jpeg_entropy_stage(datas)
+            assert all(s.status == 0 for s in staged)
+            r["pack"] = wall(lambda: ops.jpeg_pack(staged, pin_memory=True), host_iters, 1)
+            batch = ops.jpeg_pack(staged, pin_memory=True)
+            r["upload"] = alternate({"copy": lambda: batch.records.to(dev, non_blocking=True)}, iters, warmup)["copy"]
+            records = batch.records.to(dev)
+            launch = lambda: ops.jpeg_decode_records(records, batch.descs, cfg.INPUT.FORMAT)
+            r["launches"] = dict(alternate({"call": launch}, iters, warmup)["call"], device=kernels(launch, top=2))
+            pixels = N * h * w
+            r["bytes_per_pixel"] = {"record": batch.records.numel() / pixels, "file": sum(len(d) for d in datas) / pixels, "raw": 3.0}
+            del records, batch, staged
+            rec["runs"][f"{content}_{h}x{w}_images_{N}"] = r
+            print(json.dumps({f"jpeg {content} {h}x{w} images {N}": r}), flush=True)
+    import shutil
+    shutil.rmtree(tmp, ignore_errors=True)
+    return rec
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--jpeg", action="store_true", help="time the mapper from JPEG files instead (see jpeg())")
+    ap.add_argument("--jpeg-big-iters", type=int, default=8, help="--jpeg: timed iterations of the two map_batch sides at 3000 x 4000 (a Pillow "
+                    "side takes seconds per iteration), after two warm-ups")
     ap.add_argument("--strong", action="store_true", help="time the strong augmentation of the mapper instead (see strong())")
     ap.add_argument("--proposals", type=int, default=0, help="rows per image: time the proposal side of the mapper instead (see proposals())")
     ap.add_argument("--images", type=int, nargs="+", default=[1, 8])
@@ -234,10 +333,10 @@ def main(argv=None):
         raise SystemExit("time_data: needs a ROCm GPU")
     if args.iters < 50 or args.warmup < 10:
         raise SystemExit("time_data: the protocol asks for >= 10 warm-up and >= 50 timed iterations")
-    if args.proposals > 0 or args.strong:
+    if args.proposals > 0 or args.strong or args.jpeg:
         dev = torch.device("cuda:0")
         torch.cuda.set_device(dev)
-        rec = strong(args, dev) if args.strong else proposals(args, dev)
+        rec = jpeg(args, dev) if args.jpeg else strong(args, dev) if args.strong else proposals(args, dev)
         if args.out:
             os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
             with open(args.out, "w") as f:
